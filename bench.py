@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- denoising UNet-steps/s of the MI355X-native MoCA-Video hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[1]): VideoCrafter2 3D-UNet, 16 frames x 320x512
@@ -521,6 +521,29 @@ def launch_ranks(n, argv, timeout_s=3000):
     return rc
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, all files together within max_bytes.  An output set larger than
+    that is cut to a fixed sample of each array's elements (seeded: the same positions for the same shape on every run, so that two
+    builds can be compared element for element).  Returns {name: {"shape": full shape, "saved": elements written}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    budget = (max_bytes - 4096 * len(arrays)) // 4                          # (.npy headers: 128 bytes each, well inside 4 KiB)
+    total = sum(a.size for a in arrays.values())
+    info = {}
+    for name, a in arrays.items():
+        shape = list(a.shape)
+        if total > budget:
+            idx = np.random.default_rng(0).choice(a.size, size=a.size * budget // total, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        info[name] = {"shape": shape, "saved": int(a.size)}
+    return info
+
+
 def launcher_selftest(args):
     """`--selftest-cpu`: the multi-rank plumbing of this file WITHOUT the hot path (CPU, gloo): rendezvous from the
     environment, C1 exactly as the GPU job runs it (only rank 0 holds real parameters, the others NaN; timed broadcast;
@@ -587,6 +610,9 @@ def main():
     ap.add_argument("--no-emulate-world", action="store_true",
                     help="skip the default leg that measures rank 0's share of the 8-GPU configs[4] job on this GPU (`emulate_world_8`)")
     ap.add_argument("--selftest-cpu", action="store_true", help="launcher/collective plumbing only (CPU, gloo): see launcher_selftest")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the latents the last timed DDIM step left (every prompt of the run, in prompt-row "
+                         "order) as DIR/latents.npy, float32 (see dump_outputs)")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` with no launcher around it: become the launcher (before anything touches the GPU)
@@ -722,6 +748,11 @@ def main():
 
     if rank != 0:
         return
+    dumped = None
+    if args.dump_outputs:
+        # prompt row p ran on rank p % world as that rank's row p // world (shard_indices); the padding of uneven shards is dropped
+        latents = torch.stack([outs[p % world][p // world] for p in range(N_PROMPTS)]) if world > 1 else img
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, {"latents": latents})}
     n_prompts = (len(rows) if emu else 1) if world == 1 else N_PROMPTS
     if multi is not None:
         multi.update({"prompts_total": N_PROMPTS, "prompts_per_rank": len(rows), "prompts_per_forward": batches[0]["n"],
@@ -785,6 +816,8 @@ def main():
     }
     if multi is not None:
         res["multi_gpu"] = multi
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     if emu:
         res["emulated_world"] = emu
         res["config"]["workload"] = ("1-GPU rehearsal of rank 0 of the %d-GPU configs[4] job: %d prompt rows as %d forward(s) of B=%d per DDIM "

@@ -10,6 +10,8 @@ import numpy as np
 import torch
 import torch.fft as fft
 
+from . import hostmath
+
 
 def _grid(T, H, W, d_s, d_t):
     t = np.arange(T, dtype=np.float64)[:, None, None]
@@ -55,11 +57,11 @@ def prepare_latents(z, ddim_alphas, num_inference_steps, video_length, lookahead
         for i in range(video_length // 2):
             alpha = torch.as_tensor(ddim_alphas[0], dtype=torch.float32)   # a 0-dim fp32 tensor in the reference
             beta = 1 - alpha
-            out.append(alpha ** 0.5 * z[:, :, [0]] + beta ** 0.5 * noises[k]); k += 1
+            out.append(hostmath.sqrt(alpha) * z[:, :, [0]] + hostmath.sqrt(beta) * noises[k]); k += 1
     for i in range(num_inference_steps):
         alpha = torch.as_tensor(ddim_alphas[i], dtype=torch.float32)
         frame_idx = max(0, i - (num_inference_steps - z.shape[2]))
-        out.append(alpha ** 0.5 * z[:, :, [frame_idx]] + (1 - alpha) ** 0.5 * noises[k]); k += 1
+        out.append(hostmath.sqrt(alpha) * z[:, :, [frame_idx]] + hostmath.sqrt(1 - alpha) * noises[k]); k += 1
     return torch.cat(out, dim=2)
 
 

@@ -7,6 +7,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import hostmath
+
 
 # ---- utils_diffusion.py:31-53, ddpm3d.py:113-165,362-376 ----------------------------------
 def ddpm_buffers(timesteps=1000, linear_start=0.00085, linear_end=0.012, scale_a=1, scale_b=0.7, mid_step=400):
@@ -38,16 +40,16 @@ def p_sample_ddim(sch, x, e_c, e_u, cfg, index, noise, use_scale=True):
     a_prev = torch.full(size, sch["ddim_alphas_prev"][index])
     sigma_t = torch.full(size, sch["ddim_sigmas"][index])
     s1m = torch.full(size, sch["ddim_sqrt_one_minus_alphas"][index])
-    pred_x0 = (x - s1m * e_t) / a_t.sqrt()
-    dir_xt = (1. - a_prev - sigma_t ** 2).sqrt() * e_t
+    pred_x0 = (x - s1m * e_t) / hostmath.sqrt(a_t)
+    dir_xt = hostmath.sqrt(1. - a_prev - sigma_t ** 2) * e_t
     nz = sigma_t * noise
     if use_scale:
         scale_t = torch.full(size, sch["ddim_scale_arr"][index])
         scale_prev = torch.full(size, sch["ddim_scale_arr_prev"][index])
         pred_x0 = pred_x0 / scale_t
-        x_prev = a_prev.sqrt() * scale_prev * pred_x0 + dir_xt + nz
+        x_prev = hostmath.sqrt(a_prev) * scale_prev * pred_x0 + dir_xt + nz
     else:
-        x_prev = a_prev.sqrt() * pred_x0 + dir_xt + nz
+        x_prev = hostmath.sqrt(a_prev) * pred_x0 + dir_xt + nz
     return x_prev, pred_x0
 
 
@@ -113,8 +115,8 @@ def ddim_step(sch, sample, noise_pred, indices, cond_image, ts, noises, momentum
         a_prev = torch.full(size, sch["ddim_alphas_prev"][index])
         sigma_t = torch.full(size, sch["ddim_sigmas"][index])
         s1m = torch.full(size, sch["ddim_sqrt_one_minus_alphas"][index])
-        pred_x0 = (x - s1m * e_t) / a_t.sqrt()                         # :415
-        dir_xt = (1. - a_prev - sigma_t ** 2).sqrt() * e_t             # :418
+        pred_x0 = (x - s1m * e_t) / hostmath.sqrt(a_t)                  # :415
+        dir_xt = hostmath.sqrt(1. - a_prev - sigma_t ** 2) * e_t        # :418
         mi = i
         if prev_frame is not None:
             g = pred_x0 - prev_frame                                   # :422
@@ -126,7 +128,7 @@ def ddim_step(sch, sample, noise_pred, indices, cond_image, ts, noises, momentum
                 mi = len(range(0, H, 4)) - 1     # plotting loops `for i in range(len(X))` clobber i (:477,502,533)
         prev_frame = pred_x0                                            # :559
         noise = sigma_t * noises[i]                                     # :561
-        x_prev = a_prev.sqrt() * pred_x0 + dir_xt + noise               # :562
+        x_prev = hostmath.sqrt(a_prev) * pred_x0 + dir_xt + noise       # :562
         if davis_masks is not None and davis_masks.shape[2] > mi:       # :565
             mask = davis_masks[:, :, mi, :, :].unsqueeze(0)
             mask = mask.expand(-1, pred_x0.shape[1], -1, -1, -1)

@@ -20,11 +20,13 @@ import math
 import torch
 import torch.nn.functional as F
 
+from . import hostmath
+
 
 # ---- utils_diffusion.py:8-28 ---------------------------------------------------------
 def timestep_embedding(timesteps, dim, max_period=10000):
     half = dim // 2
-    freqs = torch.exp(-math.log(max_period) * torch.arange(start=0, end=half, dtype=torch.float32) / half)
+    freqs = hostmath.exp(-math.log(max_period) * torch.arange(start=0, end=half, dtype=torch.float32) / half)
     args = timesteps[:, None].float() * freqs[None]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     if dim % 2:

@@ -30,6 +30,15 @@ def golden(name):
     return np.load(os.path.join(GOLD, name + ".npz"))
 
 
+def golden_host_math():
+    """`with golden_host_math():` -- the oracle's per-step float32 sqrt / exp return what the host that made the goldens computed
+    (oracle/hostmath.py, tests/golden/host_math_f32.npz): torch's last bit differs between CPU vendors, and a bit-exact comparison
+    with a golden must not depend on the host it runs on"""
+    from oracle import hostmath
+    g = golden("host_math_f32")
+    return hostmath.pinned({k: (g[k + "_x"], g[k + "_y"]) for k in ("sqrt", "exp")})
+
+
 def state_dict_for(module, seed):
     """weightgen parameters for a module built by OUR classes (same keys/shapes as the reference)."""
     return gen_state_dict({k: v.shape for k, v in module.state_dict().items()}, seed)

@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import golden, inp, relerr
+from helpers import golden, golden_host_math, inp, relerr
 from oracle import freeinit_oracle as FO
 from oracle import sampler_oracle as SO
 
@@ -23,8 +23,9 @@ def test_p_sample_ddim():
     sch = SO.make_schedule(BUF, 50, 1.0)
     shape = (1, 4, 8, 16, 24)
     for index in (49, 20, 0):
-        xp, p0 = SO.p_sample_ddim(sch, inp(f"ps.x{index}", shape), inp(f"ps.ec{index}", shape), inp(f"ps.eu{index}", shape),
-                                  12.0, index, inp(f"ps.nz{index}", shape))
+        with golden_host_math():
+            xp, p0 = SO.p_sample_ddim(sch, inp(f"ps.x{index}", shape), inp(f"ps.ec{index}", shape), inp(f"ps.eu{index}", shape),
+                                      12.0, index, inp(f"ps.nz{index}", shape))
         assert torch.equal(xp, torch.from_numpy(g[f"i{index}_x_prev"]))
         assert torch.equal(p0, torch.from_numpy(g[f"i{index}_pred_x0"]))
 
@@ -48,7 +49,8 @@ def test_ddim_step(tag, dims):
     for call in (0, 1):
         x, e, noises, cond, mask = ddim_step_inputs(tag, C, F, H, W, call)
         ts = torch.from_numpy(g[f"c{call}_ts"]).long()
-        xp, p0 = SO.ddim_step(sch, x, e, g[f"c{call}_indices"], cond, ts, noises, momentum, davis_masks=mask)
+        with golden_host_math():
+            xp, p0 = SO.ddim_step(sch, x, e, g[f"c{call}_indices"], cond, ts, noises, momentum, davis_masks=mask)
         assert torch.equal(xp, torch.from_numpy(g[f"c{call}_x_prev"]))
         assert torch.equal(p0, torch.from_numpy(g[f"c{call}_pred_x0"]))
         assert torch.equal(momentum, torch.from_numpy(g[f"c{call}_momentum"]))
@@ -103,7 +105,8 @@ def test_ddim_step_sam_branch_vs_reference(key, seq):
     noises = noises + [inp(f"ds.small.nz0.{i}", (1, C, 1, H, W)) for i in range(len(noises), F)]
     x, e = inp("ds.small.x0", (1, C, F, H, W)), inp("ds.small.e0", (1, C, F, H, W))
     mom = torch.zeros(1, C, F, H, W)
-    xp, p0 = SO.ddim_step(sch, x, e, idx, cond, torch.from_numpy(tsn).long(), noises, mom, sam_masks=sam_candidates(F, H, W, seq))
+    with golden_host_math():
+        xp, p0 = SO.ddim_step(sch, x, e, idx, cond, torch.from_numpy(tsn).long(), noises, mom, sam_masks=sam_candidates(F, H, W, seq))
     assert torch.equal(xp, xp_g)
     assert torch.equal(p0, p0_g)
 
@@ -131,8 +134,37 @@ def test_fifo_queue():
     n_prep = int(g["n_noise_prepare"])
     assert n_prep == 72 and int(g["n_noise_total"]) == 73
     noises = [inp(f"fifo.nz{i}", (1, 4, 1, 8, 12)) for i in range(n_prep)]
-    lat = FO.prepare_latents(z, sch["ddim_alphas"], 64, 16, True, noises)
+    with golden_host_math():
+        lat = FO.prepare_latents(z, sch["ddim_alphas"], 64, 16, True, noises)
     assert torch.equal(lat, torch.from_numpy(g["prepared"]))
     sh = FO.shift_latents(lat.clone(), inp("fifo.nz72", (1, 4, 8, 12)))
     assert relerr(sh, g["shifted"]) < 1e-6
     assert torch.equal(sh[:, :, :-1], lat[:, :, 1:])
+
+
+def test_host_math_default_is_torch_and_pinned_table_is_strict():
+    from oracle import hostmath
+    a = torch.rand(1000) + 0.01
+    assert torch.equal(hostmath.sqrt(a), a.sqrt()) and torch.equal(hostmath.exp(-a), torch.exp(-a))
+    with golden_host_math():
+        with pytest.raises(KeyError):
+            hostmath.sqrt(torch.tensor([0.123]))
+
+
+def test_golden_checks_do_not_use_this_hosts_sqrt_exp(monkeypatch):
+    """another CPU's torch (last bit of float32 sqrt / exp off) must still reproduce the goldens bit for bit: with this host's
+    torch.sqrt / torch.exp moved by one ulp, the pinned oracle still matches them"""
+    from oracle import unet_oracle as UO
+    sqrt, exp = torch.sqrt, torch.exp
+    monkeypatch.setattr(torch, "sqrt", lambda t: torch.nextafter(sqrt(t), torch.full_like(t, 2.0)))
+    monkeypatch.setattr(torch, "exp", lambda t: torch.nextafter(exp(t), torch.zeros_like(t)))
+    g = golden("sampler_ddim_step_small")
+    sch = SO.make_schedule(BUF, 64, 1.0)
+    x, e, noises, cond, mask = ddim_step_inputs("small", 4, 6, 16, 16, 0)
+    with golden_host_math():
+        xp, p0 = SO.ddim_step(sch, x, e, g["c0_indices"], cond, torch.from_numpy(g["c0_ts"]).long(), noises, torch.zeros(1, 4, 6, 16, 16),
+                              davis_masks=mask)
+        te = golden("timestep_embedding")
+        y = UO.timestep_embedding(torch.from_numpy(te["t"]), 320)
+    assert torch.equal(xp, torch.from_numpy(g["c0_x_prev"])) and torch.equal(p0, torch.from_numpy(g["c0_pred_x0"]))
+    assert relerr(y, te["y"]) < 1e-6

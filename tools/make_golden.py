@@ -739,6 +739,22 @@ def loop_cases():
         os.chdir(cwd)
 
 
+def host_math_cases():
+    """torch's float32 sqrt / exp on THIS host (the one that made the goldens) for every argument the oracle takes them of in the
+    bit-exact golden tests (oracle/hostmath.py): the per-step schedule scalars of S = 50 / 64 and the frequencies of a 320-wide
+    timestep embedding.  Each sqrt is taken of a one-element tensor, as the oracle takes it; the frequencies as one vector."""
+    import math
+    from oracle import sampler_oracle as SO
+    args = []
+    for S in (50, 64):
+        sch = SO.make_schedule(SO.ddpm_buffers(), S, 1.0)
+        a, ap, sg = (torch.tensor(np.asarray(sch[k], np.float64)).float() for k in ("ddim_alphas", "ddim_alphas_prev", "ddim_sigmas"))
+        args += [a, ap, 1. - ap - sg ** 2, 1 - a]
+    x = torch.unique(torch.cat(args))
+    e = -math.log(10000) * torch.arange(start=0, end=160, dtype=torch.float32) / 160
+    save("host_math_f32", sqrt_x=x, sqrt_y=torch.cat([v.reshape(1).sqrt() for v in x]), exp_x=e, exp_y=torch.exp(e))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--full", action="store_true")
@@ -746,7 +762,7 @@ def main():
     a = ap.parse_args()
     torch.set_num_threads(8)
     om, att = import_reference()
-    todo = a.only.split(",") if a.only else ["blocks", "reduced", "sampler", "sam", "freeinit", "fifo", "vae", "loop"] + (["full"] if a.full else [])
+    todo = a.only.split(",") if a.only else ["blocks", "reduced", "sampler", "sam", "freeinit", "fifo", "vae", "loop", "host_math"] + (["full"] if a.full else [])
     if "blocks" in todo: blocks(om, att)
     if "reduced" in todo: unet_reduced(om)
     if "sampler" in todo: sampler_cases()
@@ -755,6 +771,7 @@ def main():
     if "fifo" in todo: fifo_cases()
     if "vae" in todo: vae_cases()
     if "loop" in todo: loop_cases()
+    if "host_math" in todo: host_math_cases()
     if "full" in todo: unet_full(om)
     if "fullN" in todo: unet_full(om, only_cfgN=True)
     if "fullB16" in todo: unet_full_b16(om)
