@@ -266,6 +266,19 @@ int moca_attention_f16(const void* q, const void* k, const void* v, void* out,
                        int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
                        int32_t kv_div, float scale, void* stream);
 
+/* Image cross-attention (attention.py:82-87,117-124, img_cross_attention=True) in ONE launch: per (video, head)
+ *   out = softmax(Q K^T * scale) V + ip_scale * softmax(Q K_ip^T * scale) V_ip
+ * with two separate softmaxes.  k, v: [Bq / kv_div][Nt][ldk / ldv] (the text tokens); k_ip, v_ip:
+ * [Bq / kv_div][Ni][ldk_ip / ldv_ip] (the image tokens); q, out as in moca_attention_f16.  Limits
+ * (one key tile, image rows at a fixed tile row 80): Ni == 0 and 1 <= Nt <= 96 (then it is
+ * moca_attention_f16 bit for bit), or 1 <= Nt <= 80 and 1 <= Ni <= 16.  ip_scale finite and
+ * |ip_scale| <= 64.  Pointers 16-byte aligned, every stride a multiple of 8 halves >= heads * 64.
+ * MOCA_E_BADARG otherwise.                                                         */
+int moca_attention_ip_f16(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* out,
+                          int32_t Bq, int32_t heads, int32_t Nq, int32_t Nt, int32_t Ni,
+                          int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldk_ip, int32_t ldv_ip, int32_t ldo,
+                          int32_t kv_div, float scale, float ip_scale, void* stream);
+
 /* Causal self-attention, head dim 64: query i attends to keys 0..i (the text tower of the OpenCLIP encoder,
  * condition.py:205-212: `text_transformer_forward(x, attn_mask=self.model.attn_mask)`); q/k/v/out as above, N = Nq = Nk. */
 int moca_attention_causal_f16(const void* q, const void* k, const void* v, void* out,

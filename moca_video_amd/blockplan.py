@@ -45,6 +45,9 @@ class BlockRunner:
         _PlanBase.__init__(pl, host, dev)
         pl.B, pl.T, pl.H, pl.W, pl.L, pl.BT = B, T, H, W, L, B * T
         pl.segs, pl.ctx_rows = [(B, L)], B * L
+        pl.image_attn = False
+        if any(getattr(m, "img_cross_attention", False) for m in block.modules()):
+            raise NotImplementedError("BlockRunner: image cross-attention blocks run inside the whole UNet only")
         self.plan = pl
         P = host._packed
         if isinstance(block, _ResBlock):

@@ -237,10 +237,24 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
 // between), plain softmax (no running maximum), and K / V staged ONCE per block for `q_iters` consecutive 128-query groups
 // (the general kernel re-stages them per 128 queries: 20 times per (frame, head) at 2560 tokens).  Fragment maps and LDS images
 // are those of attention_kernel.
+//
+// IP (moca_attention_ip_f16, the img_cross_attention of attention.py:82-87,117-124): the tile holds TWO contexts, text keys from k / v
+// in rows [0, Nt) and image keys from k_ip / v_ip in rows [IP_ROW0, IP_ROW0 + Ni) = [80, 96), and the block computes
+//   softmax(q k^T s) v + ip_scale * softmax(q k_ip^T s) v_ip
+// with two separate softmaxes: row maximum and row sum are taken per segment, and the image segment's P is multiplied by
+// ip_scale * l_text / l_img before its fp16 conversion, so that the one P.V MFMA chain and the 1 / l_text epilogue finish both.
+// The image rows start at a fixed multiple of 8: a lane's score register r of sub-tile `sub` holds key 32 sub + 8 (r >> 2) + 4 fh +
+// (r & 3), so with the segment boundary on an 8-key group every register belongs to one segment at COMPILE time, the same for all
+// lanes (a boundary at a runtime Nt costs a lane mask per register, 48 of them live across the softmax: SGPR spills).  Hence
+// Nt <= 80 and Ni <= 16, which covers the reference's 77 text tokens + 16 (Resampler) or 4 (ImageProjModel) image tokens.
+// (The IP = false instance ignores k_ip, v_ip, ldk_ip, ldv_ip, Nt and ip_scale; for IP = true, Nk = IP_ROW0 + Ni.)
 constexpr int KS96 = 96;
+constexpr int IP_ROW0 = 80;
+template <bool IP>
 __global__ __launch_bounds__(256, 2) void attention_short_kernel(
     const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v, half_t* __restrict__ out,
-    int heads, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, int kv_div, float scale_log2e, int q_iters) {
+    int heads, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, int kv_div, float scale_log2e, int q_iters,
+    const half_t* __restrict__ k_ip, const half_t* __restrict__ v_ip, int ldk_ip, int ldv_ip, int Nt, float ip_scale) {
     __shared__ __attribute__((aligned(16))) char sK[KS96 * ROWB];
     __shared__ __attribute__((aligned(16))) char sV[KS96 * ROWB];
     // Q rows in / O rows out pass through a per-wave LDS tile (32 rows x 128 B, chunk ^ ((row >> 1) & 7)): the global accesses are
@@ -254,17 +268,22 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
     const int bkv = bq / kv_div;
     const int fr = lane & 31, fh = lane >> 5;
     const half_t* qb = q + (int64_t)bq * Nq * ldq + head * D;
-    const half_t* kb = k + (int64_t)bkv * Nk * ldk + head * D;
-    const half_t* vb = v + (int64_t)bkv * Nk * ldv + head * D;
-    {   // stage K and V (rows >= Nk are zero; they are masked below)
+    const int Ntx = IP ? Nt : Nk;                          // text keys per video (all of them unless IP)
+    const half_t* kb = k + (int64_t)bkv * Ntx * ldk + head * D;
+    const half_t* vb = v + (int64_t)bkv * Ntx * ldv + head * D;
+    {   // stage K and V (rows >= Nk are zero; they are masked below); IP: rows [Nt, Nk) are the image tokens' k_ip / v_ip
         const int cc = tid & 7, r0 = tid >> 3;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int row = r0 + 32 * i;
             half8v a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (row < Nk) {
+            if (row < Ntx) {
                 a = *reinterpret_cast<const half8v*>(kb + (int64_t)row * ldk + cc * 8);
                 b = *reinterpret_cast<const half8v*>(vb + (int64_t)row * ldv + cc * 8);
+            } else if (IP && row >= IP_ROW0 && row < Nk) {
+                const int Ni = Nk - IP_ROW0, ri = row - IP_ROW0;
+                a = *reinterpret_cast<const half8v*>(k_ip + ((int64_t)bkv * Ni + ri) * ldk_ip + head * D + cc * 8);
+                b = *reinterpret_cast<const half8v*>(v_ip + ((int64_t)bkv * Ni + ri) * ldv_ip + head * D + cc * 8);
             }
             *reinterpret_cast<half8v*>(sK + row * ROWB + ((cc ^ ((row >> 1) & 7)) << 4)) = a;
             *reinterpret_cast<half8v*>(sV + row * ROWB + ((cc ^ (((row >> 1) & 1) << 2)) << 4)) = b;
@@ -313,26 +332,67 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
             }
         }
         float tmax = -INFINITY;
-#pragma unroll
-        for (int sub = 0; sub < 3; ++sub)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                if (key >= Nk) s[sub][r] = -INFINITY;
-                tmax = fmaxf(tmax, s[sub][r]);
-            }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float mb = tmax * scale_log2e;
-        float psum = 0.f;
         half8v pf[3][2];
+        float inv;
+        if constexpr (!IP) {
 #pragma unroll
-        for (int sub = 0; sub < 3; ++sub)
+            for (int sub = 0; sub < 3; ++sub)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pv = __builtin_amdgcn_exp2f(s[sub][r] * scale_log2e - mb);
-                psum += pv;
-                pf[sub][r >> 3][r & 7] = (half_t)pv;
-            }
+                for (int r = 0; r < 16; ++r) {
+                    const int key = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    if (key >= Nk) s[sub][r] = -INFINITY;
+                    tmax = fmaxf(tmax, s[sub][r]);
+                }
+            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+            const float mb = tmax * scale_log2e;
+            float psum = 0.f;
+#pragma unroll
+            for (int sub = 0; sub < 3; ++sub)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float pv = __builtin_amdgcn_exp2f(s[sub][r] * scale_log2e - mb);
+                    psum += pv;
+                    pf[sub][r >> 3][r & 7] = (half_t)pv;
+                }
+            inv = 1.0f / (psum + __shfl_xor(psum, 32, 64));
+        } else {
+            // per-segment maxima: registers of sub-tiles 0, 1 and r < 8 of sub-tile 2 are text keys (< 80), the rest image keys
+            float imax = -INFINITY;
+#pragma unroll
+            for (int sub = 0; sub < 3; ++sub)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    const bool txt = sub < 2 || r < 8;                       // compile time
+                    if (txt ? key >= Nt : key >= Nk) s[sub][r] = -INFINITY;
+                    if (txt) tmax = fmaxf(tmax, s[sub][r]);
+                    else imax = fmaxf(imax, s[sub][r]);
+                }
+            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+            imax = fmaxf(imax, __shfl_xor(imax, 32, 64));
+            const float mb = tmax * scale_log2e, mbi = imax * scale_log2e;
+            float psum = 0.f, isum = 0.f;
+#pragma unroll
+            for (int sub = 0; sub < 3; ++sub)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const bool txt = sub < 2 || r < 8;
+                    const float pv = __builtin_amdgcn_exp2f(s[sub][r] * scale_log2e - (txt ? mb : mbi));
+                    if (txt) psum += pv;
+                    else isum += pv;
+                    s[sub][r] = pv;
+                }
+            const float lt = psum + __shfl_xor(psum, 32, 64), li = isum + __shfl_xor(isum, 32, 64);
+            const float fi = ip_scale * lt / li;              // image P in units of the text row sum
+#pragma unroll
+            for (int sub = 0; sub < 3; ++sub)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const bool txt = sub < 2 || r < 8;
+                    pf[sub][r >> 3][r & 7] = (half_t)(txt ? s[sub][r] : s[sub][r] * fi);
+                }
+            inv = 1.0f / lt;
+        }
         f32x16 o[2];
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
@@ -354,7 +414,6 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
                     o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[sub][ss], o[dt], 0, 0, 0);
                 }
             }
-        const float inv = 1.0f / (psum + __shfl_xor(psum, 32, 64));
         // O^T[d = 32 dt + 8 g + 4 fh + j][query fr] -> row fr of the wave's LDS tile (the Q fragments are in registers), then whole rows out
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
@@ -731,6 +790,24 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(
     }
 }
 
+template <bool IP>
+void launch_short(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* out, int Bq, int heads, int Nq,
+                  int Nt, int Nk, int ldq, int ldk, int ldv, int ldk_ip, int ldv_ip, int ldo, int kv_div, float scale, float ip_scale,
+                  void* stream) {
+    // query groups of 128 per block: as many as keep >= ~3 blocks per CU in the launch (K / V are staged once per block)
+    const int qgroups = (Nq + QB - 1) / QB;
+    int q_iters = (int)(((int64_t)qgroups * Bq * heads) / 768);
+    if (q_iters < 1) q_iters = 1;
+    if (q_iters > 8) q_iters = 8;
+    if (q_iters > qgroups) q_iters = qgroups;
+    const dim3 grid_s((qgroups + q_iters - 1) / q_iters, Bq * heads), block(256);
+    hipLaunchKernelGGL(attention_short_kernel<IP>, grid_s, block, 0, moca_stream(stream),
+                       reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
+                       reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
+                       heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale * 1.4426950408889634f, q_iters,
+                       reinterpret_cast<const half_t*>(k_ip), reinterpret_cast<const half_t*>(v_ip), ldk_ip, ldv_ip, Nt, ip_scale);
+}
+
 }  // namespace
 
 extern "C" int moca_attention_f16(const void* q, const void* k, const void* v, void* out,
@@ -754,17 +831,7 @@ extern "C" int moca_attention_f16(const void* q, const void* k, const void* v, v
         return MOCA_OK;
     }
     if (Nk <= KS96) {
-        // query groups of 128 per block: as many as keep >= ~3 blocks per CU in the launch (K / V are staged once per block)
-        const int qgroups = (Nq + QB - 1) / QB;
-        int q_iters = (int)(((int64_t)qgroups * Bq * heads) / 768);
-        if (q_iters < 1) q_iters = 1;
-        if (q_iters > 8) q_iters = 8;
-        if (q_iters > qgroups) q_iters = qgroups;
-        const dim3 grid_s((qgroups + q_iters - 1) / q_iters, Bq * heads);
-        hipLaunchKernelGGL(attention_short_kernel, grid_s, block, 0, moca_stream(stream),
-                           reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
-                           reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
-                           heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale * 1.4426950408889634f, q_iters);
+        launch_short<false>(q, k, v, nullptr, nullptr, out, Bq, heads, Nq, Nk, Nk, ldq, ldk, ldv, 0, 0, ldo, kv_div, scale, 0.f, stream);
         MOCA_CHECK_LAUNCH();
         return MOCA_OK;
     }
@@ -772,6 +839,29 @@ extern "C" int moca_attention_f16(const void* q, const void* k, const void* v, v
                        reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
                        reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
                        heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale * 1.4426950408889634f);
+    MOCA_CHECK_LAUNCH();
+    return MOCA_OK;
+}
+
+extern "C" int moca_attention_ip_f16(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* out,
+                                     int32_t Bq, int32_t heads, int32_t Nq, int32_t Nt, int32_t Ni,
+                                     int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldk_ip, int32_t ldv_ip, int32_t ldo,
+                                     int32_t kv_div, float scale, float ip_scale, void* stream) {
+    auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    if (!q || !k || !v || !k_ip || !v_ip || !out) return MOCA_E_BADARG;
+    if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(k_ip) || misaligned(v_ip) || misaligned(out)) return MOCA_E_BADARG;
+    if (Bq <= 0 || heads <= 0 || Nq <= 0 || Nt < 1 || Ni < 0 || Nt + Ni > KS96 || kv_div <= 0 || Bq % kv_div) return MOCA_E_BADARG;
+    if (Ni > 0 && (Nt > IP_ROW0 || Ni > KS96 - IP_ROW0)) return MOCA_E_BADARG;     // the fixed text / image rows of the tile
+    if (ldq % 8 || ldk % 8 || ldv % 8 || ldk_ip % 8 || ldv_ip % 8 || ldo % 8) return MOCA_E_BADARG;
+    if (ldq < heads * D || ldk < heads * D || ldv < heads * D || ldk_ip < heads * D || ldv_ip < heads * D || ldo < heads * D)
+        return MOCA_E_BADARG;
+    // |ip_scale| <= 64: the scaled image P (<= ip_scale * l_text <= 64 * 80) stays far inside the fp16 range; rejects inf and NaN too
+    if ((int64_t)Bq * heads > 65535 || !(fabsf(ip_scale) <= 64.f)) return MOCA_E_BADARG;
+    if (Ni == 0)   // no image tokens (a 77-token context): exactly moca_attention_f16's launch, bit for bit
+        launch_short<false>(q, k, v, nullptr, nullptr, out, Bq, heads, Nq, Nt, Nt, ldq, ldk, ldv, 0, 0, ldo, kv_div, scale, 0.f, stream);
+    else
+        launch_short<true>(q, k, v, k_ip, v_ip, out, Bq, heads, Nq, Nt, IP_ROW0 + Ni, ldq, ldk, ldv, ldk_ip, ldv_ip, ldo, kv_div, scale,
+                           ip_scale, stream);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }

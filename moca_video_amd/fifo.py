@@ -78,6 +78,15 @@ def shift_latents(latents, davis_data=None, model=None, noise=None, anchor_noise
     return latents, (frames, masks)
 
 
+def refuse_image_attention(model):
+    """The MoCA loop's two-prompt context is 154 tokens; an image-attention UNet would split it 77 / 77 into "text" and "image"
+    tokens by the reference's rule (attention.py:82-84).  That mode is not supported: raise instead of computing it."""
+    unet = getattr(getattr(model, "model", None), "diffusion_model", None)
+    if getattr(unet, "use_image_attention", False):
+        raise NotImplementedError("FIFO / MoCA sampling with an image-attention UNet (use_image_attention=True) is not supported: "
+                                  "its 154-token two-prompt context would be read as 77 text + 77 image tokens")
+
+
 def uncond_embedding(model, c_emb, uc_emb):
     """The unconditional context of funcs.py:199-208 / :268-270: `model.uncond_type == "empty_seq"` (the YAML's value) is
     the text encoding of the EMPTY PROMPT -- it needs the text encoder, so the caller must pass it (`uc_emb`, e.g.
@@ -107,6 +116,9 @@ def base_ddim_sampling(model, cond, noise_shape, ddim_steps=50, ddim_eta=1.0, cf
     if cfg_scale != 1.0:
         c_emb = cond["c_crossattn"][0] if isinstance(cond, dict) else cond
         uc_emb = uncond_embedding(model, c_emb, uc_emb)   # model.uncond_type (:199-206)
+        if hasattr(model, "embedder"):                    # image-conditioned model (:207-210): + the embedding of a zero image
+            uc_img = model.get_image_embeds(torch.zeros(noise_shape[0], 3, 224, 224, device=model.device))
+            uc_emb = torch.cat([uc_emb, uc_img], dim=1)
         if isinstance(cond, dict):
             uc = {key: cond[key] for key in cond.keys()}
             uc.update({'c_crossattn': [uc_emb]})
@@ -147,6 +159,7 @@ def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg
     `noises[i][w]` / `shift_noises[i]` optionally fix the per-window DDIM noise and the enqueued noise (else: device Philox
     stream keyed by `seed` on the graph path, torch.randn on the host path)."""
     kwargs.update({"clean_cond": True})
+    refuse_image_attention(model)
     cond = conditioning
     uc = None
     if cfg_scale != 1.0:

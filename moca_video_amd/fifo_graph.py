@@ -67,6 +67,8 @@ class FifoEngine:
         """sam_capacity > 0 (and no `masks`): prompt mode with precomputed Grounded-SAM-2 candidates -- `ddim_step`'s segmentation
         branch (ddim.py:592-606 -> `_apply_segmentation` :739-903) runs inside the iteration graph on at most `sam_capacity`
         candidate masks per iteration, handed to `step(sam_masks=...)`."""
+        from .fifo import refuse_image_attention
+        refuse_image_attention(model)
         self.unet = unet = model.model.diffusion_model
         dev = latents.device
         self.device = dev

@@ -373,6 +373,16 @@ def attention(q, k, v, out, *, Bq, heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, sc
     return out
 
 
+def attention_ip(q, k, v, k_ip, v_ip, out, *, Bq, heads, Nq, Nt, Ni, ldq, ldk, ldv, ldk_ip, ldv_ip, ldo, kv_div, scale,
+                 ip_scale=1.0):
+    """softmax(q k^T s) v + ip_scale softmax(q k_ip^T s) v_ip in one launch (text keys k / v, image keys k_ip / v_ip).  Limits: Ni == 0 and
+    Nt <= 96 (= `attention`, bit for bit), or Nt <= 80 and Ni <= 16; |ip_scale| <= 64 (include/moca_hip.h)"""
+    _l.check(_l.load().moca_attention_ip_f16(_l.ptr(q), _l.ptr(k), _l.ptr(v), _l.ptr(k_ip), _l.ptr(v_ip), _l.ptr(out), Bq, heads, Nq,
+                                             Nt, Ni, ldq, ldk, ldv, ldk_ip, ldv_ip, ldo, kv_div, scale, ip_scale, _st()),
+             "moca_attention_ip_f16")
+    return out
+
+
 def temporal_attention(q, k, v, out, *, B, T, HW, heads, ld_qkv, ldo, scale):
     _l.check(_l.load().moca_temporal_attention_f16(_l.ptr(q), _l.ptr(k), _l.ptr(v), _l.ptr(out), B, T, HW, heads,
                                                    ld_qkv, ldo, scale, _st()), "moca_temporal_attention_f16")

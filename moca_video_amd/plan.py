@@ -20,8 +20,8 @@ import torch
 
 from . import lib as _l
 from . import ops
-from .unet import (_BasicTransformerBlock, _CatMap, _Downsample, _FMap, _Pool, _ResBlock, _SpatialTransformer,
-                   _TemporalTransformer, _Upsample)
+from .unet import (IMAGE_CONTEXT_MAX, TEXT_CONTEXT_LEN, _BasicTransformerBlock, _CatMap, _Downsample, _FMap, _Pool, _ResBlock,
+                   _SpatialTransformer, _TemporalTransformer, _Upsample)
 
 N_CU = 256
 
@@ -390,6 +390,12 @@ class _Plan(_PlanBase):
         classifier-free guidance, ddim.py:298-299,366-369, on one x): `x_in` holds the distinct latents only, everything up to the
         first cross-attention (conv_in, init_attn, the first ResBlock, the first SpatialTransformer's self-attention and to_q:
         8 % of the forward) is computed once and repeated where the contexts first enter (`_expand`)."""
+        self.image_attn = getattr(model, "use_image_attention", False)
+        if self.image_attn:
+            for Ls in ([L] if isinstance(L, int) else [l for _, l in L]):
+                if Ls > IMAGE_CONTEXT_MAX:
+                    raise ValueError(f"image-attention UNet: a context of {Ls} tokens is longer than {IMAGE_CONTEXT_MAX} ({TEXT_CONTEXT_LEN} "
+                                     f"text + {IMAGE_CONTEXT_MAX - TEXT_CONTEXT_LEN} image tokens, the fused attention's key tile)")
         super().__init__(model, device)
         self.B, self.T, self.H, self.W, self.L = B, T, H, W, L
         self.BT = B * T
@@ -398,8 +404,15 @@ class _Plan(_PlanBase):
         # launch per segment on its own rows of the shared K|V projection -- no padded or masked keys
         self.segs = [(B, L)] if isinstance(L, int) else [(int(n), int(l)) for n, l in L]
         assert sum(n for n, _ in self.segs) == B
-        self.ctx_rows = sum(n * l for n, l in self.segs)
         m = model
+        # image cross-attention (use_image_attention): the first 77 rows of a context are text, the rest image tokens (attention.py:82-84);
+        # `ctx` holds the text rows of every video, `ctx_img` the image rows, each projected by its own up-front K|V GEMM
+        if self.image_attn:
+            self.seg_txt = [min(Ls, TEXT_CONTEXT_LEN) for _, Ls in self.segs]
+        else:
+            self.seg_txt = [Ls for _, Ls in self.segs]
+        self.ctx_rows = sum(n * lt for (n, _), lt in zip(self.segs, self.seg_txt))
+        self.img_rows = sum(n * (l - lt) for (n, l), lt in zip(self.segs, self.seg_txt))
         if shared_x:
             assert len(self.segs) > 1 and all(n == self.segs[0][0] for n, _ in self.segs)
             self.reps = len(self.segs)
@@ -408,6 +421,7 @@ class _Plan(_PlanBase):
         self.t_rows = torch.empty(self.BT, dtype=torch.int64, device=device)
         self.fps_rows = torch.empty(self.BT, dtype=torch.int64, device=device)
         self.ctx = torch.empty(self.ctx_rows, m.context_dim, dtype=torch.float16, device=device)
+        self.ctx_img = torch.empty(self.img_rows, m.context_dim, dtype=torch.float16, device=device) if self.img_rows else None
         self.out = torch.empty(B, m.out_channels, T, H, W, dtype=in_dtype, device=device)
         self._build()
 
@@ -555,18 +569,30 @@ class _Plan(_PlanBase):
         off, inner = self.model._kv_cols[id(att)]                # one K/V per video (context.repeat_interleave, :547),
         ld = self.kv_all.shape[1]                                # all layers' K|V projected by one GEMM up front
         o = self.pool.get(M * (self.reps if expand else 1), Cn)
-        r0 = k0 = 0
+        r0 = k0 = i0 = 0
         segs = self.segs
         if not expand and len(segs) > 1 and all(Ls == segs[0][1] for _, Ls in segs):
             segs = [(sum(nv for nv, _ in segs), segs[0][1])]     # equal context lengths: the segments are one contiguous batch
         for nv, Ls in segs:                                      # (one launch per context segment: rows of q / o, rows of K|V)
             rows = nv * self.T * HW
-            kv = self.kv_all[k0:k0 + nv * Ls]
-            self._emit(ops.attention, q[0:rows] if expand else q[r0:r0 + rows], kv[:, off:off + inner],
-                       kv[:, off + inner:off + 2 * inner], o[r0:r0 + rows], Bq=nv * self.T, heads=heads, Nq=HW, Nk=Ls, ldq=Cn, ldk=ld,
-                       ldv=ld, ldo=Cn, kv_div=self.T, scale=att.dim_head ** -0.5)
+            Lt = min(Ls, TEXT_CONTEXT_LEN) if self.image_attn else Ls
+            Li = Ls - Lt
+            kv = self.kv_all[k0:k0 + nv * Lt]
+            qs = q[0:rows] if expand else q[r0:r0 + rows]
+            if Li:                                               # text + image tokens: both softmaxes in one launch
+                kvi = self.kv_ip_all[i0:i0 + nv * Li]
+                ldi = self.kv_ip_all.shape[1]
+                self._emit(ops.attention_ip, qs, kv[:, off:off + inner], kv[:, off + inner:off + 2 * inner], kvi[:, off:off + inner],
+                           kvi[:, off + inner:off + 2 * inner], o[r0:r0 + rows], Bq=nv * self.T, heads=heads, Nq=HW, Nt=Lt, Ni=Li,
+                           ldq=Cn, ldk=ld, ldv=ld, ldk_ip=ldi, ldv_ip=ldi, ldo=Cn, kv_div=self.T, scale=att.dim_head ** -0.5,
+                           ip_scale=att.image_cross_attention_scale)
+            else:                                                # (<= 77 tokens: the reference's image slice is empty, adds 0)
+                self._emit(ops.attention, qs, kv[:, off:off + inner], kv[:, off + inner:off + 2 * inner], o[r0:r0 + rows],
+                           Bq=nv * self.T, heads=heads, Nq=HW, Nk=Lt, ldq=Cn, ldk=ld, ldv=ld, ldo=Cn, kv_div=self.T,
+                           scale=att.dim_head ** -0.5)
             r0 += rows
-            k0 += nv * Ls
+            k0 += nv * Lt
+            i0 += nv * Li
         self._release(q)
         return o
 
@@ -773,6 +799,10 @@ class _Plan(_PlanBase):
         if "ctx_kv_all" in P:
             self.kv_all = self.linear(self.ctx, self.ctx_rows, P["ctx_kv_all"])  # [sum B_i L_i][sum 2C]: every cross-attention K|V
             self._pinned.add(self.kv_all.data_ptr())
+        self.kv_ip_all = None
+        if self.ctx_img is not None:
+            self.kv_ip_all = self.linear(self.ctx_img, self.img_rows, P["ctx_kv_ip_all"])  # [sum B_i (L_i - 77)][sum 2C]: image K|V
+            self._pinned.add(self.kv_ip_all.data_ptr())
 
         FT = self.Bx * T                                         # frames of the distinct latents (= BT unless shared_x)
         x8 = self.pool.get(FT * H * W, 8)
@@ -888,13 +918,20 @@ class _Plan(_PlanBase):
 
     def set_context(self, context):
         """context [B, L, D], or one [n_i, L_i, D] tensor per segment"""
-        if torch.is_tensor(context):
+        if torch.is_tensor(context) and not self.img_rows:
             self.ctx.copy_(context.reshape(self.ctx_rows, -1), non_blocking=True)
             return
-        r = 0
-        for (nv, Ls), c in zip(self.segs, context):
-            self.ctx[r:r + nv * Ls].copy_(c.reshape(nv * Ls, -1), non_blocking=True)
-            r += nv * Ls
+        if torch.is_tensor(context):
+            context = [context]
+        r = ri = 0
+        for (nv, Ls), Lt, c in zip(self.segs, self.seg_txt, context):
+            if Lt == Ls:
+                self.ctx[r:r + nv * Ls].copy_(c.reshape(nv * Ls, -1), non_blocking=True)
+            else:                                                # text rows -> ctx, image rows -> ctx_img
+                self.ctx[r:r + nv * Lt].view(nv, Lt, -1).copy_(c[:, :Lt], non_blocking=True)
+                self.ctx_img[ri:ri + nv * (Ls - Lt)].view(nv, Ls - Lt, -1).copy_(c[:, Lt:], non_blocking=True)
+            r += nv * Lt
+            ri += nv * (Ls - Lt)
 
     def launch_async(self, x, t_rows, fps_rows, context, cur):
         """enqueue one forward on this plan's stream (ordered after `cur`); the caller joins"""

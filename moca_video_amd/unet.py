@@ -22,6 +22,9 @@ from . import ops
 
 __all__ = ["UNetModel"]
 
+TEXT_CONTEXT_LEN = 77          # attention.py:60: context rows past these are image tokens (use_image_attention)
+IMAGE_CONTEXT_MAX = 93         # longest image-attention context: 77 text + 16 image tokens (moca_attention_ip_f16's one key tile)
+
 
 # --------------------------------------------------------------------------------------
 # parameter containers: reproduce the reference module tree / state_dict names only
@@ -72,9 +75,9 @@ class _TemporalConvBlock(nn.Module):
 
 
 class _CrossAttention(nn.Module):
-    """attention.py:45-57"""
+    """attention.py:45-64 (img_cross_attention: to_k_ip / to_v_ip for the context rows past the 77 text tokens)"""
 
-    def __init__(self, query_dim, context_dim, heads, dim_head):
+    def __init__(self, query_dim, context_dim, heads, dim_head, img_cross_attention=False):
         super().__init__()
         inner = heads * dim_head
         context_dim = query_dim if context_dim is None else context_dim
@@ -83,6 +86,12 @@ class _CrossAttention(nn.Module):
         self.to_k = _Param((inner, context_dim), bias=False)
         self.to_v = _Param((inner, context_dim), bias=False)
         self.to_out = _seq(_Param((query_dim, inner)), nn.Identity())
+        self.image_cross_attention_scale = 1.0
+        self.text_context_len = TEXT_CONTEXT_LEN
+        self.img_cross_attention = img_cross_attention
+        if img_cross_attention:
+            self.to_k_ip = _Param((inner, context_dim), bias=False)
+            self.to_v_ip = _Param((inner, context_dim), bias=False)
 
 
 class _GEGLU(nn.Module):
@@ -102,11 +111,11 @@ class _FeedForward(nn.Module):
 class _BasicTransformerBlock(nn.Module):
     """attention.py:189-202"""
 
-    def __init__(self, dim, n_heads, d_head, context_dim):
+    def __init__(self, dim, n_heads, d_head, context_dim, img_cross_attention=False):
         super().__init__()
         self.attn1 = _CrossAttention(dim, None, n_heads, d_head)
         self.ff = _FeedForward(dim)
-        self.attn2 = _CrossAttention(dim, context_dim, n_heads, d_head)
+        self.attn2 = _CrossAttention(dim, context_dim, n_heads, d_head, img_cross_attention=img_cross_attention)
         self.attn2.is_self = context_dim is None
         self.norm1 = _Param((dim,), kind="norm")
         self.norm2 = _Param((dim,), kind="norm")
@@ -116,13 +125,14 @@ class _BasicTransformerBlock(nn.Module):
 class _SpatialTransformer(nn.Module):
     """attention.py:233-259"""
 
-    def __init__(self, ch, n_heads, d_head, depth, context_dim, use_linear):
+    def __init__(self, ch, n_heads, d_head, depth, context_dim, use_linear, img_cross_attention=False):
         super().__init__()
         inner = n_heads * d_head
         self.ch, self.inner, self.heads = ch, inner, n_heads
         self.norm = _Param((ch,), kind="norm")
         self.proj_in = _Param((inner, ch) if use_linear else (inner, ch, 1, 1))
-        self.transformer_blocks = nn.ModuleList([_BasicTransformerBlock(inner, n_heads, d_head, context_dim) for _ in range(depth)])
+        self.transformer_blocks = nn.ModuleList([_BasicTransformerBlock(inner, n_heads, d_head, context_dim, img_cross_attention)
+                                                 for _ in range(depth)])
         self.proj_out = _Param((ch, inner) if use_linear else (ch, inner, 1, 1))
 
 
@@ -281,6 +291,13 @@ def pack_tree(root, dev):
         ws += [a.to_k.weight.detach(), a.to_v.weight.detach()]
     if ws:
         P["ctx_kv_all"] = ops.pack_linear_cat(ws, device=dev)
+    # image cross-attention: every attn2 has to_k_ip / to_v_ip (use_image_attention is one switch for the whole tree); their K|V of the
+    # image rows of the contexts are ONE more up-front GEMM with the column layout of ctx_kv_all (same kv_cols)
+    ip = [a for a in cross if a.img_cross_attention]
+    if ip:
+        assert len(ip) == len(cross), "image cross-attention on some cross-attention layers only"
+        P["ctx_kv_ip_all"] = ops.pack_linear_cat([w for a in cross for w in (a.to_k_ip.weight.detach(), a.to_v_ip.weight.detach())],
+                                                 device=dev)
     return P, emb_cols, kv_cols
 
 
@@ -350,7 +367,6 @@ class UNetModel(nn.Module):
         if tempspatial_aware: unsupported.append("tempspatial_aware")
         if use_relative_position: unsupported.append("use_relative_position")
         if use_causal_attention: unsupported.append("use_causal_attention")
-        if use_image_attention: unsupported.append("use_image_attention")
         if not temporal_selfatt_only: unsupported.append("temporal_selfatt_only=False")
         if not conv_resample: unsupported.append("conv_resample=False")
         if num_head_channels != 64: unsupported.append("num_head_channels != 64 (kernels are head-dim 64)")
@@ -369,6 +385,7 @@ class UNetModel(nn.Module):
         self.addition_attention = addition_attention
         self.fps_cond = fps_cond
         self.context_dim = context_dim
+        self.use_image_attention = use_image_attention
         self.temporal_length = temporal_length
         time_embed_dim = model_channels * 4
 
@@ -382,7 +399,8 @@ class UNetModel(nn.Module):
 
         def attn_layers(ch):
             heads = ch // num_head_channels
-            layers = [_SpatialTransformer(ch, heads, num_head_channels, transformer_depth, context_dim, use_linear)]
+            layers = [_SpatialTransformer(ch, heads, num_head_channels, transformer_depth, context_dim, use_linear,
+                                          img_cross_attention=use_image_attention)]
             if temporal_attention:
                 layers.append(_TemporalTransformer(ch, heads, num_head_channels, temporal_transformer_depth, use_linear))
             return layers
@@ -402,7 +420,8 @@ class UNetModel(nn.Module):
                 input_block_chans.append(ch)
                 ds *= 2
         mid = [_ResBlock(ch, time_embed_dim, ch, temporal_conv),
-               _SpatialTransformer(ch, ch // num_head_channels, num_head_channels, transformer_depth, context_dim, use_linear)]
+               _SpatialTransformer(ch, ch // num_head_channels, num_head_channels, transformer_depth, context_dim, use_linear,
+                                   img_cross_attention=use_image_attention)]
         if temporal_attention:
             mid.append(_TemporalTransformer(ch, ch // num_head_channels, num_head_channels, temporal_transformer_depth, use_linear))
         mid.append(_ResBlock(ch, time_embed_dim, ch, temporal_conv))

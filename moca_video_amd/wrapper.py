@@ -177,3 +177,46 @@ class DenoiseModel(nn.Module):
         if isinstance(x_recon, tuple):
             return x_recon[0]
         return x_recon
+
+
+class LatentVisualDiffusion(DenoiseModel):
+    """ddpm3d.py:660-692: the image-conditioned model of the i2v configs.  `image_proj_model` is the HIP projector the reference's
+    `init_projector` picks (`Resampler` with 16 queries for `finegrained`, else `ImageProjModel` with 4 tokens; output dim 1024, so the UNet
+    needs `context_dim: 1024`).  The image embedder (the OpenCLIP ViT-H/14 vision tower, condition.py:298-376) is a seam like the text
+    tokenizer: it is instantiated from `cond_img_config` when that target imports, otherwise it stays None and the caller assigns
+    `.embedder`; `get_image_embeds` raises without one.  `project_image_features` runs the projector on precomputed features
+    ([B, 257, 1280] for the Resampler, [B, 1024] for ImageProjModel)."""
+
+    def __init__(self, cond_img_config=None, finegrained=False, random_cond=False, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        from .image_proj import ImageProjModel, Resampler
+        self.random_cond = random_cond
+        self.finegrained = finegrained
+        self.embedder = None
+        if cond_img_config is not None:
+            try:
+                get_obj_from_str(cond_img_config["target"])
+            except (ImportError, AttributeError):
+                pass                                     # the seam: the caller assigns .embedder
+            else:
+                self.embedder = instantiate_from_config(cond_img_config).eval()
+                for p in self.embedder.parameters():
+                    p.requires_grad = False
+        num_tokens = 16 if finegrained else 4
+        if finegrained:
+            self.image_proj_model = Resampler(dim=1024, depth=4, dim_head=64, heads=12, num_queries=num_tokens, embedding_dim=1280,
+                                              output_dim=1024, ff_mult=4)
+        else:
+            self.image_proj_model = ImageProjModel(clip_extra_context_tokens=num_tokens, cross_attention_dim=1024, clip_embeddings_dim=1024)
+
+    def project_image_features(self, feats):
+        """the projector on precomputed image features"""
+        return self.image_proj_model(feats)
+
+    @torch.no_grad()
+    def get_image_embeds(self, batch_imgs):
+        """ddpm3d.py:689-693: img [b, c, h, w] -> image tokens [b, 16 | 4, 1024]"""
+        if self.embedder is None:
+            raise RuntimeError("LatentVisualDiffusion has no image embedder: cond_img_config's target did not import (the OpenCLIP vision "
+                               "tower is not part of this package); assign `.embedder` or call project_image_features on features")
+        return self.image_proj_model(self.embedder(batch_imgs))
