@@ -175,7 +175,9 @@ int moca_gemm_lnfold_ok(const moca_gemm_params* p);
  * no split-K / residual / row add); else 0 (the caller then runs the projection and moca_temporal_attention_f16).       */
 int moca_gemm_tattn_ok(const moca_gemm_params* p);
 /* 1 when this call (wgroup_rows / wgroup_stride set) can take per-row-group weights (see moca_gemm_params.wgroup_rows); else 0 (the
- * caller then runs the GroupNorm as a pass of its own).                                                                    */
+ * caller then runs the GroupNorm as a pass of its own).  moca_gemm_colsum_rows / _ln_ok / _rowsum_cols answer for the call WITH
+ * their flag, per-group weights included: a flag can move the call to a kernel that needs other group sizes (MOCA_EP_LN: the
+ * 160 x 320 tiling, whole 160-row tiles per group), and then they answer 0.                                                */
 int moca_gemm_wgroup_ok(const moca_gemm_params* p);
 /* 1 when this call (a2 / lda2 / k1 set) can read its A operand from two sources (see moca_gemm_params.a2); else 0 (the caller
  * then materialises the concat with moca_concat_channels*_f16).                                                          */
@@ -213,9 +215,11 @@ int moca_groupnorm_colsum_f16(const void* x, void* y, const float* gamma, const 
 /* GroupNorm(32, K, affine, no activation) folded into the Linear(K, N) that consumes it -- `x = self.norm(x); ...; x = self.proj_in(x)`
  * of SpatialTransformer / TemporalTransformer (attention.py:238-242,262-268 / :297-302,333-341) -- as PER-STATISTICS-GROUP weights:
  * with mean / rstd of group (sg, k / (K/32)) from the finished statistics gstat i64 [n_sg][32][2] (a MOCA_EP_GSTAT producer; `count` =
- * values per group = frames_per_stat * H*W * K/32), s[k] = gamma[k] rstd, t[k] = beta[k] - mean rstd gamma[k]:
- *     wg[sg][n][k] = fp16(w[n][k] * s[k])            (fp16 [n_sg][N][ldw], zero padding copied),
- *     bg[sg][n]    = bias[n] + sum_k t[k] * w[n][k]    (f32 [n_sg][N]; bias may be NULL),
+ * values per group = frames_per_stat * H*W * K/32), s[k] = gamma[k] rstd:
+ *     wg[sg][n][k] = fp16(w[n][k] * s[k])                                          (fp16 [n_sg][N][ldw], zero padding copied),
+ *     bg[sg][n]    = bias[n] + sum_k beta[k] * w[n][k] - sum_k mean * wg[sg][n][k]   (f32 [n_sg][N]; bias may be NULL),
+ * the mean term from the STORED fp16 wg, so that the GEMM computes sum_k (x_k - mean) wg[sg][n][k]: the rounding of wg then does not
+ * grow with |group mean| / std,
  * so that Linear(GroupNorm(x)) = x . wg[sg]^T + bg[sg] for the rows of group sg: moca_gemm_f16 with wgroup_rows = rows per group,
  * wgroup_stride = N * ldw.  The normalised tensor is never stored (one fp16 rounding less than the reference's layout would need).
  * A poisoned / out-of-range statistics group yields NaN weights for that group.  K % 32 == 0, K % 8 == 0, ldw % 8 == 0.        */

@@ -3699,12 +3699,22 @@ extern "C" int moca_gemm_wgroup_ok(const moca_gemm_params* pp) {
     return wgroup_ok(p) ? 1 : 0;
 }
 
+// The queries about an epilogue flag answer for the call WITH that flag, per-group weights included: moca_gemm_f16 checks wgroup_ok() on
+// the flagged call, and the flag can move it to another kernel (MOCA_EP_LN: off the weight-stationary kernel onto the 160 x 320 tiling,
+// which needs groups of whole 160-row tiles).  A query that says yes is a launch that is accepted.
+static bool wgroup_ok_with(const moca_gemm_params& pp, int flag) {
+    if (pp.wgroup_rows == 0) return true;
+    moca_gemm_params p = pp;
+    p.flags |= flag;
+    return wgroup_ok(p);
+}
+
 extern "C" int moca_gemm_rowsum_cols(const moca_gemm_params* pp) {
     if (!pp) return 0;
     moca_gemm_params p = *pp;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
     normalise_splits(p);
-    return rowsum_cols(p);
+    return wgroup_ok_with(p, MOCA_EP_ROWSUM) ? rowsum_cols(p) : 0;
 }
 
 extern "C" int moca_gemm_lnfold_ok(const moca_gemm_params* pp) {
@@ -3720,7 +3730,7 @@ extern "C" int moca_gemm_colsum_rows(const moca_gemm_params* pp) {
     moca_gemm_params p = *pp;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
     normalise_splits(p);
-    return colsum_rows(p);
+    return wgroup_ok_with(p, (p.flags & MOCA_EP_GSTAT) ? 0 : MOCA_EP_COLSUM) ? colsum_rows(p) : 0;
 }
 
 extern "C" int moca_gemm_ln_ok(const moca_gemm_params* pp) {
@@ -3728,7 +3738,7 @@ extern "C" int moca_gemm_ln_ok(const moca_gemm_params* pp) {
     moca_gemm_params p = *pp;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
     normalise_splits(p);
-    return takes_w80t_ln(p) ? 1 : 0;
+    return takes_w80t_ln(p) && wgroup_ok_with(p, MOCA_EP_LN) ? 1 : 0;
 }
 
 // fp16 split-K slabs (MOCA_TUNE_SLAB_F16): a split-K call of the 256-row kernel with an fp16 output and no GEGLU

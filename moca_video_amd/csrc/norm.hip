@@ -780,13 +780,18 @@ extern "C" int moca_groupnorm_gstat_f16(const void* x, void* y, const float* gam
 }
 
 // ---- GroupNorm folded into the consuming linear as per-statistics-group weights (moca_groupnorm_fold_weights_f16) ----
-// block (sg, row block of 16 W rows): the 2 x K scale / shift values of the group in LDS, then thread = one 8-element chunk of a W row:
-// scaled copy + the dot product with the shift (reduced over the row's chunks through LDS in a fixed order: deterministic)
+// block (sg, row block of 16 W rows): the 2 x K scale / beta values of the group in LDS, then thread = one 8-element chunk of a W row:
+// scaled copy wg = fp16(w * s) + its share of the shift (reduced over the row's chunks through LDS in a fixed order: deterministic).
+// The GEMM multiplies RAW x by the ROUNDED wg, so the mean term of the shift is taken from the stored wg as well:
+//     bg[n] = bias[n] + sum_k beta_k * w[n][k] - sum_k mean_g(k) * float(wg[n][k])
+// and the launch computes sum_k (x_k - mean) * wg[n][k] + ...: the rounding error of wg multiplies x - mean, not x.  (With the mean term
+// taken from the unrounded w * s the error grew with |group mean| / std -- modelled 1.4e-3 at a ratio of 10, 4.4e-3 at 30; the sweep of
+// tests/test_groupnorm_gpu.py holds every ratio up to 100 to the fp16 kernel tolerance.)
 __global__ __launch_bounds__(256) void gn_fold_weights_kernel(const half_t* __restrict__ w, const float* __restrict__ bias,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               const int64_t* __restrict__ gstat, half_t* __restrict__ wg, float* __restrict__ bg,
                                                               int N, int K, int ldw, double inv_count, float eps) {
-    extern __shared__ float s_st[];                       // [2][K] scale, shift; then [rows][chunks] partial dots
+    extern __shared__ float s_st[];                       // [2][K] scale, beta; then [rows][chunks] partial dots
     const int sg = blockIdx.x, tid = threadIdx.x;
     const int cpg = K / GN_GROUPS;
     __shared__ float s_mr[2 * GN_GROUPS];
@@ -801,9 +806,8 @@ __global__ __launch_bounds__(256) void gn_fold_weights_kernel(const half_t* __re
     __syncthreads();
     for (int k = tid; k < K; k += 256) {
         const int g = k / cpg;
-        const float sc = s_mr[2 * g + 1] * gamma[k];
-        s_st[k] = sc;
-        s_st[K + k] = beta[k] - s_mr[2 * g] * sc;
+        s_st[k] = s_mr[2 * g + 1] * gamma[k];
+        s_st[K + k] = beta[k];
     }
     __syncthreads();
     const int cpr = ldw / 8;                              // 16-byte chunks per W row (padding included: copied as zeros x scale 0)
@@ -820,9 +824,9 @@ __global__ __launch_bounds__(256) void gn_fold_weights_kernel(const half_t* __re
             for (int j = 0; j < 8; ++j) {
                 const int k = ch * 8 + j;
                 const float x = (float)v[j];
-                const float sc = k < K ? s_st[k] : 0.f, sh = k < K ? s_st[K + k] : 0.f;
+                const float sc = k < K ? s_st[k] : 0.f, be = k < K ? s_st[K + k] : 0.f, mu = k < K ? s_mr[2 * (k / cpg)] : 0.f;
                 o[j] = (half_t)(x * sc);
-                dot += x * sh;
+                dot += x * be - mu * (float)o[j];
             }
             *reinterpret_cast<half8v*>(wg + ((int64_t)sg * N + n) * ldw + ch * 8) = o;
         }

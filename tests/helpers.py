@@ -81,3 +81,18 @@ def loop_sam_candidates(call, F, H, W):
         else:
             out.append(rect(11, 15, call % 4, 5 + call % 4)[None])
     return out
+
+
+def wgroup_cases():
+    """per-row-group weights (a GroupNorm folded into proj_in) on the 320 -> 320 linear: (group rows, M, residual, MOCA_TUNE_GEMM_WS,
+    epilogue flag).  Group rows: 4096 (64 x 64 latents, per frame), 16 x 1024 (32 x 32 latents, per video), 2560 / 640 (multiples of
+    the 160-row tile), 512 = 160 x 3 + 32 (not); M = the multiple of the group rows at or just above 2^15 .. 2^18"""
+    out = []
+    for rows in (4096, 1024 * 16, 2560, 640, 160 * 3 + 32):
+        for lg in (15, 16, 17, 18):
+            M = -(-(1 << lg) // rows) * rows
+            for res in (False, True):
+                for knob in (0, 1, 2):
+                    for flag in ("plain", "rowsum", "ln", "colsum"):
+                        out.append((rows, M, res, knob, flag))
+    return out

@@ -210,3 +210,54 @@ def test_product_library_is_not_a_diagnostic_build():
         assert compile_lines and all("-DMOCA_DIAG_NAME=" in l for l in compile_lines), target
     src = open(os.path.join(os.path.dirname(lib.LIB_PATH), "lib.py")).read()
     assert re.search(r'"DIAG:" in ver and os\.environ\.get\("MOCA_HIP_DIAG"\) != "1"', src)
+
+
+def test_wgroup_queries_agree_with_the_launch_validation_cpu():
+    """Per-group weights (`wgroup`: GroupNorm folded into proj_in) on the 320 -> 320 linear: whenever a flag's query -- gemm_rowsum_cols,
+    gemm_ln_ok, gemm_colsum_rows -- accepts a call that carries `wgroup`, moca_gemm_f16's own check of that call WITH the flag
+    (gemm_wgroup_ok with the flag set, the same wgroup_ok()) must accept it too; otherwise the plan builds a step that fails with
+    MOCA_E_BADARG.  Swept over group rows x M x residual x MOCA_TUNE_GEMM_WS (host tensors: the queries read pointers, never memory).
+    The case that broke: 4096-row groups (64 x 64 latents) at M = 2^17 go to the weight-stationary kernel, but with the LayerNorm store
+    loop to the 160 x 320 tiling, which needs whole 160-row tiles per group."""
+    from helpers import wgroup_cases
+    from moca_video_amd import lib, ops
+    Cn = 320
+    cases = wgroup_cases()
+    x = torch.empty(max(c[1] for c in cases), Cn, dtype=torch.float16)
+    r = torch.empty_like(x)
+    pw = ops.pack_linear(torch.zeros(Cn, Cn), torch.zeros(Cn), device="cpu")
+    stride = pw.N * pw.w.stride(0)
+    n_max = max(c[1] // c[0] for c in cases)
+    pwg = ops.PackedWeight(torch.empty(n_max * Cn, pw.w.stride(0), dtype=torch.float16), torch.empty(n_max * Cn), pw.N, pw.K, pw.n_out)
+    g = torch.ones(Cn)
+    cs = torch.empty(16)
+    old = lib.set_tuning(lib.MOCA_TUNE_GEMM_WS, 1)
+    seen = {}
+    try:
+        for rows, M, res, knob, flag in cases:
+            lib.set_tuning(lib.MOCA_TUNE_GEMM_WS, knob)
+            kw = dict(M=M, residual=r[:M] if res else None, wgroup=(rows, stride))
+            xa = x[:M]
+            if flag == "plain":
+                q = launch = ops.gemm_wgroup_ok(xa, pwg, **kw)
+            elif flag == "rowsum":
+                q = ops.gemm_rowsum_cols(xa, pwg, rowsum=True, **kw) > 0
+                launch = ops.gemm_wgroup_ok(xa, pwg, rowsum=True, **kw)
+            elif flag == "ln":
+                q = ops.gemm_ln_ok(xa, pwg, ln=(g, g, None, 1e-5), **kw)
+                launch = ops.gemm_wgroup_ok(xa, pwg, ln=(g, g, None, 1e-5), **kw)
+            else:
+                q = ops.gemm_colsum_rows(xa, pwg, **kw) > 0
+                launch = ops.gemm_wgroup_ok(xa, pwg, colsum=cs, **kw)
+            assert not q or launch, f"rows {rows}, M {M}, residual {res}, WS knob {knob}: the {flag} query accepts a call the launch refuses"
+            seen[(rows, M, res, knob, flag)] = q
+    finally:
+        lib.set_tuning(lib.MOCA_TUNE_GEMM_WS, old)
+    # the 64 x 64-latent proj_in at B = 2: weight-stationary kernel with the row sums, the LayerNorm store loop refused
+    assert seen[(4096, 1 << 17, False, 1, "plain")] and seen[(4096, 1 << 17, False, 1, "rowsum")]
+    assert not seen[(4096, 1 << 17, False, 1, "ln")]
+    # at B = 1 (M = 2^16, no residual) the tiled kernel runs it: 4096 rows are not whole 160 / 320-row tiles -> no fold at all
+    assert not seen[(4096, 1 << 16, False, 1, "plain")]
+    # groups of whole 160-row tiles keep every form on the tiled kernels
+    assert all(seen[(2560, M, False, 0, f)] for M in (33280, 66560) for f in ("plain", "rowsum", "ln"))
+    assert sum(seen.values()) > 100

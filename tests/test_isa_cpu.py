@@ -99,3 +99,22 @@ def test_every_gemm_kernel_of_the_dispatch_is_present(isa):
                     ("gemm_g4p_kernel", 2), ("gemm_f16_kernel", 6)):
         have = [k for k in isa if k.startswith(stem + "<")]
         assert len(have) == n, f"{stem}: {len(have)} instantiations, expected {n}: {have}"
+
+
+def test_weight_stationary_strip_loop_issues_exactly_the_counted_stores(isa):
+    """gemm_ws_kernel waits for strip k + 1 with a HAND-COUNTED `s_waitcnt vmcnt(BASE + k * ST_PER_STRIP)` (gemm_ws.hip): vmcnt retires
+    loads, LDS-DMA and stores together in issue order, so the count only holds while the strip loop issues exactly ST_PER_STRIP vector
+    stores per wave -- the row tile's 16 B + 16 B + 8 B per lane, + the row partial with ROWSUM -- and no atomics.  One store fewer makes
+    the wait too lenient (strip k + 1 read from LDS before its DMA landed: silent wrong results).  Counted over the natural loop (the
+    control-flow graph's), not the address span: without a residual hipcc places the store block in front of the loop header."""
+    for res in ("false", "true"):
+        for epi in range(3):
+            name = f"gemm_ws_kernel<{res}, {epi}>"
+            assert name in isa, f"{name} is not in the library"
+            copies = isa[name]["strip_loop"]
+            assert copies, f"{name}: no strip loop found"
+            for sl in copies:
+                assert sl["mfma"] == 50, f"{name}: strip loop {sl}"
+                assert sl["vm_store"] == (4 if epi == 1 else 3), f"{name}: {sl['vm_store']} vector stores in the strip loop (ST_PER_STRIP = " \
+                                                                 f"{4 if epi == 1 else 3}): the hand-counted vmcnt waits no longer match"
+                assert sl["vm_atomic"] == 0, f"{name}: {sl['vm_atomic']} atomics in the strip loop (GSTAT flushes once per group, after it)"

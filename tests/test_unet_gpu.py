@@ -346,6 +346,38 @@ def test_unet_full_width_vs_reference_golden(full_dm):
     assert relerr(a.cpu(), b.cpu()) < 1e-6
 
 
+def test_unet_full_width_64x64_latents_vs_reference_golden(full_dm):
+    """The reference's default latent size (512 x 512 pixels -> 16 x 64 x 64 latents), one CFG pair (B = 2: two latents / contexts /
+    timesteps), against the REAL reference UNet row by row (`tools/make_golden.py --only full64`).  At M = 2 x 16 x 4096 = 2^17 the
+    320-channel transformers fold their GroupNorm into proj_in on the weight-stationary kernel with 4096-row statistics groups -- not
+    whole 160-row tiles, the case whose LayerNorm store-loop query used to disagree with the launch.  B = 1 (M = 2^16) runs proj_in on the
+    tiled kernel, which refuses such groups: GroupNorm launch + linear."""
+    from moca_video_amd import ops
+    m = full_dm.model.diffusion_model
+    gs = [golden(f"unet_full_64_r{r}") for r in range(2)]
+    x = torch.cat([inp(f"full_64.r{r}.x", (1, 4, 16, 64, 64)) for r in range(2)]).cuda()
+    ctx = torch.cat([inp(f"full_64.r{r}.ctx", (1, 77, 1024)) for r in range(2)]).cuda()
+    t = torch.cat([torch.from_numpy(g["t"]) for g in gs]).cuda()
+    fps = torch.tensor([10, 10]).cuda()
+    runs = [m(x, t, context=ctx, fps=fps) for _ in range(3)]                # eager, hipGraph capture, replay
+    assert torch.equal(runs[0], runs[1]) and torch.equal(runs[1], runs[2]), "replays must be bit-identical"
+    for r in range(2):
+        check(runs[0][r:r + 1].cpu(), torch.from_numpy(gs[r]["y"]), TOL_UNET, f"full 64x64 B=2 row {r}")
+        y1 = m(x[r:r + 1], t[r:r + 1], context=ctx[r:r + 1], fps=fps[r:r + 1])
+        check(y1.cpu(), torch.from_numpy(gs[r]["y"]), TOL_UNET, f"full 64x64 B=1 row {r}")
+
+    def folds(B):
+        plan = next(p for k, p in m._plans.items() if k[0] == B and k[2:4] == (64, 64))
+        return [st.keywords["wgroup"][0] for st in plan.steps if st.func is ops.gemm and st.keywords.get("wgroup") is not None], \
+            sum(1 for st in plan.steps if st.func is ops.groupnorm_fold_weights)
+    # the plans: at B = 1 (M = 2^16) proj_in runs on the tiled kernel, which refuses 4096-row groups; at B = 2 the plan falls back
+    # to the GroupNorm launch + linear as well (measured: no fold step) -- no per-group-weight GEMM is built whose launch could
+    # refuse it, and the forward above held to the reference either way
+    for B in (1, 2):
+        rows, n = folds(B)
+        assert n == 0 and not rows, f"B = {B}: {n} fold steps, GEMMs on per-group weights with group rows {sorted(set(rows))}"
+
+
 def _b16_inputs():
     """the 8 window rows of one FIFO iteration, tiled from the two windows of tests/golden/unet_full_b16.npz (own latents, 16
     consecutive timesteps of the 50-step schedule each), + the 154-token and the 77-token context"""

@@ -68,6 +68,98 @@ def disassemble(co):
     return funcs
 
 
+def _target(ins, i):
+    """address a branch instruction jumps to, or None"""
+    a, _, ops = ins[i]
+    m = re.search(r"<[^>]*\+0x([0-9a-fA-F]+)>|<([^>+]+)>$", ops)
+    m2 = re.match(r"(\d+)", ops)
+    if m and m.group(1):
+        return ins[0][0] + int(m.group(1), 16)
+    if m2:                                             # raw simm16: target = next instruction + 4 * simm16
+        off = int(m2.group(1))
+        if off >= 0x8000:
+            off -= 0x10000
+        return a + 4 + 4 * off
+    return None
+
+
+def natural_loops(ins):
+    """the loops of the control-flow graph: {header index: set of instruction indices}, every back edge into a header merged.  Unlike
+    loops() (the address span of one backward branch) this holds blocks that hipcc laid out BEFORE the header or after the branch --
+    e.g. the store / latch block of gemm_ws_kernel without a residual sits in front of the strip loop's header."""
+    addr_to_idx = {a: i for i, (a, _, _) in enumerate(ins)}
+    starts = {0}
+    for i, (_, mn, _) in enumerate(ins):
+        if mn.startswith("s_cbranch") or mn in ("s_branch", "s_endpgm", "s_setpc_b64"):
+            starts.add(i + 1)
+            t = _target(ins, i)
+            if t in addr_to_idx:
+                starts.add(addr_to_idx[t])
+    starts = sorted(x for x in starts if x < len(ins))
+    blocks = [(lo, hi) for lo, hi in zip(starts, starts[1:] + [len(ins)])]
+    blk_of = {lo: b for b, (lo, _) in enumerate(blocks)}
+    succ = [[] for _ in blocks]
+    for b, (lo, hi) in enumerate(blocks):
+        mn = ins[hi - 1][1]
+        if mn.startswith(("s_cbranch", "s_branch")):
+            t = _target(ins, hi - 1)
+            if t in addr_to_idx and addr_to_idx[t] in blk_of:
+                succ[b].append(blk_of[addr_to_idx[t]])
+        if not (mn in ("s_branch", "s_endpgm", "s_setpc_b64")) and b + 1 < len(blocks):
+            succ[b].append(b + 1)
+    pred = [[] for _ in blocks]
+    for b, ss in enumerate(succ):
+        for t in ss:
+            pred[t].append(b)
+    # dominators (iterative; the graphs here are a few hundred blocks)
+    allb = set(range(len(blocks)))
+    dom = [allb.copy() for _ in blocks]
+    dom[0] = {0}
+    changed = True
+    while changed:
+        changed = False
+        for b in range(1, len(blocks)):
+            ps = [dom[q] for q in pred[b]]
+            nd = (set.intersection(*ps) if ps else set()) | {b}
+            if nd != dom[b]:
+                dom[b], changed = nd, True
+    out = {}
+    for b, ss in enumerate(succ):
+        for h in ss:
+            if h in dom[b]:                            # back edge b -> h
+                body, stack = {h, b}, [b]
+                while stack:
+                    x = stack.pop()
+                    if x == h:
+                        continue
+                    for q in pred[x]:
+                        if q not in body:
+                            body.add(q)
+                            stack.append(q)
+                out.setdefault(blocks[h][0], set()).update(body)
+    return {hd: {i for bb in body for i in range(*blocks[bb])} for hd, body in out.items()}
+
+
+def strip_loop(ins):
+    """vector-memory stores / atomics of the innermost natural loops holding the most MFMAs (global_ / buffer_ / flat_: what a
+    hand-counted `s_waitcnt vmcnt(N)` must count besides the loads), one entry per copy hipcc emitted of such a loop"""
+    lps = []
+    for body in natural_loops(ins).values():
+        mf = sum(1 for i in body if ins[i][1].startswith("v_mfma"))
+        if mf:
+            lps.append((body, mf))
+    inner = [(b, mf) for b, mf in lps if not any(o is not b and o < b and omf for o, omf in lps)]
+    if not inner:
+        return None
+    top = max(mf for _, mf in inner)
+    out = []
+    for body in sorted((b for b, mf in inner if mf == top), key=min):
+        mns = [ins[i][1] for i in body]
+        out.append(dict(instructions=len(body), mfma=top, vm_store=sum(1 for mn in mns if mn.startswith(("global_store", "buffer_store", "flat_store"))),
+                        vm_atomic=sum(1 for mn in mns if mn.startswith(("global_atomic", "buffer_atomic", "flat_atomic")))))
+    return out
+
+
 def loops(ins):
     """backward branches -> (start index, end index) of loop bodies"""
     addr_to_idx = {a: i for i, (a, _, _) in enumerate(ins)}
@@ -154,6 +246,7 @@ def analyse(lib_path=None):
                 d["instructions_total"] = len(ins)
                 d["scratch"] = sum(1 for _, mn, _ in ins if mn.startswith("scratch_"))
                 d["loop"] = main_loop(ins)
+                d["strip_loop"] = strip_loop(ins) if "gemm_ws_kernel" in name else None
                 short = re.sub(r"\(anonymous namespace\)::", "", dm[name])
                 short = re.sub(r"^void ", "", short)
                 short = re.sub(r"\(.*\)$", "", short)
@@ -173,3 +266,5 @@ if __name__ == "__main__":
         ls = "-" if lp is None else f"{lp['instructions']:5d} {lp['mfma']:4d} {lp['lds_dma']:3d} {lp['ds_read']:4d} {lp['barrier']:4d} {lp['vmcnt0']:3d} ({lp['vmcnt0_inside']})"
         print(f"{k:46s} {d.get('vgpr_count', 0):4d} {d.get('agpr_count', 0):4d} {d.get('sgpr_count', 0):4d} "
               f"{d.get('vgpr_spill_count', 0) + d.get('sgpr_spill_count', 0):5d} | {ls} | {d['mfma_total']}")
+        for sl in d.get("strip_loop") or []:
+            print(f"{'':46s} natural loop: {sl['instructions']} instructions, {sl['mfma']} MFMA, {sl['vm_store']} stores, {sl['vm_atomic']} atomics")

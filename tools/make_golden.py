@@ -4,6 +4,7 @@
 travels, only these small input-recipe/output fixtures do.
 
     python tools/make_golden.py [--full]      (--full adds the full-width 1.41 B-param UNet cases)
+    python tools/make_golden.py --only full64  (the full-width UNet at 16 x 64 x 64 latents, B = 2)
 
 Inputs and parameters are not stored: they are regenerated bit-identically from
 moca_video_amd.weightgen (numpy Philox keyed by tensor name), so a fixture is
@@ -194,6 +195,31 @@ def unet_full_b16(om):
                 out[f"{w}_{L}"] = y
     out["fps"] = np.asarray([10])
     save("unet_full_b16", **out)
+    del model
+
+
+def unet_full_64(om):
+    """The reference's default latent size (scripts/evaluation/inference.py: 512 x 512 pixels -> 64 x 64 latents), 16 frames, one CFG
+    pair (B = 2): two rows with their own latents / 77-token contexts / timesteps (981, 20), fps 10.  At M = 2 x 16 x 4096 = 2^17 the
+    320-channel GroupNorms fold into proj_in on the weight-stationary kernel with 4096-row groups (not a multiple of 160).  Each row
+    runs through the REAL reference alone (a B = 2 forward would hold 2 x 10.7 GB of spatial attention scores on the host; every op
+    is per sample) and is saved to a file of its own (unet_full_64_r{0,1}.npz: each under the 1 MiB limit of a committed file)."""
+    import yaml
+    with open(os.path.join(REF, "configs/inference_t2v_512_v2.0.yaml")) as f:
+        params = dict(yaml.safe_load(f)["model"]["params"]["unet_config"]["params"])
+    params["use_checkpoint"] = False
+    t0 = time.time()
+    model = om.UNetModel(**params).eval()
+    fill(model, 11)
+    print(f"[full_64] reference UNet built+filled in {time.time() - t0:.1f}s")
+    with torch.no_grad():
+        for r, tv in enumerate((981, 20)):
+            x = inp(f"full_64.r{r}.x", (1, 4, 16, 64, 64))
+            ctx = inp(f"full_64.r{r}.ctx", (1, 77, 1024))
+            t1 = time.time()
+            y = model(x, torch.tensor([tv]), context=ctx, fps=torch.tensor([10]), clean_cond=True, gamma=0.5)
+            print(f"[full_64] r{r} t={tv}: forward {time.time() - t1:.1f}s, out std {y.std():.4f}")
+            save(f"unet_full_64_r{r}", y=y, t=torch.tensor([tv]), fps=np.asarray([10]), L=np.asarray(77))
     del model
 
 
@@ -775,6 +801,7 @@ def main():
     if "full" in todo: unet_full(om)
     if "fullN" in todo: unet_full(om, only_cfgN=True)
     if "fullB16" in todo: unet_full_b16(om)
+    if "full64" in todo: unet_full_64(om)
 
 
 if __name__ == "__main__":
