@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- denoising UNet-steps/s of the MI355X-native MoCA-Video hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line (headline `value`,
+`ms_per_step`, the in-step `roofline`).  `--full` adds the legs that take runs of their own, after the headline and in the same
+line: `emulate_world_8`, the FIFO iteration / VAE decode / whole-video legs and the CPU-oracle `cpu_baseline` (1 GPU only).
 
 Workload (BASELINE.json configs[1]): VideoCrafter2 3D-UNet, 16 frames x 320x512
 (latents [1,4,16,40,64]), fp16 storage / fp32 accumulate, one prompt (77 context tokens),
@@ -587,8 +591,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fifo", action="store_true", help="skip the extra batched-FIFO-iteration measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the extra legs (emulate_world_8, FIFO / VAE / whole-video, cpu_baseline; 1 GPU "
+                         "only) into the same JSON line; the --no-* options below leave single legs out of such a run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-oracle baseline leg")
+    ap.add_argument("--no-fifo", action="store_true", help="--full: skip the FIFO iteration, VAE and whole-video legs")
     ap.add_argument("--cfg-mode", default="batched", choices=["batched", "concurrent"],
                     help="cond+uncond as one B=2 launch, or as two concurrent B=1 hipGraphs on two streams")
     ap.add_argument("--no-shared-prefix", action="store_true",
@@ -599,16 +606,17 @@ def main():
     ap.add_argument("--no-weight-prefetch", action="store_true",
                     help="A/B: no moca_gemm_params.prefetch (spare blocks of a GEMM launch's grid that read the next weight-heavy "
                          "launch's weights into the Infinity Cache)")
-    ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: host threads of the cpu_baseline leg (0: one GPU's share)")
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--height", type=int, default=40)
     ap.add_argument("--width", type=int, default=64)
-    ap.add_argument("--no-video", action="store_true", help="skip the measured whole-video leg (base sampling + 148 FIFO iterations + decode)")
+    ap.add_argument("--no-video", action="store_true",
+                    help="--full: skip the measured whole-video leg (base sampling + 148 FIFO iterations + decode)")
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="1-GPU rehearsal of rank 0's share of the N-GPU configs[4] job (its 64/N prompt rows in B=16 forwards, no "
                          "collectives): `value` is then THIS GPU's UNet-steps/s on that workload; extra legs are skipped")
     ap.add_argument("--no-emulate-world", action="store_true",
-                    help="skip the default leg that measures rank 0's share of the 8-GPU configs[4] job on this GPU (`emulate_world_8`)")
+                    help="--full: skip the leg that measures rank 0's share of the 8-GPU configs[4] job on this GPU (`emulate_world_8`)")
     ap.add_argument("--selftest-cpu", action="store_true", help="launcher/collective plumbing only (CPU, gloo): see launcher_selftest")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the latents the last timed DDIM step left (every prompt of the run, in prompt-row "
@@ -621,6 +629,7 @@ def main():
     if args.selftest_cpu:
         return launcher_selftest(args)
 
+    t_start = time.perf_counter()
     from moca_video_amd import dist as mdist
     from moca_video_amd import lib as mlib
     from moca_video_amd.sampler import DDIMSampler
@@ -693,6 +702,7 @@ def main():
         return out
 
     img = [b["x"] for b in batches]
+    t_setup = time.perf_counter()
     for i in range(max(args.warmup, 2)):       # >= 2: eager pass + hipGraph capture pass
         img = ddim_step(i, img)
     torch.cuda.synchronize()
@@ -825,11 +835,15 @@ def main():
         print(json.dumps(res))
         return
     note = lambda m: print(f"[bench] {m}", file=sys.stderr, flush=True)     # (progress on stderr: a silent multi-minute run looks hung)
-    note("headline measured: %.2f UNet-steps/s" % value)
-    if world == 1 and not args.no_emulate_world:
+    note("headline measured: %.2f UNet-steps/s (set-up %.1f s, warm-up %.1f s, timed steps %.1f s)"
+         % (value, t_setup - t_start, t0 - t_setup, dt))
+    if not (args.full and world == 1):                 # a plain run: the headline is all it measures
+        print(json.dumps(res))
+        return
+    if not args.no_emulate_world:
         res["emulate_world_8"] = emulate_world_leg(dm, sampler, device, T, H, W)
         note("emulate_world_8 done")
-    if world == 1 and not args.no_fifo:
+    if not args.no_fifo:
         # (operand statistics move the clock -- the same iteration on the headline's random-init weights, beside the
         #  zero-data one the long video leg needs)
         res["fifo_random_init"] = fifo_leg(dm, device, T, H, W, iters=5, weights="random-init")
@@ -841,12 +855,12 @@ def main():
         note("fifo prompt-mode + vae legs done")
         res["fifo"]["projected_s_per_video_incl_vae_decode"] = round(
             res["fifo"]["projected_s_per_video_148_iterations"] + res["vae_decode"]["s_per_video_148_frames"], 1)
-    if world == 1 and not args.no_fifo and not args.no_video:
+    if not args.no_fifo and not args.no_video:
         res["video"] = video_leg(dm, ae, device, T, H, W)
         note("video leg done")
-    if world == 1 and not args.no_fifo:
+    if not args.no_fifo:
         zdd.restore()                           # back to the headline weights
-    if world == 1 and not args.no_cpu_baseline:
+    if not args.no_cpu_baseline:
         # the host cores of ONE GPU's share of the box: min(affinity set, CPUs online / 8 GPUs per node) -- 32 of the 256 on the 8-GPU
         # hosts of this pool.  (All 256 threads on the fp32 oracle oversubscribe the convolutions: the leg then runs for > 7 minutes.)
         threads = args.cpu_threads or max(1, min(len(os.sched_getaffinity(0)), (os.cpu_count() or 8) // 8))

@@ -8,7 +8,7 @@ mkdir -p "$(dirname "$OUT")"; : > "$OUT"
 for i in $(seq 1 "$N"); do
   for spec in "$@"; do
     name="${spec%%:*}"; envs="${spec#*:}"
-    env $envs python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-video --no-emulate-world 2>/dev/null | python3 -c "
+    env $envs python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-video --no-emulate-world 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$name', '[$envs ]', 'UNet-steps/s', d['value'], 'ms_per_step', d['ms_per_step'], 'fifo_ms', d.get('fifo', {}).get('iteration_ms'))" >> "$OUT"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU-box pass that produces what profiles/ holds for a round (all on ONE box, named in box.txt):
 #   kernel-trace stats of the bench command, the two PMC traffic passes, the per-step plan profile on TRUE operands (B = 2 and B = 16),
-#   in-graph vs isolated per kernel, the in-bench SQ counters of the spatial attention kernel, the default bench line.
+#   in-graph vs isolated per kernel, the in-bench SQ counters of the spatial attention kernel, the full bench line (--full).
 # usage (on the GPU box, repo root):  bash tools/profile_round.sh gpurun_out/prof_rNN
 set -e
 OUT=$1
@@ -37,5 +37,5 @@ echo "plan profiles done" >&2
 bash tools/ingraph_vs_hot.sh $OUT/ivh > /dev/null 2>&1 || true
 cp $OUT/ivh/ingraph_vs_hot.txt $OUT/ingraph_vs_isolated.txt 2>/dev/null || true
 python3 tools/bench_attn.py > $OUT/bench_attn.txt 2>&1
-if [ -z "$SKIP_DEFAULT_BENCH" ]; then python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; fi
+if [ -z "$SKIP_DEFAULT_BENCH" ]; then python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; fi
 [ -f $OUT/bench_default.json ] && tail -c 400 $OUT/bench_default.json || true
