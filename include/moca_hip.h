@@ -327,6 +327,29 @@ int moca_silu_add_rows_f16(const void* a, int32_t div_a, const void* b, int32_t 
 int moca_embed_tokens_f16(const int64_t* tokens, const float* table, const float* pos, void* out,
                           int32_t n_tokens, int32_t L, int32_t C, int32_t vocab, void* stream);
 
+/* ---- image embedder: the OpenCLIP ViT-H/14 vision tower (condition.py:238-376; moca_video_amd/clip_vision.py) ---- */
+/* Non-causal self-attention, head dim 80 (width 1280 / 16 heads), fp16 in / out, fp32 online softmax: per image b and head h,
+ * softmax(Q K^T * scale) V over the N tokens of that image.  q/k/v/out: [B][N][ld] with head h at column h*80 (q, k, v may be
+ * column slices of one fused in_proj output, ld = 3 * width).  Keys >= N are masked before the maximum, rows >= N are never
+ * stored.  Limits: N >= 1 (one block per 64 queries, the keys streamed in tiles of 64: 257 is the tower's case), B * heads
+ * <= 65535; q, k, v 16-byte aligned, out 8-byte aligned; ldq, ldk, ldv multiples of 8 and ldo of 4 halves, all >= heads * 80;
+ * scale * log2(e) finite.  MOCA_E_BADARG otherwise.                                                                     */
+int moca_attention_d80_f16(const void* q, const void* k, const void* v, void* out,
+                           int32_t B, int32_t heads, int32_t N, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
+                           float scale, void* stream);
+/* preprocess (condition.py:355-363) + conv1's patchify: img [B][3][H][W] (f32 or f16, values in [-1, 1]) -> kornia's resize to
+ * size x size (antialias != 0 and H or W > size: separable Gaussian pre-blur, sigma = max((H / size - 1) / 2, 0.001) per axis,
+ * int(max(4 sigma, 3)) taps made odd, reflect border; then bicubic A = -0.75, align_corners, clamped taps), (x + 1) / 2, CLIP
+ * mean / std; written as the patch GEMM's A operand out [B * (size/patch)^2][ldo] fp16, column (c, ky, kx) = c * patch^2 +
+ * ky * patch + kx, columns 3 * patch^2 .. ldo - 1 zero.  Limits: 2 <= H, W <= 16384, size % patch == 0, ldo % 8 == 0,
+ * ldo >= 3 * patch^2, at most 63 Gaussian taps per axis.  MOCA_E_BADARG otherwise.                                      */
+int moca_clip_preprocess_patches_f16(const void* img, int32_t img_is_f32, void* out, int32_t B, int32_t H, int32_t W,
+                                     int32_t size, int32_t patch, int32_t ldo, int32_t antialias, void* stream);
+/* token rows of the vision transformer: out[b * (P+1) + 0][:] = cls + pos[0], out[b * (P+1) + 1 + p][:] = patch[b * P + p] + pos[1 + p]
+ * (fp32 patch embeddings [B * P][ldp >= C], class embedding [C] and positional embedding [P+1][C]; fp16 out [B * (P+1)][C]).   */
+int moca_clip_assemble_tokens_f16(const float* patch, int32_t ldp, const float* cls, const float* pos, void* out, int32_t B, int32_t P,
+                                  int32_t C, void* stream);
+
 /* ---- VAE decoder helpers (next row N1: AutoencoderKL.decode, lvdm/models/autoencoder.py:104-107) ---- */
 /* out[(b*T+t)*HW+p][co] = bias[co] + sum_ci w[co][ci] * z[b][ci][t][p] * inv_scale  (co < Cout; zero up to Cpad).
  * Replaces `z = 1/scale_factor * z` (ddpm3d.py:559) + `post_quant_conv` (autoencoder.py:105) + the NCHW -> channels-last

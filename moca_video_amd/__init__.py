@@ -11,7 +11,8 @@ Public surface mirrors the reference interfaces for this path only:
   AutoencoderKL                 lvdm/models/autoencoder.py:13-107 + lvdm/modules/networks/ae_modules.py:364-579
   FrozenOpenCLIPEmbedder        lvdm/modules/encoders/condition.py:174-235 (text tower on token ids)
   SimpleTokenizer               what open_clip.tokenize does (condition.py:207): byte-level BPE, needs the CLIP merges file
-  LatentVisualDiffusion         lvdm/models/ddpm3d.py:660-692 (image-conditioned model; the image embedder is a seam)
+  FrozenOpenCLIPImageEmbedderV2, FrozenOpenCLIPImageEmbedder   condition.py:298-376 / :238-296 (OpenCLIP ViT-H/14 vision tower)
+  LatentVisualDiffusion         lvdm/models/ddpm3d.py:660-692 (image-conditioned model)
   Resampler, ImageProjModel     lvdm/modules/encoders/ip_resampler.py (image projectors)
 Importing the package loads libmoca_hip.so and fails loudly if it has not been built.
 """
@@ -25,7 +26,9 @@ from .vae import AutoencoderKL  # noqa: E402
 from .clip_text import FrozenOpenCLIPEmbedder  # noqa: E402
 from .tokenizer import SimpleTokenizer  # noqa: E402
 from .image_proj import ImageProjModel, Resampler  # noqa: E402
+from .clip_vision import FrozenOpenCLIPImageEmbedder, FrozenOpenCLIPImageEmbedderV2  # noqa: E402
 from .wrapper import LatentVisualDiffusion  # noqa: E402
 
 __all__ = ["UNetModel", "DiffusionWrapper", "DenoiseModel", "AutoencoderKL", "FrozenOpenCLIPEmbedder", "SimpleTokenizer", "ImageProjModel", "Resampler",
-           "LatentVisualDiffusion", "instantiate_from_config", "load_unet_config"]
+           "FrozenOpenCLIPImageEmbedder", "FrozenOpenCLIPImageEmbedderV2", "LatentVisualDiffusion", "instantiate_from_config",
+           "load_unet_config"]

@@ -456,3 +456,26 @@ def embed_tokens(tokens, table, pos, out, *, n_tokens, L, Cn, vocab):
     _l.check(_l.load().moca_embed_tokens_f16(_l.ptr(tokens), _l.ptr(table), _l.ptr(pos), _l.ptr(out), n_tokens, L, Cn, vocab, _st()),
              "moca_embed_tokens_f16")
     return out
+
+
+def attention_d80(q, k, v, out, *, B, heads, N, ldq, ldk, ldv, ldo, scale):
+    """non-causal self-attention, head dim 80, per image over its N tokens (the OpenCLIP vision tower)"""
+    _l.check(_l.load().moca_attention_d80_f16(_l.ptr(q), _l.ptr(k), _l.ptr(v), _l.ptr(out), B, heads, N, ldq, ldk, ldv, ldo, scale,
+                                              _st()), "moca_attention_d80_f16")
+    return out
+
+
+def clip_preprocess_patches(img, out, *, size=224, patch=14, antialias=True):
+    """img [B, 3, H, W] f32 / f16 in [-1, 1] -> the patch GEMM's A operand out [B * (size / patch)^2][ldo] fp16 (kornia resize,
+    CLIP normalisation, conv1's (c, ky, kx) patch flattening, zero columns from 3 * patch^2 to ldo)"""
+    B, _, H, W = img.shape
+    _l.check(_l.load().moca_clip_preprocess_patches_f16(_l.ptr(img), int(img.dtype == torch.float32), _l.ptr(out), B, H, W, size, patch,
+                                                        out.stride(0), int(bool(antialias)), _st()), "moca_clip_preprocess_patches_f16")
+    return out
+
+
+def clip_assemble_tokens(patch, cls, pos, out, *, B, P, Cn):
+    """out [B * (P+1)][Cn] fp16 = [cls; patch rows of image b] + pos  (patch: f32 [B * P][>= Cn])"""
+    _l.check(_l.load().moca_clip_assemble_tokens_f16(_l.ptr(patch), patch.stride(0), _l.ptr(cls), _l.ptr(pos), _l.ptr(out), B, P, Cn, _st()),
+             "moca_clip_assemble_tokens_f16")
+    return out

@@ -182,9 +182,10 @@ class DenoiseModel(nn.Module):
 class LatentVisualDiffusion(DenoiseModel):
     """ddpm3d.py:660-692: the image-conditioned model of the i2v configs.  `image_proj_model` is the HIP projector the reference's
     `init_projector` picks (`Resampler` with 16 queries for `finegrained`, else `ImageProjModel` with 4 tokens; output dim 1024, so the UNet
-    needs `context_dim: 1024`).  The image embedder (the OpenCLIP ViT-H/14 vision tower, condition.py:298-376) is a seam like the text
-    tokenizer: it is instantiated from `cond_img_config` when that target imports, otherwise it stays None and the caller assigns
-    `.embedder`; `get_image_embeds` raises without one.  `project_image_features` runs the projector on precomputed features
+    needs `context_dim: 1024`).  The image embedder (the OpenCLIP ViT-H/14 vision tower, condition.py:298-376) is instantiated from
+    `cond_img_config` when that target imports -- `moca_video_amd.clip_vision.FrozenOpenCLIPImageEmbedderV2` (or
+    `FrozenOpenCLIPImageEmbedder`) is the HIP one -- otherwise it stays None and the caller assigns `.embedder`; `get_image_embeds`
+    raises without one.  `project_image_features` runs the projector on precomputed features
     ([B, 257, 1280] for the Resampler, [B, 1024] for ImageProjModel)."""
 
     def __init__(self, cond_img_config=None, finegrained=False, random_cond=False, *args, **kwargs):
@@ -217,6 +218,7 @@ class LatentVisualDiffusion(DenoiseModel):
     def get_image_embeds(self, batch_imgs):
         """ddpm3d.py:689-693: img [b, c, h, w] -> image tokens [b, 16 | 4, 1024]"""
         if self.embedder is None:
-            raise RuntimeError("LatentVisualDiffusion has no image embedder: cond_img_config's target did not import (the OpenCLIP vision "
-                               "tower is not part of this package); assign `.embedder` or call project_image_features on features")
+            raise RuntimeError("LatentVisualDiffusion has no image embedder: cond_img_config's target did not import (the HIP vision tower "
+                               "is moca_video_amd.clip_vision.FrozenOpenCLIPImageEmbedderV2); assign `.embedder` or call "
+                               "project_image_features on features")
         return self.image_proj_model(self.embedder(batch_imgs))
