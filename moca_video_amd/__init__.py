@@ -7,6 +7,8 @@ Public surface mirrors the reference interfaces for this path only:
   DDIMSampler          lvdm/models/samplers/ddim.py (make_schedule, p_sample_ddim, unet, ddim_step, fifo_onestep)
   freq_mix_3d, get_freq_filter   utils/freeinit_utils.py
   prepare_latents, shift_latents, fifo_ddim_sampling, base_ddim_sampling   scripts/evaluation/funcs.py
+  fifo_ddim_sampling_multiprompts   funcs.py:375-468 (one video, prompts switched inside the one-graph loop)
+  load_multiprompts, run_multiprompts   its prompt file and driver (moca_video_amd.io)
   instantiate_from_config       utils/utils.py:27-42
   AutoencoderKL                 lvdm/models/autoencoder.py:13-107 + lvdm/modules/networks/ae_modules.py:364-579
   FrozenOpenCLIPEmbedder        lvdm/modules/encoders/condition.py:174-235 (text tower on token ids)
@@ -28,7 +30,9 @@ from .tokenizer import SimpleTokenizer  # noqa: E402
 from .image_proj import ImageProjModel, Resampler  # noqa: E402
 from .clip_vision import FrozenOpenCLIPImageEmbedder, FrozenOpenCLIPImageEmbedderV2  # noqa: E402
 from .wrapper import LatentVisualDiffusion  # noqa: E402
+from .fifo import fifo_ddim_sampling_multiprompts  # noqa: E402
+from .io import load_multiprompts, run_multiprompts  # noqa: E402
 
 __all__ = ["UNetModel", "DiffusionWrapper", "DenoiseModel", "AutoencoderKL", "FrozenOpenCLIPEmbedder", "SimpleTokenizer", "ImageProjModel", "Resampler",
            "FrozenOpenCLIPImageEmbedder", "FrozenOpenCLIPImageEmbedderV2", "LatentVisualDiffusion", "instantiate_from_config",
-           "load_unet_config"]
+           "load_unet_config", "fifo_ddim_sampling_multiprompts", "load_multiprompts", "run_multiprompts"]

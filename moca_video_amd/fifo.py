@@ -157,7 +157,11 @@ def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg
     emission, FreeInit mix, shift -- is one hipGraph on a device-resident ring queue (fifo_graph.py) and the host never
     synchronises inside the loop; `latents` / `masks` are updated in place at the end like the reference's tensors.
     `noises[i][w]` / `shift_noises[i]` optionally fix the per-window DDIM noise and the enqueued noise (else: device Philox
-    stream keyed by `seed` on the graph path, torch.randn on the host path)."""
+    stream keyed by `seed` on the graph path, torch.randn on the host path).
+
+    `context_at(i)` (keyword; the hook of `fifo_ddim_sampling_multiprompts`): called at the top of iteration i; None keeps the
+    conditional context, a tensor [1,L,D] replaces it from this iteration on (same L; on the graph path `FifoEngine.set_context`)."""
+    context_at = kwargs.pop("context_at", None)
     kwargs.update({"clean_cond": True})
     refuse_image_attention(model)
     cond = conditioning
@@ -206,6 +210,9 @@ def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg
                          scale_factor=getattr(model, "scale_factor", 1.0), sam_capacity=sam_capacity if sam_in_graph else 0)
         try:
             for i in range(total):
+                ctx = None if context_at is None else context_at(i)
+                if ctx is not None:
+                    eng.set_context(ctx)
                 sm = sam_of(i)
                 if noises is not None or shift_noises is not None or anchor_noises is not None:
                     nz = noises[i] if noises is not None else [torch.randn(noise_shape, device=latents.device) for _ in eng.wins]
@@ -231,6 +238,9 @@ def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg
         return frames
 
     for i in range(total):
+        ctx = None if context_at is None else context_at(i)
+        if ctx is not None:
+            cond = dict(cond, c_crossattn=[ctx])
         wins = list(fifo_windows(args))
         eps_list = None
         if batch_windows:
@@ -277,6 +287,90 @@ def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg
                 masks[:, :, :-1] = masks[:, :, 1:].clone()
     if pending:
         frames.extend(decode_frames(model, pending))
+    return frames
+
+
+def multiprompt_segments(args, multiprompts, n_iterations=None):
+    """funcs.py:379,420-427: the prompt segment j of every outer iteration of `fifo_ddim_sampling_multiprompts`.  `multiprompts[-1]`
+    holds the comma-separated frame count of each prompt, prompt_lengths = their cumsum; the loop runs prompt_lengths[-1] + S - f
+    iterations (`n_iterations`: the trange cut) and at the top of iteration i moves j by at most one,
+    `if i - (S - f) >= prompt_lengths[j]: j += 1` -- a segment of 0 frames still lasts one iteration and the first S - f iterations
+    stay on prompt 0, exactly as in the reference.  ValueError where the reference would index past its last prompt."""
+    lengths = np.array([int(c) for c in multiprompts[-1].split(",")]).cumsum()
+    if len(lengths) != len(multiprompts) - 1:
+        raise ValueError(f"{len(lengths)} frame counts ({multiprompts[-1]!r}) for {len(multiprompts) - 1} prompts")
+    warm = args.num_inference_steps - args.video_length
+    total = int(lengths[-1]) + warm if n_iterations is None else int(n_iterations)
+    seg, j = [], 0
+    for i in range(total):
+        if i - warm >= lengths[j]:
+            j += 1
+            if j == len(lengths):
+                raise ValueError(f"iteration {i} runs past the last prompt (prompt_lengths {lengths.tolist()})")
+        seg.append(j)
+    return seg
+
+
+def fifo_ddim_sampling_multiprompts(args, model, conditioning, noise_shape, ddim_sampler, multiprompts, cfg_scale=1.0,
+                                    output_dir=None, latents_dir=None, save_frames=False, embeds=None, uc_emb=None, latents=None,
+                                    noises=None, shift_noises=None, seed=None, decode=False, decode_batch=8, n_iterations=None,
+                                    batch_windows=True, use_graph=True, conditioned_image=None, targets=None, sam_masks=None,
+                                    sam_masks_fn=None, sam_capacity=None, emit=None, **kwargs):
+    """funcs.py:375-468: one long video whose prompt changes over time.  `multiprompts` = [prompt_0, ..., prompt_n-1, "c_0,...,c_n-1"]
+    (frame counts); the prompt of every iteration follows `multiprompt_segments`, and all windows of an iteration use that ONE
+    prompt's context (77 tokens, not MoCA's two-prompt 154).  Returns what `fifo_ddim_sampling` returns, whose loop this is: on the
+    one-graph path a switch is `FifoEngine.set_context` between two replays (no new plan, no capture), on the host-driven path the
+    next iteration's conditioning.  `save_frames` (needs `decode=True`) writes `output_dir/fifo/{i}.png` like funcs.py:455-459.
+
+    embeds: the per-prompt contexts [1,77,D] (the prompt strings then only name the segments); without them the model's text
+    encoder embeds each prompt string (`model.get_learned_conditioning(prompt)`, funcs.py:382).  uc_emb: the unconditional
+    context, which here is the EMPTY PROMPT whatever `model.uncond_type` says (funcs.py:398-399); needed when the model has no text
+    encoder.  Queue: `latents`, else `prepare_latents` in prompt mode (`{S}.pt` under `latents_dir`); shifts in prompt mode.
+
+    `cond_image=` / `target=` (the reference's `fifo_onestep` keywords reached through **kwargs) are `conditioned_image` / `targets`:
+    every window then takes `ddim_step`'s segmentation branch (MoCA injection at t <= 300) with the Grounded-SAM-2 masks of
+    `sam_masks` / `sam_masks_fn`, as in `fifo_ddim_sampling`.  With neither nothing is injected -- the reference itself would fail
+    there (`target.endswith` on None at the first frame with t <= 300).  DAVIS inputs (`davis_data`, `davis_masks`: static masks
+    indexed relative to the window, no meaning in this loop) and an image-attention UNet are refused."""
+    for k in ("davis_data", "davis_masks"):
+        if kwargs.pop(k, None) is not None:
+            raise NotImplementedError(f"fifo_ddim_sampling_multiprompts has no DAVIS-video mode: {k} is not supported")
+    refuse_image_attention(model)
+    if save_frames and (not decode or output_dir is None):
+        raise ValueError("save_frames writes decoded frames: it needs decode=True and an output_dir")
+    conditioned_image = kwargs.pop("cond_image", conditioned_image)
+    targets = kwargs.pop("target", targets)
+    seg = multiprompt_segments(args, multiprompts, n_iterations)
+    n_prompts = len(multiprompts) - 1
+    text_encoder = getattr(model, "cond_stage_model", None) is not None
+    if embeds is None:
+        if not text_encoder:
+            raise ValueError("the model has no text encoder: pass the prompt contexts as embeds=[embed_text(p) for p in prompts]")
+        embeds = [model.get_learned_conditioning(p) for p in multiprompts[:-1]]
+    if len(embeds) != n_prompts:
+        raise ValueError(f"embeds holds {len(embeds)} contexts for {n_prompts} prompts")
+    if cfg_scale != 1.0 and uc_emb is None:
+        if not text_encoder:
+            raise ValueError('the unconditional context is the empty prompt (funcs.py:398-399): pass uc_emb=embed_text("")')
+        b = noise_shape[0]
+        uc_emb = model.get_learned_conditioning(model.empty_prompt_tokens.expand(b, -1) if hasattr(model, "empty_prompt_tokens")
+                                                else b * [""])
+    cond = dict(conditioning or {})          # (the reference rewrites the caller's dict each iteration; this one stays as it was)
+    cond["c_crossattn"] = [embeds[seg[0] if seg else 0]]
+    if latents is None:
+        latents = prepare_latents(args, latents_dir, ddim_sampler)
+
+    def switch(i):                           # set_context only where j changes
+        return embeds[seg[i]] if i > 0 and seg[i] != seg[i - 1] else None
+    frames = fifo_ddim_sampling(args, model, cond, noise_shape, ddim_sampler, cfg_scale, uc_emb=uc_emb, latents=latents,
+                                conditioned_image=conditioned_image, emit=emit, n_iterations=len(seg), batch_windows=batch_windows,
+                                noises=noises, shift_noises=shift_noises, decode=decode, decode_batch=decode_batch,
+                                sam_masks=sam_masks, sam_masks_fn=sam_masks_fn, targets=targets, use_graph=use_graph, seed=seed,
+                                sam_capacity=sam_capacity, context_at=switch, **kwargs)
+    if save_frames:
+        import os
+        from .io import save_frames as write_frames
+        write_frames([tensor2image(fr) for fr in frames], os.path.join(output_dir, "fifo"))
     return frames
 
 

@@ -270,6 +270,24 @@ class FifoEngine:
         self.sam_tab.copy_(tab, non_blocking=True)
         ev.record(self.plan.stream)
 
+    def set_context(self, cond_ctx):
+        """The prompt switch of funcs.py:426-430: replace the conditional windows' context rows of `plan.ctx` between two iterations.
+        `cond_ctx` [1,L,D] (or a `c_crossattn` list, concatenated as the constructor does) must have the token count L the plan was
+        built with.  The copy is enqueued on the plan's stream, after the iteration enqueued last and before the next one, whose
+        in-graph K|V projection (`_Plan.kv_all`, a recorded step) reads it; nothing else of the plan is derived from the context, so
+        no plan is rebuilt and no graph re-captured.  The unconditional rows, the queue and the device state stay as they are."""
+        c = torch.cat(list(cond_ctx), 1) if isinstance(cond_ctx, (list, tuple)) else cond_ctx
+        L = self.plan.segs[0][1]
+        if c.dim() != 3 or c.shape[0] != 1 or c.shape[1] != L:
+            raise ValueError(f"set_context: the plan's conditional segment holds [1, {L}, D] contexts, got {tuple(c.shape)}")
+        plan = self.plan
+        cur = torch.cuda.current_stream(self.device)
+        src = c.to(self.device)
+        plan.stream.wait_stream(cur)
+        with torch.cuda.stream(plan.stream):
+            plan.set_context([src.expand(self.nW, -1, -1)])       # (only the first segment: zip over the plan's segments)
+        src.record_stream(plan.stream)
+
     # ------------------------------------------------------------------------------------------------------------------
     def step(self, noise=None, shift_noise=None, anchor_noise=None, sam_masks=None):
         """one outer iteration (enqueued, not synchronised).  `noise` = list over windows (reference order: rank 2n-1 .. 0) of

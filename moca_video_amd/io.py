@@ -13,7 +13,7 @@ import os
 
 import torch
 
-from .fifo import base_ddim_sampling, fifo_ddim_sampling, fifo_windows, prepare_latents, tensor2image
+from .fifo import base_ddim_sampling, fifo_ddim_sampling, fifo_ddim_sampling_multiprompts, fifo_windows, prepare_latents, tensor2image
 from .sampler import DDIMSampler
 
 _FIELDS = ("prompt", "conditioned_object", "conditioned_image_path", "conditioned_prompt", "gamma")
@@ -233,6 +233,59 @@ def run_prompts(args, model, embed_text, cond_image_fn=None, mask_fn=None, root=
             torch.save(torch.cat(keep, dim=2).cpu(), path)
         done[idx] = path
     return done
+
+
+def load_multiprompts(path):
+    """A multi-prompt file: one prompt per line, the last line the comma-separated frame count of each prompt (`40,60`); blank
+    lines are skipped.  Returns the list layout `fifo_ddim_sampling_multiprompts` takes (funcs.py:375-382):
+    [prompt_0, ..., prompt_n-1, "c_0,...,c_n-1"]."""
+    with open(path, "r") as f:
+        lines = [line.strip() for line in f if line.strip()]
+    if len(lines) < 2:
+        raise ValueError(f"{path}: needs at least one prompt line and a line of frame counts")
+    counts = [int(c) for c in lines[-1].split(",")]
+    if len(counts) != len(lines) - 1:
+        raise ValueError(f"{path}: {len(counts)} frame counts for {len(lines) - 1} prompts")
+    return lines[:-1] + [",".join(str(c) for c in counts)]
+
+
+def run_multiprompts(args, model, embed_text, multiprompts, cond_image=None, root=".", uc_emb=None, decode=True, n_iterations=None,
+                     sam_masks=None, sam_masks_fn=None, targets=None):
+    """One long video whose prompt changes over time (`fifo_ddim_sampling_multiprompts`, funcs.py:375-468) on the drop-in classes.
+    `multiprompts` = the list layout or a file for `load_multiprompts`; `embed_text` as in run_prompts, called once per prompt and
+    once for "" (the loop's unconditional context).  The base sampling that leaves the `{S}.pt` cache runs on the FIRST prompt as
+    in run_prompts (skipped when the cache exists), then the multi-prompt FIFO loop; `cond_image` / `targets` / `sam_masks` /
+    `sam_masks_fn` feed the segmentation branch as in `fifo_ddim_sampling`.  Writes the frames of the prompt segments (the last
+    sum-of-counts emitted frames) as `fifo_multiprompt.gif`, or their latents as `fifo_multiprompt_latents.pt`; returns the path."""
+    if isinstance(multiprompts, str):
+        multiprompts = load_multiprompts(multiprompts)
+    prompts = multiprompts[:-1]
+    embeds = [embed_text(p) for p in prompts]
+    h, w = args.height // 8, args.width // 8
+    out_dir, lat_dir = set_directory(args, prompts[0], root=root)
+    noise_shape = [1, 4, args.video_length, h, w]
+    fps = torch.tensor([args.fps], device=model.device).long()
+    cond = {"c_crossattn": [embeds[0]], "fps": fps}
+    if os.path.exists(f"{lat_dir}/{args.num_inference_steps}.pt") and os.path.exists(f"{lat_dir}/0.pt"):
+        sampler = DDIMSampler(model)
+        sampler.make_schedule(ddim_num_steps=args.num_inference_steps, ddim_eta=args.eta, verbose=False)
+    else:
+        base, sampler, _ = base_ddim_sampling(model, cond, noise_shape, args.num_inference_steps, args.eta,
+                                              args.unconditional_guidance_scale, uc_emb=_empty_prompt_embedding(model, embed_text, uc_emb),
+                                              latents_dir=lat_dir)
+        if decode and base is not None:
+            save_gif(base, out_dir, "origin")
+    frames = fifo_ddim_sampling_multiprompts(args, model, cond, noise_shape, sampler, multiprompts, args.unconditional_guidance_scale,
+                                             output_dir=out_dir, latents_dir=lat_dir, embeds=embeds,
+                                             uc_emb=embed_text("") if uc_emb is None else uc_emb, decode=decode,
+                                             n_iterations=n_iterations, conditioned_image=cond_image, targets=targets,
+                                             sam_masks=sam_masks, sam_masks_fn=sam_masks_fn)
+    keep = frames[-sum(int(c) for c in multiprompts[-1].split(",")):] if frames else frames
+    if decode:
+        return save_gif(torch.cat(keep, dim=2), out_dir, "fifo_multiprompt", duration_ms=int(1000 / args.output_fps))
+    path = os.path.join(out_dir, "fifo_multiprompt_latents.pt")
+    torch.save(torch.cat(keep, dim=2).cpu(), path)
+    return path
 
 
 def run_davis(args, model, embed_text, prompt, cond_image=None, root=".", uc_emb=None, decode=True, n_iterations=None):
