@@ -303,6 +303,12 @@ int moca_temporal_attention_f16(const void* q, const void* k, const void* v, voi
  * (openaimodel3d.py:552-554) */
 int moca_ncthw_to_nhwc_f16(const void* x, int32_t x_is_f32, void* y, int32_t B, int32_t Cin,
                            int32_t T, int32_t HW, int32_t Cpad, void* stream);
+/* One piece of the channel concat in front of the first conv (`torch.cat([x] + c_concat, dim=1)`, ddpm3d.py:715), without the
+ * concat: x [B][k][T][H][W] (f32 or f16) -> columns [c0, c0 + k) of the channels-last fp16 rows [B*T][H*W][Cpad]; the other
+ * columns keep what they hold (pad columns are zeroed once by the owner of the rows).  Cpad is 8 or 16, c0 + k <= Cpad, y is
+ * 16-byte aligned. */
+int moca_ncthw_scatter_f16(const void* x, int32_t x_is_f32, void* y, int32_t B, int32_t k, int32_t T,
+                           int32_t HW, int32_t Cpad, int32_t c0, void* stream);
 /* channels-last fp16 [B*T][H*W][ld] (first Cout columns) -> [B][Cout][T][H][W] f32/f16
  * (openaimodel3d.py:573-577) */
 int moca_nhwc_to_ncthw(const void* y, int32_t ld, void* x, int32_t x_is_f32, int32_t B,

@@ -22,6 +22,33 @@ __global__ __launch_bounds__(256) void ncthw_to_nhwc_kernel(const TIN* __restric
     }
 }
 
+// x [B][k][T][HW] -> columns [c0, c0 + k) of y [(b*T+t)*HW + p][Cpad] fp16; the other columns of a row are not touched.  One piece of
+// the channel concat `torch.cat([x] + c_concat, dim=1)` in front of the first conv (ddpm3d.py:715): the concat itself never exists
+template <typename TIN>
+__global__ __launch_bounds__(256) void ncthw_scatter_kernel(const TIN* __restrict__ x, half_t* __restrict__ y,
+                                                            int B, int k, int T, int HW, int Cpad, int c0) {
+    const int64_t total = (int64_t)B * T * HW;
+    const bool quads = (k % 4 == 0) && (c0 % 4 == 0);          // 8-byte stores: rows are 16 / 32 bytes, c0 a multiple of 4 halves
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < total; r += (int64_t)gridDim.x * 256) {
+        const int p = (int)(r % HW);
+        const int64_t bt = r / HW;
+        const int t = (int)(bt % T), b = (int)(bt / T);
+        const TIN* src = x + (((int64_t)b * k) * T + t) * HW + p;
+        const int64_t cs = (int64_t)T * HW;                    // channel stride of the source
+        half_t* dst = y + r * Cpad + c0;
+        if (quads) {
+            for (int c = 0; c < k; c += 4) {
+                half4v h;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) h[q] = (half_t)(float)src[(c + q) * cs];
+                *reinterpret_cast<half4v*>(dst + c) = h;
+            }
+        } else {
+            for (int c = 0; c < k; ++c) dst[c] = (half_t)(float)src[c * cs];
+        }
+    }
+}
+
 template <typename TOUT>
 __global__ __launch_bounds__(256) void nhwc_to_ncthw_kernel(const half_t* __restrict__ y, int ld, TOUT* __restrict__ x,
                                                             int B, int Cout, int T, int HW) {
@@ -174,6 +201,21 @@ extern "C" int moca_ncthw_to_nhwc_f16(const void* x, int32_t x_is_f32, void* y, 
     else
         hipLaunchKernelGGL(ncthw_to_nhwc_kernel<half_t>, dim3(g), dim3(256), 0, moca_stream(stream),
                            reinterpret_cast<const half_t*>(x), reinterpret_cast<half_t*>(y), B, Cin, T, HW, Cpad);
+    MOCA_CHECK_LAUNCH();
+    return MOCA_OK;
+}
+
+extern "C" int moca_ncthw_scatter_f16(const void* x, int32_t x_is_f32, void* y, int32_t B, int32_t k, int32_t T, int32_t HW,
+                                      int32_t Cpad, int32_t c0, void* stream) {
+    if (!x || !y || B <= 0 || k <= 0 || T <= 0 || HW <= 0 || (Cpad != 8 && Cpad != 16) || c0 < 0 || c0 + k > Cpad) return MOCA_E_BADARG;
+    if ((uintptr_t)y & 15) return MOCA_E_BADARG;               // (rows of 16 / 32 bytes: the 8-byte stores stay aligned)
+    const int g = grid_for((int64_t)B * T * HW);
+    if (x_is_f32)
+        hipLaunchKernelGGL(ncthw_scatter_kernel<float>, dim3(g), dim3(256), 0, moca_stream(stream),
+                           reinterpret_cast<const float*>(x), reinterpret_cast<half_t*>(y), B, k, T, HW, Cpad, c0);
+    else
+        hipLaunchKernelGGL(ncthw_scatter_kernel<half_t>, dim3(g), dim3(256), 0, moca_stream(stream),
+                           reinterpret_cast<const half_t*>(x), reinterpret_cast<half_t*>(y), B, k, T, HW, Cpad, c0);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }

@@ -87,6 +87,17 @@ def refuse_image_attention(model):
                                   "its 154-token two-prompt context would be read as 77 text + 77 image tokens")
 
 
+def refuse_concat(model, cond=None):
+    """FIFO / MoCA sampling has no channel-concatenated conditioning: the reference's loop hands every window the whole `cond`
+    and never slices `c_concat` along the queue, so there is no behaviour to reproduce.  Raise instead of computing something."""
+    from .wrapper import HYBRID_KEYS
+    key = getattr(getattr(model, "model", None), "conditioning_key", None)
+    if key in HYBRID_KEYS or (isinstance(cond, dict) and cond.get("c_concat") is not None):
+        raise NotImplementedError(f"FIFO / MoCA sampling with channel-concatenated conditioning (conditioning_key={key!r}, c_concat) is "
+                                  "not supported: the queue's windows would each need their own slice of c_concat; use "
+                                  "base_ddim_sampling")
+
+
 def uncond_embedding(model, c_emb, uc_emb):
     """The unconditional context of funcs.py:199-208 / :268-270: `model.uncond_type == "empty_seq"` (the YAML's value) is
     the text encoding of the EMPTY PROMPT -- it needs the text encoder, so the caller must pass it (`uc_emb`, e.g.
@@ -164,6 +175,7 @@ def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg
     context_at = kwargs.pop("context_at", None)
     kwargs.update({"clean_cond": True})
     refuse_image_attention(model)
+    refuse_concat(model, conditioning)
     cond = conditioning
     uc = None
     if cfg_scale != 1.0:
@@ -336,6 +348,7 @@ def fifo_ddim_sampling_multiprompts(args, model, conditioning, noise_shape, ddim
         if kwargs.pop(k, None) is not None:
             raise NotImplementedError(f"fifo_ddim_sampling_multiprompts has no DAVIS-video mode: {k} is not supported")
     refuse_image_attention(model)
+    refuse_concat(model, conditioning)
     if save_frames and (not decode or output_dir is None):
         raise ValueError("save_frames writes decoded frames: it needs decode=True and an output_dir")
     conditioned_image = kwargs.pop("cond_image", conditioned_image)

@@ -67,8 +67,9 @@ class FifoEngine:
         """sam_capacity > 0 (and no `masks`): prompt mode with precomputed Grounded-SAM-2 candidates -- `ddim_step`'s segmentation
         branch (ddim.py:592-606 -> `_apply_segmentation` :739-903) runs inside the iteration graph on at most `sam_capacity`
         candidate masks per iteration, handed to `step(sam_masks=...)`."""
-        from .fifo import refuse_image_attention
+        from .fifo import refuse_concat, refuse_image_attention
         refuse_image_attention(model)
+        refuse_concat(model, cond)
         self.unet = unet = model.model.diffusion_model
         dev = latents.device
         self.device = dev
@@ -359,8 +360,24 @@ class BaseEngine:
     def supported(model, x, cond, uc, scale):
         unet = getattr(getattr(model, "model", None), "diffusion_model", None)
         ok = isinstance(unet, UNetModel) and x.is_cuda and isinstance(cond, dict) and isinstance(uc, dict) and scale != 1.0
-        return ok and set(cond.keys()) == set(uc.keys()) <= {"c_crossattn", "fps"} and \
-            getattr(model.model, "conditioning_key", None) == "crossattn" and 2 * x.shape[0] <= 64 and \
+        if not ok or set(cond.keys()) != set(uc.keys()) or 2 * x.shape[0] > 64:
+            return False
+        key = getattr(model.model, "conditioning_key", None)
+        if key in ("hybrid", "hybrid-adm-mask"):
+            # (the other hybrid keys need c_adm / s: they stay on the host-issued path, which keeps the reference's asserts.)  Both
+            # guidance branches must see the SAME c_concat (funcs.py:211-214 copies cond and replaces c_crossattn only): the shared
+            # prefix holds one set of input rows.  fps is dropped by these keys (ddpm3d.py:717), so nothing to compare
+            a, b = cond.get("c_concat"), uc.get("c_concat")
+            if a is None and key == "hybrid":
+                return False
+            # a wrong channel total goes to the host-issued path, whose wrapper names it in a ValueError
+            if x.shape[1] + sum(int(c.shape[1]) for c in a or ()) != unet.in_channels:
+                return False
+            same = a is b or (a is not None and b is not None and len(a) == len(b) and all(
+                p is q or (p.data_ptr() == q.data_ptr() and p.shape == q.shape and p.stride() == q.stride() and p.dtype == q.dtype)
+                for p, q in zip(a, b)))
+            return same and set(cond.keys()) <= {"c_crossattn", "fps", "c_concat"}
+        return set(cond.keys()) <= {"c_crossattn", "fps"} and key == "crossattn" and \
             same_fps([cond.get("fps", 16), uc.get("fps", 16)])      # (the shared prefix adds ONE fps embedding)
 
     def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, keep_pred_x0=False):
@@ -375,7 +392,12 @@ class BaseEngine:
         self.S = S
         cc, cu = torch.cat(cond["c_crossattn"], 1), torch.cat(uc["c_crossattn"], 1)
         segs = ((B, int(cc.shape[1])), (B, int(cu.shape[1])))
-        self.plan = plan = _Plan(unet, 2 * B, T, H, W, segs, torch.float32, dev, shared_x=True)
+        # hybrid keys: x carries the latent channels only; the c_concat columns of the first conv's input rows are constant over a
+        # trajectory (reset() writes them), the recorded step rewrites the latent columns from plan.x_in; fps is dropped (16)
+        self.hybrid = getattr(model.model, "conditioning_key", None) != "crossattn"
+        concat = cond.get("c_concat") if self.hybrid else None
+        pieces = None if concat is None else tuple(int(c.shape[1]) for c in concat)
+        self.plan = plan = _Plan(unet, 2 * B, T, H, W, segs, torch.float32, dev, shared_x=True, pieces=pieces)
 
         def fps_rows(fp):
             if isinstance(fp, int):
@@ -416,7 +438,8 @@ class BaseEngine:
         """start a new trajectory on the same plan: latents x_T, contexts, fps, iteration 0, a new noise stream"""
         plan, dev = self.plan, self.device
         B = self.shape[0]
-        if not same_fps([cond.get("fps", 16), uc.get("fps", 16)]):
+        fps_c, fps_u = (16, 16) if self.hybrid else (cond.get("fps", 16), uc.get("fps", 16))
+        if not same_fps([fps_c, fps_u]):
             raise ValueError("BaseEngine shares the UNet prefix between the two guidance branches: their fps must be equal")
         cc, cu = (torch.cat(c["c_crossattn"], 1).expand(B, -1, -1) for c in (cond, uc))
         st = _l.FifoState(0, 0, seed & 0xffffffff, (seed >> 32) & 0xffffffff, 0)
@@ -425,8 +448,14 @@ class BaseEngine:
         with torch.cuda.stream(plan.stream):
             self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
             plan.x_in.copy_(x.to(torch.float32))
-            plan.fps_rows.copy_(torch.cat([self._fps_rows(cond.get("fps", 16)), self._fps_rows(uc.get("fps", 16))]))
+            plan.fps_rows.copy_(torch.cat([self._fps_rows(fps_c), self._fps_rows(fps_u)]))
             plan.set_context([cc, cu])
+            if plan.pieces is not None:
+                ops.set_stream(plan.stream.cuda_stream)
+                try:
+                    plan.set_concat(cond["c_concat"])
+                finally:
+                    ops.set_stream(None)
         cur.wait_stream(plan.stream)
         self.n_iter = 0
 

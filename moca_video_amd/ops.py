@@ -395,6 +395,17 @@ def ncthw_to_nhwc(x, y, *, B, Cin, T, HW, Cpad):
     return y
 
 
+def ncthw_scatter(x, y, *, B, k, T, HW, Cpad, c0):
+    """x [B][k][T][HW] (fp32 / fp16, contiguous) -> columns [c0, c0 + k) of the fp16 rows y [B*T*HW][Cpad]; other columns untouched"""
+    if x.dtype not in (torch.float32, torch.float16) or not x.is_contiguous() or x.numel() != B * k * T * HW:
+        raise ValueError("ncthw_scatter: x must be a contiguous fp32 / fp16 tensor of B * k * T * HW elements")
+    if y.dtype != torch.float16 or not y.is_contiguous() or y.numel() != B * T * HW * Cpad:
+        raise ValueError("ncthw_scatter: y must be the contiguous fp16 rows [B * T * HW][Cpad]")
+    _l.check(_l.load().moca_ncthw_scatter_f16(_l.ptr(x), 1 if x.dtype == torch.float32 else 0, _l.ptr(y), B, k, T, HW, Cpad, c0,
+                                              _st()), "moca_ncthw_scatter_f16")
+    return y
+
+
 def nhwc_to_ncthw(y, ld, x, *, B, Cout, T, HW):
     _l.check(_l.load().moca_nhwc_to_ncthw(_l.ptr(y), ld, _l.ptr(x), 1 if x.dtype == torch.float32 else 0, B, Cout, T, HW,
                                           _st()), "moca_nhwc_to_ncthw")

@@ -385,11 +385,15 @@ class _PlanBase:
 class _Plan(_PlanBase):
     _defer_slabs = True
 
-    def __init__(self, model, B, T, H, W, L, in_dtype, device, shared_x=False):
+    def __init__(self, model, B, T, H, W, L, in_dtype, device, shared_x=False, pieces=None):
         """shared_x: the B videos are `len(L)` context variants of the SAME B / len(L) latents (the two `apply_model` calls of
         classifier-free guidance, ddim.py:298-299,366-369, on one x): `x_in` holds the distinct latents only, everything up to the
         first cross-attention (conv_in, init_attn, the first ResBlock, the first SpatialTransformer's self-attention and to_q:
-        8 % of the forward) is computed once and repeated where the contexts first enter (`_expand`)."""
+        8 % of the forward) is computed once and repeated where the contexts first enter (`_expand`).
+        pieces: channel counts of the c_concat tensors of a `hybrid*` call (UNetModel.forward_concat): `x_in` holds the remaining
+        (latent) channels only, the first conv reads the persistent rows `x_rows` whose columns the sources are scattered into --
+        x_in's by a recorded launch, the c_concat ones by `set_concat` (outside the recorded sequence: they change per call on the
+        host-issued path and once per trajectory in fifo_graph.BaseEngine)."""
         self.image_attn = getattr(model, "use_image_attention", False)
         if self.image_attn:
             for Ls in ([L] if isinstance(L, int) else [l for _, l in L]):
@@ -417,7 +421,12 @@ class _Plan(_PlanBase):
             assert len(self.segs) > 1 and all(n == self.segs[0][0] for n, _ in self.segs)
             self.reps = len(self.segs)
         self.Bx = B // self.reps
-        self.x_in = torch.empty(self.Bx, m.in_channels, T, H, W, dtype=in_dtype, device=device)
+        self.pieces = None if pieces is None else tuple(int(k) for k in pieces)
+        self.kx = m.in_channels - sum(self.pieces or ())         # channels of x_in (all of them without c_concat)
+        if self.kx <= 0 or any(k <= 0 for k in self.pieces or ()):
+            raise ValueError(f"c_concat channels {self.pieces} leave no room for x in in_channels={m.in_channels}")
+        self.x_in = torch.empty(self.Bx, self.kx, T, H, W, dtype=in_dtype, device=device)
+        self.x_rows = None
         self.t_rows = torch.empty(self.BT, dtype=torch.int64, device=device)
         self.fps_rows = torch.empty(self.BT, dtype=torch.int64, device=device)
         self.ctx = torch.empty(self.ctx_rows, m.context_dim, dtype=torch.float16, device=device)
@@ -805,10 +814,18 @@ class _Plan(_PlanBase):
             self._pinned.add(self.kv_ip_all.data_ptr())
 
         FT = self.Bx * T                                         # frames of the distinct latents (= BT unless shared_x)
-        x8 = self.pool.get(FT * H * W, 8)
-        self._emit(ops.ncthw_to_nhwc, self.x_in, x8, B=self.Bx, Cin=m.in_channels, T=T, HW=H * W, Cpad=8)
-        h = self.conv(_FMap(x8, FT, H, W, 8), P[id(m.input_blocks[0][0])])
-        self._release(x8)
+        Cpad = m.in_cpad
+        if self.pieces is None:
+            x8 = self.pool.get(FT * H * W, Cpad)
+            self._emit(ops.ncthw_to_nhwc, self.x_in, x8, B=self.Bx, Cin=m.in_channels, T=T, HW=H * W, Cpad=Cpad)
+            h = self.conv(_FMap(x8, FT, H, W, Cpad), P[id(m.input_blocks[0][0])])
+            self._release(x8)
+        else:
+            # torch.cat([x] + c_concat, dim=1) (ddpm3d.py:715) never exists: the rows live outside the pool (the c_concat columns must
+            # survive from set_concat to the conv, and across the steps of a trajectory), pad columns zeroed here once
+            self.x_rows = torch.zeros(FT * H * W, Cpad, dtype=torch.float16, device=self.device)
+            self._emit(ops.ncthw_scatter, self.x_in, self.x_rows, B=self.Bx, k=self.kx, T=T, HW=H * W, Cpad=Cpad, c0=0)
+            h = self.conv(_FMap(self.x_rows, FT, H, W, Cpad), P[id(m.input_blocks[0][0])])
         hs = []
         for i, module in enumerate(m.input_blocks):
             if i == 0:
@@ -933,8 +950,25 @@ class _Plan(_PlanBase):
             r += nv * Lt
             ri += nv * (Ls - Lt)
 
-    def launch_async(self, x, t_rows, fps_rows, context, cur):
+    def set_concat(self, c_concat):
+        """write the c_concat tensors [Bx, k_i, T, H, W] into their columns of the first conv's input rows (launches on the current
+        ops stream; the latent columns [0, kx) belong to the recorded scatter of x_in)"""
+        if self.pieces is None or len(c_concat) != len(self.pieces):
+            raise ValueError(f"this plan was built for c_concat channels {self.pieces}")
+        c0 = self.kx
+        for k, c in zip(self.pieces, c_concat):
+            if tuple(c.shape) != (self.Bx, k, self.T, self.H, self.W):
+                raise ValueError(f"c_concat entry {tuple(c.shape)}: expected {(self.Bx, k, self.T, self.H, self.W)}")
+            if c.dtype not in (torch.float32, torch.float16):
+                c = c.float()
+            ops.ncthw_scatter(c.to(self.device).contiguous(), self.x_rows, B=self.Bx, k=k, T=self.T, HW=self.H * self.W,
+                              Cpad=self.x_rows.shape[1], c0=c0)
+            c0 += k
+
+    def launch_async(self, x, t_rows, fps_rows, context, cur, c_concat=None):
         """enqueue one forward on this plan's stream (ordered after `cur`); the caller joins"""
+        if (c_concat is None) != (self.pieces is None):
+            raise ValueError("c_concat goes with a plan built for it (UNetModel.forward_concat)")
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             self.x_in.copy_(x, non_blocking=True)
@@ -944,6 +978,8 @@ class _Plan(_PlanBase):
             handle = self.stream.cuda_stream
             ops.set_stream(handle)
             try:
+                if c_concat is not None:
+                    self.set_concat(c_concat)
                 self._launch(handle)
             finally:
                 ops.set_stream(None)
@@ -951,9 +987,9 @@ class _Plan(_PlanBase):
         self.n_runs += 1
         return out
 
-    def run(self, x, t_rows, fps_rows, context):
+    def run(self, x, t_rows, fps_rows, context, c_concat=None):
         cur = torch.cuda.current_stream(self.device)
-        out = self.launch_async(x, t_rows, fps_rows, context, cur)
+        out = self.launch_async(x, t_rows, fps_rows, context, cur, c_concat=c_concat)
         out.record_stream(cur)
         cur.wait_stream(self.stream)
         return out

@@ -198,7 +198,8 @@ class DDIMSampler(object):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())                  # the host generator seeds the device stream
             cu, cn = conditioning["c_crossattn"], unconditional_conditioning["c_crossattn"]
             key = (tuple(img.shape), sum(c.shape[1] for c in cu), sum(c.shape[1] for c in cn), float(unconditional_guidance_scale),
-                   self.ddim_timesteps.tobytes(), np.asarray(self.ddim_sigmas).tobytes(), str(img.device))
+                   self.ddim_timesteps.tobytes(), np.asarray(self.ddim_sigmas).tobytes(), str(img.device),
+                   tuple(int(c.shape[1]) for c in conditioning.get("c_concat") or ()))
             if self._base_engine is not None and self._base_engine[0] != key:
                 self._base_engine[1].close()
                 self._base_engine = None

@@ -23,6 +23,7 @@ from . import ops
 __all__ = ["UNetModel"]
 
 TEXT_CONTEXT_LEN = 77          # attention.py:60: context rows past these are image tokens (use_image_attention)
+IN_CHANNELS_MAX = 16           # latent + channel-concatenated conditioning (hybrid keys): 4 + 4 (i2v), 4 + 4 + 1 (inpainting)
 IMAGE_CONTEXT_MAX = 93         # longest image-attention context: 77 text + 16 image tokens (moca_attention_ip_f16's one key tile)
 
 
@@ -371,6 +372,7 @@ class UNetModel(nn.Module):
         if not conv_resample: unsupported.append("conv_resample=False")
         if num_head_channels != 64: unsupported.append("num_head_channels != 64 (kernels are head-dim 64)")
         if model_channels % 32 or model_channels % 64: unsupported.append("model_channels % 64 != 0")
+        if in_channels > IN_CHANNELS_MAX: unsupported.append(f"in_channels > {IN_CHANNELS_MAX} (the first conv's input rows hold 8 or 16 channels)")
         if unsupported:
             raise NotImplementedError("moca_video_amd.UNetModel covers the inference_t2v_512_v2.0.yaml surface; "
                                       "unsupported: " + ", ".join(unsupported))
@@ -447,6 +449,11 @@ class UNetModel(nn.Module):
         self.register_load_state_dict_post_hook(lambda m, k: m._invalidate())
         _l.load()                 # fail loudly at construction time if the HIP library is missing
 
+    @property
+    def in_cpad(self):
+        """channels per pixel of the first conv's fp16 input rows (zero padded)"""
+        return 8 if self.in_channels <= 8 else 16
+
     # ---- weights -----------------------------------------------------------------------
     def _invalidate(self):
         self._packed = None
@@ -470,14 +477,15 @@ class UNetModel(nn.Module):
             for m in (sq[0], sq[2]):
                 P[id(m)] = ops.pack_linear(m.weight.detach(), m.bias.detach(), device=dev)
         cin = self.input_blocks[0][0]
-        P[id(cin)] = ops.pack_conv3x3(cin.weight.detach(), cin.bias.detach(), cpad=8, device=dev)
+        P[id(cin)] = ops.pack_conv3x3(cin.weight.detach(), cin.bias.detach(), cpad=self.in_cpad, device=dev)
         P[id(self.out[0])] = (f32(self.out[0].weight), f32(self.out[0].bias))
         P[id(self.out[2])] = ops.pack_conv3x3(self.out[2].weight.detach(), self.out[2].bias.detach(), device=dev)
         self._packed = P
 
     # ---- forward -----------------------------------------------------------------------
-    def _prepare(self, x, timesteps, context, features_adapter, fps, check_context=True):
-        """argument checks + per-(b,t) timestep / fps rows shared by forward() and forward_concurrent()"""
+    def _prepare(self, x, timesteps, context, features_adapter, fps, check_context=True, concat_channels=0):
+        """argument checks + per-(b,t) timestep / fps rows shared by forward() and forward_concurrent(); `concat_channels`: channels
+        that reach the first conv beside x's (forward_concat)"""
         if features_adapter is not None:
             raise NotImplementedError("features_adapter is always None on the MoCA path")
         if context is None:
@@ -487,7 +495,7 @@ class UNetModel(nn.Module):
         if self._packed is None:
             self._pack()
         B, Cin, T, H, W = x.shape
-        assert Cin == self.in_channels
+        assert Cin + concat_channels == self.in_channels
         if T > 16:
             raise ValueError("temporal attention kernel supports T <= 16 (temporal_length of the YAML)")
         timesteps = torch.as_tensor(timesteps, device=x.device).reshape(-1).to(torch.int64)
@@ -516,19 +524,21 @@ class UNetModel(nn.Module):
             raise ValueError("context batch must equal x batch")
         return t_rows, fps_rows
 
-    def _plan_for(self, x, L, replica=0, shared_x=False):
+    def _plan_for(self, x, L, replica=0, shared_x=False, pieces=None):
         """L: context tokens, or a tuple of (videos, tokens) segments (see _Plan.segs); shared_x: x holds the distinct latents of
-        a batch that repeats them once per segment"""
+        a batch that repeats them once per segment; pieces: channel counts of the c_concat tensors (forward_concat)"""
         B, _, T, H, W = x.shape
         if shared_x:
             B *= len(L)
         key = (B, T, H, W, L, x.dtype, x.device.index, replica, shared_x)
+        if pieces is not None:
+            key += (pieces,)
         plan = self._plans.get(key)
         if plan is None and getattr(self, "_packed_only", False):
             raise RuntimeError("this rank received the packed operand set of the plans built before dist.broadcast_packed and holds no "
                                "parameters to pack a new plan from")
         if plan is None:
-            plan = _Plan(self, B, T, H, W, L, x.dtype, x.device, shared_x=shared_x)
+            plan = _Plan(self, B, T, H, W, L, x.dtype, x.device, shared_x=shared_x, pieces=pieces)
             self._plans[key] = plan
         return plan
 
@@ -539,6 +549,24 @@ class UNetModel(nn.Module):
         fps int or [B]; unknown kwargs (clean_cond, gamma, ...) are ignored exactly as upstream."""
         t_rows, fps_rows = self._prepare(x, timesteps, context, features_adapter, fps)
         return self._plan_for(x, context.shape[1]).run(x, t_rows, fps_rows, context)
+
+    @torch.no_grad()
+    def forward_concat(self, x, c_concat, timesteps, context=None, fps=16, **kwargs):
+        """forward(torch.cat([x] + c_concat, dim=1), ...) without the concat (the `hybrid*` keys of DiffusionWrapper, ddpm3d.py:713-759):
+        x [B,kx,T,h,w] and every c_concat entry [B,k_i,T,h,w] are written straight into their channel columns of the first conv's
+        input rows (moca_ncthw_scatter_f16); kx + sum k_i must be `in_channels`.  Same kernels on the same operands as the plain
+        forward of the materialised concat from the first conv on."""
+        c_concat = list(c_concat)
+        pieces = tuple(int(c.shape[1]) for c in c_concat)
+        if x.dim() != 5 or any(c.dim() != 5 or c.shape[:1] + c.shape[2:] != x.shape[:1] + x.shape[2:] for c in c_concat):
+            raise ValueError("c_concat entries must be [B, k, T, h, w] with the batch, frames and size of x")
+        if x.shape[1] + sum(pieces) != self.in_channels:
+            raise ValueError(f"x has {x.shape[1]} channels and c_concat {list(pieces)}: {x.shape[1] + sum(pieces)} in all, the UNet was "
+                             f"built with in_channels={self.in_channels}")
+        if not c_concat:
+            return self.forward(x, timesteps, context=context, fps=fps)
+        t_rows, fps_rows = self._prepare(x, timesteps, context, None, fps, concat_channels=sum(pieces))
+        return self._plan_for(x, context.shape[1], pieces=pieces).run(x, t_rows, fps_rows, context, c_concat=c_concat)
 
     @torch.no_grad()
     def forward_segments(self, x, timesteps, contexts, fps=16, shared_x=False):

@@ -1,5 +1,5 @@
 """Drop-in boundary above the UNet: `DiffusionWrapper.forward` (lvdm/models/ddpm3d.py:702-763,
-`crossattn` branch :710-712) and the slice of `LatentDiffusion` the samplers touch:
+`crossattn` branch :710-712 and the `hybrid*` branches :713-759) and the slice of `LatentDiffusion` the samplers touch:
 `apply_model` (:512-527), the DDPM schedule buffers (`register_schedule`, :113-165) and
 `scale_arr` (:362-376).  VAE / text encoder / training scaffolding are out of scope."""
 from __future__ import annotations
@@ -58,9 +58,18 @@ def load_unet_config(yaml_path):
     return cfg["model"]["params"]["unet_config"], cfg["model"]["params"]
 
 
+# conditioning latents concatenated to x along the channel axis + a cross-attention context (ddpm3d.py:713-717,724-733,747-759)
+HYBRID_KEYS = ("hybrid", "hybrid-adm", "hybrid-time", "hybrid-adm-mask", "hybrid-time-adm")
+# keys whose branch calls the UNet with context=None: the reference's own UNet fails there (openaimodel3d.py:547,
+# `context.repeat_interleave` on None)
+CONTEXT_FREE_KEYS = (None, "concat", "adm", "resblockcond", "concat-time-mask", "concat-adm-mask")
+
+
 class DiffusionWrapper(nn.Module):
-    """lvdm/models/ddpm3d.py:696-763 -- only the conditioning modes reachable from the YAML
-    (`crossattn`; `None` kept for completeness) are implemented, the rest raise like upstream."""
+    """lvdm/models/ddpm3d.py:696-763: `crossattn` and the five `hybrid*` keys (x and the `c_concat` latents concatenated along the
+    channel axis, `c_crossattn` as the context).  The hybrid branches keep the reference's argument handling: `**kwargs` (so a
+    `fps` of the conditioning dict) are NOT forwarded and the UNet runs with its default fps=16; `y=` / `s=` / `mask=` are passed
+    and ignored by the UNet as upstream.  The concat is not materialised for our UNet (`UNetModel.forward_concat`)."""
 
     def __init__(self, diff_model_config, conditioning_key):
         super().__init__()
@@ -71,9 +80,45 @@ class DiffusionWrapper(nn.Module):
         if self.conditioning_key == 'crossattn':
             cc = torch.cat(c_crossattn, 1)                                   # :711
             out = self.diffusion_model(x, t, context=cc, **kwargs)           # :712
+        elif self.conditioning_key == 'hybrid':
+            out = self._hybrid(x, t, c_concat, c_crossattn)                  # :715-717 (no **kwargs: fps is dropped)
+        elif self.conditioning_key == 'hybrid-adm':
+            assert c_adm is not None                                         # :725
+            out = self._hybrid(x, t, c_concat, c_crossattn, y=c_adm)
+        elif self.conditioning_key == 'hybrid-time':
+            assert s is not None                                             # :730
+            out = self._hybrid(x, t, c_concat, c_crossattn, s=s)
+        elif self.conditioning_key == 'hybrid-adm-mask':
+            out = self._hybrid(x, t, c_concat, c_crossattn, concat_optional=True, y=s, mask=mask)     # :748-753
+        elif self.conditioning_key == 'hybrid-time-adm':
+            assert c_adm is not None                                         # :756
+            out = self._hybrid(x, t, c_concat, c_crossattn, s=s, y=c_adm)
+        elif self.conditioning_key in CONTEXT_FREE_KEYS:
+            raise NotImplementedError(f"conditioning_key={self.conditioning_key!r} calls the UNet without a context, which the reference's "
+                                      "own UNet cannot run either (openaimodel3d.py:547: context.repeat_interleave on None)")
         else:
-            raise NotImplementedError(f"conditioning_key={self.conditioning_key!r} is outside the MoCA hot path")
+            raise NotImplementedError(f"conditioning_key={self.conditioning_key!r}")
         return out
+
+    def _hybrid(self, x, t, c_concat, c_crossattn, concat_optional=False, **unet_kwargs):
+        """`xc = torch.cat([x] + c_concat, dim=1); diffusion_model(xc, t, context=cat(c_crossattn, 1), **unet_kwargs)`"""
+        cc = torch.cat(c_crossattn, 1)
+        if c_concat is None and concat_optional:
+            pieces = []                                                      # :749-752 (`xc = x`)
+        else:
+            if c_concat is None:
+                raise TypeError("c_concat is None (upstream: `[x] + c_concat`); only 'hybrid-adm-mask' runs without it")
+            pieces = list(c_concat)
+        want = getattr(self.diffusion_model, "in_channels", None)
+        total = x.shape[1] + sum(int(p.shape[1]) for p in pieces)
+        if want is not None and total != want:
+            raise ValueError(f"conditioning_key={self.conditioning_key!r}: x has {x.shape[1]} channels and c_concat "
+                             f"{[int(p.shape[1]) for p in pieces]}, {total} in all; the UNet was built with in_channels={want}")
+        if not pieces:
+            return self.diffusion_model(x, t, context=cc, **unet_kwargs)
+        if hasattr(self.diffusion_model, "forward_concat"):                  # our UNet: the pieces go straight into the first conv's rows
+            return self.diffusion_model.forward_concat(x, pieces, t, context=cc, **unet_kwargs)
+        return self.diffusion_model(torch.cat([x] + pieces, dim=1), t, context=cc, **unet_kwargs)
 
 
 def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2):
