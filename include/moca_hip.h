@@ -103,6 +103,9 @@ typedef struct moca_gemm_params {
                               bottom/right (F.pad(x,(0,1,0,1)) + conv pad 0: ae_modules.py Downsample.forward);
                               0 = the symmetric padding 1 of every other 3x3 conv                              */
     int32_t prefetch_kib;  /* size of `prefetch` in KiB (0: none) */
+    int32_t tattn_causal;  /* MOCA_EP_TATTN: 1 = causal mask (TemporalTransformer(causal_attention=True), attention.py:309-311,342-346 ->
+                              :101-105): key frame > query frame gets -inf before the row maximum of the epilogue's softmax; 0 = none.
+                              Needs tattn_scale > 0; 0 without MOCA_EP_TATTN.  (Fills what was padding in front of `colsum`.)      */
     float*      colsum;    /* MOCA_EP_COLSUM: f32 [ceil(M/rows)][N][2] = (sum, sum of squares) over the rows of each
                               row tile (rows = moca_gemm_colsum_rows()), of the values as stored (after bias / row add /
                               residual, before the fp16 rounding)                                                      */
@@ -172,7 +175,8 @@ int moca_gemm_rowsum_cols(const moca_gemm_params* p);
  * two-blocks-per-CU kernel, fp16 output, no split-K); else 0 (the caller then runs moca_layernorm_f16 first).           */
 int moca_gemm_lnfold_ok(const moca_gemm_params* p);
 /* 1 when this call can run as MOCA_EP_TATTN (linear, K % 64 == 0, N % 192 == 0, T == 16, HW % 20 == 0, M % (16 HW) == 0,
- * no split-K / residual / row add); else 0 (the caller then runs the projection and moca_temporal_attention_f16).       */
+ * no split-K / residual / row add; tattn_causal 0, or 1 with tattn_scale > 0); else 0 (the caller then runs the projection and
+ * moca_temporal_attention_f16 / moca_temporal_attention_causal_f16).  Answers for the call as given, tattn_causal included. */
 int moca_gemm_tattn_ok(const moca_gemm_params* p);
 /* 1 when this call (wgroup_rows / wgroup_stride set) can take per-row-group weights (see moca_gemm_params.wgroup_rows); else 0 (the
  * caller then runs the GroupNorm as a pass of its own).  moca_gemm_colsum_rows / _ln_ok / _rowsum_cols answer for the call WITH
@@ -297,6 +301,13 @@ int moca_attention_causal_f16(const void* q, const void* k, const void* v, void*
 int moca_temporal_attention_f16(const void* q, const void* k, const void* v, void* out,
                                 int32_t B, int32_t T, int32_t HW, int32_t heads,
                                 int32_t ld_qkv, int32_t ldo, float scale, void* stream);
+/* The same with the causal mask of TemporalTransformer(causal_attention=True): frame t attends to frames <= t.  Replaces
+ * `self.mask = torch.tril(torch.ones([1, temporal_length, temporal_length]))` (attention.py:309-311), its repeat over the
+ * (b h w) batch (:342-346) and `sim.masked_fill_(~(mask>0.5), max_neg_value)` in front of the softmax (:101-105, reached
+ * through BasicTransformerBlock._forward :217-218 for attn1 AND attn2).  scale > 0.                                          */
+int moca_temporal_attention_causal_f16(const void* q, const void* k, const void* v, void* out,
+                                       int32_t B, int32_t T, int32_t HW, int32_t heads,
+                                       int32_t ld_qkv, int32_t ldo, float scale, void* stream);
 
 /* ---- layout / embedding helpers ----------------------------------------------- */
 /* x [B][Cin][T][H][W] (f32 or f16) -> channels-last fp16 [B*T][H*W][Cpad], zero padded

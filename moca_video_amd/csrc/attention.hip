@@ -705,6 +705,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 2) void attention_v4_kernel(
 // ---- temporal attention: one wavefront per (video, pixel, head), T <= 16 -------
 constexpr int TV_ROWB = 144;  // 128 B + 16 B pad per V row in LDS
 
+// CAUSAL (TemporalTransformer(causal_attention=True): attention.py:309-311,342-346 -> :101-105): a frame attends to itself and
+// earlier frames only.  In the S^T register layout a key above the query gets -inf BEFORE the row maximum; the diagonal is never
+// masked, so the maximum is finite and exp2f(-inf) = 0 exactly -- the values of masked_fill_(-finfo.max) followed by softmax.
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void temporal_attention_kernel(
     const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v, half_t* __restrict__ out,
     int B, int T, int HW, int heads, int ld, int ldo, float scale_log2e) {
@@ -753,6 +757,7 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         if (4 * fg + r >= T) s[r] = -INFINITY;
+        if (CAUSAL && 4 * fg + r > fr) s[r] = -INFINITY;
         mx = fmaxf(mx, s[r]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -882,18 +887,30 @@ extern "C" int moca_attention_causal_f16(const void* q, const void* k, const voi
     return MOCA_OK;
 }
 
-extern "C" int moca_temporal_attention_f16(const void* q, const void* k, const void* v, void* out,
-                                           int32_t B, int32_t T, int32_t HW, int32_t heads,
-                                           int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
+static int launch_temporal_attention(bool causal, const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T, int32_t HW,
+                                     int32_t heads, int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
     if (!q || !k || !v || !out) return MOCA_E_BADARG;
     if (B <= 0 || T <= 0 || T > 16 || HW <= 0 || heads <= 0) return MOCA_E_BADARG;
     if (ld_qkv % 8 || ldo % 4 || ld_qkv < heads * D || ldo < heads * D) return MOCA_E_BADARG;
     const int64_t total = (int64_t)B * HW * heads;
     const dim3 grid((unsigned)((total + 3) / 4)), block(256);
-    hipLaunchKernelGGL(temporal_attention_kernel, grid, block, 0, moca_stream(stream),
+    hipLaunchKernelGGL(causal ? temporal_attention_kernel<true> : temporal_attention_kernel<false>, grid, block, 0, moca_stream(stream),
                        reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
                        reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
                        B, T, HW, heads, ld_qkv, ldo, scale * 1.4426950408889634f);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
+}
+
+extern "C" int moca_temporal_attention_f16(const void* q, const void* k, const void* v, void* out,
+                                           int32_t B, int32_t T, int32_t HW, int32_t heads,
+                                           int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
+    return launch_temporal_attention(false, q, k, v, out, B, T, HW, heads, ld_qkv, ldo, scale, stream);
+}
+
+extern "C" int moca_temporal_attention_causal_f16(const void* q, const void* k, const void* v, void* out,
+                                                  int32_t B, int32_t T, int32_t HW, int32_t heads,
+                                                  int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
+    if (!(scale > 0.f)) return MOCA_E_BADARG;          // (the mask is applied before the scale: -inf must stay -inf)
+    return launch_temporal_attention(true, q, k, v, out, B, T, HW, heads, ld_qkv, ldo, scale, stream);
 }

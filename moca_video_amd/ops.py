@@ -197,9 +197,10 @@ def _gemm_params(a, pw: PackedWeight, out, *, M, lda=None, mode=_l.MOCA_A_LINEAR
     if rowsum is not None:                   # f32 [N / cols][M][2] (cols = gemm_rowsum_cols), or True when only probing
         p.flags |= _l.MOCA_EP_ROWSUM
         p.rowsum = rowsum.data_ptr() if torch.is_tensor(rowsum) else None
-    if tattn is not None:                    # (T, HW, softmax scale): projection + temporal attention in one launch (MOCA_EP_TATTN)
+    if tattn is not None:                    # (T, HW, softmax scale[, causal]): projection + temporal attention in one launch (MOCA_EP_TATTN)
         p.flags |= _l.MOCA_EP_TATTN
-        p.T, p.HW, p.tattn_scale = tattn
+        p.T, p.HW, p.tattn_scale = tattn[:3]
+        p.tattn_causal = 1 if len(tattn) > 3 and tattn[3] else 0
     if gstat is not None:                    # (i64 [M / rows][32][2] fixed-point accumulators, zeroed before the launch; rows per statistics group
         p.flags |= _l.MOCA_EP_GSTAT         #  [, columns per channel group, channel of column 0]: one source of a virtual concat)
         p.gstat = gstat[0].data_ptr()
@@ -386,6 +387,13 @@ def attention_ip(q, k, v, k_ip, v_ip, out, *, Bq, heads, Nq, Nt, Ni, ldq, ldk, l
 def temporal_attention(q, k, v, out, *, B, T, HW, heads, ld_qkv, ldo, scale):
     _l.check(_l.load().moca_temporal_attention_f16(_l.ptr(q), _l.ptr(k), _l.ptr(v), _l.ptr(out), B, T, HW, heads,
                                                    ld_qkv, ldo, scale, _st()), "moca_temporal_attention_f16")
+    return out
+
+
+def temporal_attention_causal(q, k, v, out, *, B, T, HW, heads, ld_qkv, ldo, scale):
+    """temporal_attention with the causal mask of TemporalTransformer(causal_attention=True): frame t attends to frames <= t"""
+    _l.check(_l.load().moca_temporal_attention_causal_f16(_l.ptr(q), _l.ptr(k), _l.ptr(v), _l.ptr(out), B, T, HW, heads,
+                                                          ld_qkv, ldo, scale, _st()), "moca_temporal_attention_causal_f16")
     return out
 
 

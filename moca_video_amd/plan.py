@@ -87,7 +87,8 @@ class _PlanBase:
         self.device = device
         self.P = model._packed
         self.pool = _Pool(device)
-        self.stream = torch.cuda.Stream(device=device)
+        # (a plan recorded on a host device -- the CPU tests read its launch list -- is never launched and has no stream)
+        self.stream = torch.cuda.Stream(device=device) if torch.device(device).type == "cuda" else None
         self.steps = []
         self._pinned = set()
         self.graph = None
@@ -389,7 +390,9 @@ class _Plan(_PlanBase):
         """shared_x: the B videos are `len(L)` context variants of the SAME B / len(L) latents (the two `apply_model` calls of
         classifier-free guidance, ddim.py:298-299,366-369, on one x): `x_in` holds the distinct latents only, everything up to the
         first cross-attention (conv_in, init_attn, the first ResBlock, the first SpatialTransformer's self-attention and to_q:
-        8 % of the forward) is computed once and repeated where the contexts first enter (`_expand`).
+        8 % of the forward) is computed once and repeated where the contexts first enter (`_expand`).  With
+        temporal_selfatt_only=False the temporal attn2 is a cross-attention too: the first one of EITHER kind ends the prefix -- with
+        addition_attention that is init_attn's attn2, right behind conv_in.
         pieces: channel counts of the c_concat tensors of a `hybrid*` call (UNetModel.forward_concat): `x_in` holds the remaining
         (latent) channels only, the first conv reads the persistent rows `x_rows` whose columns the sources are scattered into --
         x_in's by a recorded launch, the c_concat ones by `set_concat` (outside the recorded sequence: they change per call on the
@@ -532,19 +535,21 @@ class _Plan(_PlanBase):
             self.P[k] = build()
         return self.P[k]
 
-    def _attn_temporal_fused(self, att, l, M, Cn, heads, HW, norm):
+    def _attn_temporal_fused(self, att, l, M, Cn, heads, HW, norm, causal=False):
         """q|k|v projection + attention over the frame axis in ONE launch (MOCA_EP_TATTN) where its 320-row tiles (16 frames x 20
         pixels, one head) come in whole rounds of the chip; None -> the caller runs projection + temporal_attention.
         Used wherever the kernel applies (round-2 same-device A/B of the whole CFG step: never 37.2 ms, only where the tile count is a
         multiple of 256 or >= 1024 36.4, everywhere 36.0 -- the launch and the q|k|v round trip it removes outweigh the partial last
-        round of tiles at the 640- and 1280-channel levels)."""
+        round of tiles at the 640- and 1280-channel levels).
+        causal: the mask of TemporalTransformer(causal_attention=True) in the epilogue's softmax (moca_gemm_params.tattn_causal), so a
+        causal model keeps the fused form wherever the non-causal one has it."""
         if self.T != 16 or HW % 20:
             return None
         folded = isinstance(l, _LNRef)
         x = l.x if folded else l
         pw = self._tattn_pw(att, norm, heads, folded)
         scale = att.dim_head ** -0.5
-        kw = dict(M=M, lda=x.stride(-2), splits=1, tattn=(self.T, HW, scale))
+        kw = dict(M=M, lda=x.stride(-2), splits=1, tattn=(self.T, HW, scale, True) if causal else (self.T, HW, scale))
         if not ops.gemm_tattn_ok(x, pw, lnfold=(None, l.nparts, 1e-5) if folded else None, **kw):
             return None
         o = self.pool.get(M, Cn)
@@ -552,10 +557,11 @@ class _Plan(_PlanBase):
         self._emit(ops.gemm, x, pw, o, lnfold=(l.part, l.nparts, 1e-5) if folded else None, **kw)
         return o
 
-    def _attn_self(self, att, l, M, Cn, heads, spatial, F, HW, norm=None):
+    def _attn_self(self, att, l, M, Cn, heads, spatial, F, HW, norm=None, causal=False):
         P = self.P
+        assert not (spatial and causal)
         if not spatial:
-            o = self._attn_temporal_fused(att, l, M, Cn, heads, HW, norm)
+            o = self._attn_temporal_fused(att, l, M, Cn, heads, HW, norm, causal)
             if o is not None:
                 return o
         qkv = self.linear_of_ln(l, M, P[id(att)], lambda: self._fold_pw("qkv", att, norm))   # [M][3C] fused to_q|to_k|to_v
@@ -566,8 +572,8 @@ class _Plan(_PlanBase):
             self._emit(ops.attention, q, k, v, o, Bq=F, heads=heads, Nq=HW, Nk=HW, ldq=3 * Cn, ldk=3 * Cn, ldv=3 * Cn,
                        ldo=Cn, kv_div=1, scale=scale)
         else:
-            self._emit(ops.temporal_attention, q, k, v, o, B=M // (self.T * HW), T=self.T, HW=HW, heads=heads, ld_qkv=3 * Cn, ldo=Cn,
-                       scale=scale)
+            self._emit(ops.temporal_attention_causal if causal else ops.temporal_attention, q, k, v, o, B=M // (self.T * HW), T=self.T,
+                       HW=HW, heads=heads, ld_qkv=3 * Cn, ldo=Cn, scale=scale)
         self._release(qkv)
         return o
 
@@ -648,17 +654,21 @@ class _Plan(_PlanBase):
         out = self._gemm(a, pw, M, lda=lda, residual=residual, **wk)
         return out, self.ln(out, M, pw.N, gb)
 
-    def tblock(self, blk, h, l, M, Cn, heads, spatial, F, HW, next_gb=None, next_consumer=None):
+    def tblock(self, blk, h, l, M, Cn, heads, spatial, F, HW, next_gb=None, next_consumer=None, causal=False):
         """BasicTransformerBlock._forward, attention.py:216-220.  `l` = norm1(h), already computed by the producer of h;
         returns (h_out, norm1 of the NEXT block applied to it or None, rows, frames) -- rows / frames grow by `reps` when this
-        block holds the first cross-attention of a shared-latents plan."""
+        block holds the first cross-attention of a shared-latents plan (a spatial attn2, or the attn2 of a temporal block with
+        only_self_att=False: its rows are (frame, pixel) queries of their video's tokens exactly as the spatial ones).
+        causal: `mask` of :217-218 -- it reaches attn1 AND attn2, both self-attentions over the frames (the cross branch of
+        TemporalTransformer.forward passes none, :362-363)."""
         P = self.P
         geglu = blk.ff.net[0].proj
         consumers = (self._ln_consumer(blk.attn2, blk.norm2), lambda: self._fold_pw("geglu", geglu, blk.norm3))
         for (att, cur, nxt), cons in zip(((blk.attn1, blk.norm1, blk.norm2), (blk.attn2, blk.norm2, blk.norm3)), consumers):
             if att.is_self:
-                o = self._attn_self(att, l, M, Cn, heads, spatial, F, HW, norm=cur)
+                o = self._attn_self(att, l, M, Cn, heads, spatial, F, HW, norm=cur, causal=causal)
             else:
+                assert not causal
                 expand = self.reps > 1 and F == self.Bx * self.T      # first use of the contexts: the shared prefix ends here
                 o = self._attn_cross(att, l, M, Cn, heads, F, HW, norm=cur, expand=expand)
                 if expand:
@@ -725,6 +735,19 @@ class _Plan(_PlanBase):
         """SpatialTransformer.forward attention.py:262-278 / TemporalTransformer.forward :331-373"""
         P = self.P
         blocks = list(mod.transformer_blocks)
+        causal = False
+        if not spatial:
+            causal = mod.causal
+            if causal and self.T != mod.temporal_length:
+                # the reference's mask is tril(ones(1, temporal_length, temporal_length)) (attention.py:311): it broadcasts against
+                # the [.., T, T] scores only when the two agree
+                raise ValueError(f"causal temporal attention: x has T = {self.T} frames, the model was built with temporal_length = "
+                                 f"{mod.temporal_length} (the reference's mask broadcasts only when they are equal)")
+            if not mod.only_self_att and (x.H * x.W) % self.T:
+                # attention.py:359-361 repeats the context over the pixels as (t r), r = hw // t: with hw % t != 0 it has fewer rows than
+                # the hw queries and the reference fails.  (With one context per video the mapping itself never matters.)
+                raise ValueError(f"temporal cross-attention (temporal_selfatt_only=False): a {x.H} x {x.W} map has hw = {x.H * x.W} "
+                                 f"pixels, not a multiple of T = {self.T}; the reference's context repeat (t r), r = hw // t, fails there")
         fold = self._gn_fold(x, P[id(mod.norm)], P[id(mod.proj_in)], fps=1 if spatial else self.T, eps=1e-6)
         if fold is not None:
             # `x = self.norm(x)` (attention.py:262-268 / :333-341) lives in proj_in's per-statistics-group weights: no GroupNorm launch,
@@ -743,7 +766,8 @@ class _Plan(_PlanBase):
             last = i + 1 >= len(blocks)
             nxt = None if last else P[id(blocks[i + 1].norm1)]
             ncons = None if last else self._ln_consumer(blocks[i + 1].attn1, blocks[i + 1].norm1)
-            h, l, M, Fr = self.tblock(blk, h, l, M, mod.inner, mod.heads, spatial, Fr, x.H * x.W, next_gb=nxt, next_consumer=ncons)
+            h, l, M, Fr = self.tblock(blk, h, l, M, mod.inner, mod.heads, spatial, Fr, x.H * x.W, next_gb=nxt, next_consumer=ncons,
+                                      causal=causal)
         if Fr != x.F:                                            # the shared prefix ended inside: the outer residual too
             xres = self._expand(x.buf, x.M, x.C)
         out, cs = self.linear(h, M, P[id(mod.proj_out)], residual=xres, want_colsum=True)

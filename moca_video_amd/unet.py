@@ -138,16 +138,30 @@ class _SpatialTransformer(nn.Module):
 
 
 class _TemporalTransformer(nn.Module):
-    """attention.py:288-329 (only_self_att=True)"""
+    """attention.py:288-329.  only_self_att=False: attn2 of every block attends to the text context (to_k / to_v are
+    [inner, context_dim], :313-314,353-363); causal_attention: frame t attends to frames <= t in attn1 AND attn2 of a
+    self-attention-only block (:309-311,342-351 -> :217-218); the cross branch passes no mask (:362-363), so there the flag
+    only keeps its constructor assert.  The reference's `mask` is a plain attribute, not a buffer: no state-dict key."""
 
-    def __init__(self, ch, n_heads, d_head, depth, use_linear):
+    def __init__(self, ch, n_heads, d_head, depth, use_linear, context_dim=None, only_self_att=True, causal_attention=False,
+                 temporal_length=None):
         super().__init__()
         inner = n_heads * d_head
         self.ch, self.inner, self.heads = ch, inner, n_heads
+        self.only_self_att, self.causal_attention, self.temporal_length = only_self_att, causal_attention, temporal_length
+        if causal_attention:
+            assert temporal_length is not None              # attention.py:310
+        if only_self_att:
+            context_dim = None                              # attention.py:313-314
         self.norm = _Param((ch,), kind="norm")
         self.proj_in = _Param((inner, ch) if use_linear else (inner, ch, 1))
-        self.transformer_blocks = nn.ModuleList([_BasicTransformerBlock(inner, n_heads, d_head, None) for _ in range(depth)])
+        self.transformer_blocks = nn.ModuleList([_BasicTransformerBlock(inner, n_heads, d_head, context_dim) for _ in range(depth)])
         self.proj_out = _Param((ch, inner) if use_linear else (ch, inner, 1))
+
+    @property
+    def causal(self):
+        """the mask reaches the attentions: only on the self-attention-only path (attention.py:348-351 against :353-363)"""
+        return self.causal_attention and self.only_self_att
 
 
 class _Downsample(nn.Module):
@@ -228,9 +242,9 @@ class _CatMap:
 def pack_tree(root, dev):
     """Pack every block under `root` (a whole UNetModel, or a holder of ONE block: blockplan.BlockRunner) into GEMM operands.
     Returns (P, emb_cols, kv_cols): P maps id(parameter module) -> packed operands; all ResBlock.emb_layers Linears share
-    the input SiLU(emb) and all cross-attention to_k/to_v share the text context, so each family is fused into ONE wide GEMM
-    per forward (P["emb_all"], P["ctx_kv_all"]; column offsets are multiples of 64) with the per-module column ranges in
-    emb_cols / kv_cols."""
+    the input SiLU(emb) and all cross-attention to_k/to_v (every spatial attn2, and the temporal attn2 of a model with
+    temporal_selfatt_only=False) share the text context, so each family is fused into ONE wide GEMM per forward (P["emb_all"],
+    P["ctx_kv_all"]; column offsets are multiples of 64) with the per-module column ranges in emb_cols / kv_cols."""
     P = {}
     f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
 
@@ -367,8 +381,9 @@ class UNetModel(nn.Module):
         if resblock_updown: unsupported.append("resblock_updown")
         if tempspatial_aware: unsupported.append("tempspatial_aware")
         if use_relative_position: unsupported.append("use_relative_position")
-        if use_causal_attention: unsupported.append("use_causal_attention")
-        if not temporal_selfatt_only: unsupported.append("temporal_selfatt_only=False")
+        if use_image_attention and not temporal_selfatt_only and temporal_attention:
+            # (the temporal attn2 has no to_k_ip / to_v_ip: it would project the image rows of the context with to_k / to_v)
+            unsupported.append("use_image_attention with temporal_selfatt_only=False")
         if not conv_resample: unsupported.append("conv_resample=False")
         if num_head_channels != 64: unsupported.append("num_head_channels != 64 (kernels are head-dim 64)")
         if model_channels % 32 or model_channels % 64: unsupported.append("model_channels % 64 != 0")
@@ -389,7 +404,11 @@ class UNetModel(nn.Module):
         self.context_dim = context_dim
         self.use_image_attention = use_image_attention
         self.temporal_length = temporal_length
+        self.temporal_selfatt_only, self.use_causal_attention = temporal_selfatt_only, use_causal_attention
         time_embed_dim = model_channels * 4
+        # openaimodel3d.py:379-389,415-425,460-470,503-513: every TemporalTransformer gets the same four arguments
+        tkw = dict(context_dim=context_dim, only_self_att=temporal_selfatt_only, causal_attention=use_causal_attention,
+                   temporal_length=temporal_length)
 
         self.time_embed = _seq(_Param((time_embed_dim, model_channels)), nn.Identity(), _Param((time_embed_dim, time_embed_dim)))
         if fps_cond:
@@ -397,14 +416,14 @@ class UNetModel(nn.Module):
 
         self.input_blocks = nn.ModuleList([_seq(_Param((model_channels, in_channels, 3, 3), kind="conv"))])
         if addition_attention:
-            self.init_attn = _seq(_TemporalTransformer(model_channels, 8, num_head_channels, transformer_depth, use_linear=False))
+            self.init_attn = _seq(_TemporalTransformer(model_channels, 8, num_head_channels, transformer_depth, use_linear=False, **tkw))
 
         def attn_layers(ch):
             heads = ch // num_head_channels
             layers = [_SpatialTransformer(ch, heads, num_head_channels, transformer_depth, context_dim, use_linear,
                                           img_cross_attention=use_image_attention)]
             if temporal_attention:
-                layers.append(_TemporalTransformer(ch, heads, num_head_channels, temporal_transformer_depth, use_linear))
+                layers.append(_TemporalTransformer(ch, heads, num_head_channels, temporal_transformer_depth, use_linear, **tkw))
             return layers
 
         input_block_chans = [model_channels]
@@ -425,7 +444,7 @@ class UNetModel(nn.Module):
                _SpatialTransformer(ch, ch // num_head_channels, num_head_channels, transformer_depth, context_dim, use_linear,
                                    img_cross_attention=use_image_attention)]
         if temporal_attention:
-            mid.append(_TemporalTransformer(ch, ch // num_head_channels, num_head_channels, temporal_transformer_depth, use_linear))
+            mid.append(_TemporalTransformer(ch, ch // num_head_channels, num_head_channels, temporal_transformer_depth, use_linear, **tkw))
         mid.append(_ResBlock(ch, time_embed_dim, ch, temporal_conv))
         self.middle_block = _seq(*mid)
 
@@ -467,10 +486,12 @@ class UNetModel(nn.Module):
         self._invalidate()
         return out
 
-    def _pack(self):
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("moca_video_amd.UNetModel runs on an MI355X only; call .cuda() first (no CPU path)")
+    def _pack(self, dev=None):
+        """dev: only to RECORD a plan on the host (the CPU tests read its launch list; nothing is launched there)"""
+        if dev is None:
+            dev = next(self.parameters()).device
+            if dev.type != "cuda":
+                raise RuntimeError("moca_video_amd.UNetModel runs on an MI355X only; call .cuda() first (no CPU path)")
         P, self._emb_cols, self._kv_cols = pack_tree(self, dev)
         f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
         for sq in (self.time_embed,) + ((self.fps_embedding,) if self.fps_cond else ()):

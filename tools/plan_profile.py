@@ -19,7 +19,9 @@ PP_MODE
 Columns: total / count / each [us], TF/s (executed FLOPs), GB/s (operand bytes touched once: A, W, output, residual), then the
 roofline floor of the step = max(FLOP / 1.7 PFLOP/s, bytes / 5.5 TB/s) -- 1.7 PFLOP/s is what the matrix pipe sustains on random
 fp16 data on this chip (tools/micro/mfma_peak.hip), 5.5 TB/s a streaming kernel's HBM rate -- and the slack each - floor.
-A JSON copy (PP_JSON=path) carries the per-key numbers for tools/ingraph_vs_hot.py."""
+A JSON copy (PP_JSON=path) carries the per-key numbers for tools/ingraph_vs_hot.py.
+PP_CAUSAL=1: the same model and weights with use_causal_attention (every TemporalTransformer flagged before the plan is built): the
+fused q|k|v launches then carry the mask and print as "+tattn causal" -- same operands as the plain run's "+tattn" lines."""
 import collections
 import json
 import os
@@ -39,6 +41,11 @@ dev = torch.device("cuda", 0)
 torch.cuda.set_device(dev)
 dm = bench.build_model(dev, seed=321)
 unet = dm.model.diffusion_model
+if os.environ.get("PP_CAUSAL", "0") == "1":
+    from moca_video_amd.unet import _TemporalTransformer
+    for mod in unet.modules():
+        if isinstance(mod, _TemporalTransformer):
+            mod.causal_attention, mod.temporal_length = True, 16
 g = torch.Generator(device=dev).manual_seed(1)
 SHARED = os.environ.get("PP_SHARED", "1") != "0" and B % 2 == 0
 n = B // 2 if SHARED else B
@@ -69,7 +76,7 @@ def describe(s):
               (f" splits={kw['splits']}" if kw.get("splits", 1) > 1 else "") + (" f32" if kw.get("out_f32") else "") + \
               (" +colsum" if kw.get("colsum") is not None else "") + (" +LN" if kw.get("ln") is not None else "") + \
               (" +rowsum" if kw.get("rowsum") is not None else "") + (" lnfold" if kw.get("lnfold") is not None else "") + \
-              (" +gstat" if kw.get("gstat") is not None else "") + (" +tattn" if kw.get("tattn") is not None else "") + \
+              (" +gstat" if kw.get("gstat") is not None else "") + (" +tattn" if kw.get("tattn") is not None else "") + (" causal" if len(kw.get("tattn") or ()) > 3 else "") + \
               (f" up{kw['up_phase']}" if kw.get("up_phase") else "") + (" cat2" if kw.get("a2") is not None else "") + \
               (" slabs" if kw.get("slabs") else "")
         M = kw["M"]

@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Record the two "as at another commit" fixtures of tests/test_temporal_variants_{cpu,gpu}.py from a CHECKOUT of that commit (its tree
+with its own built libmoca_hip.so), so that they can be audited and re-recorded when a plan optimisation or a compiler bump
+legitimately changes them:
+
+  tests/golden/plan_full_launches.npz            (--plans, no GPU)  the launch list of the FULL configuration at [.,4,16,40,64]: the plain
+                                                 B = 1 forward and the shared-prefix CFG pair, one line per launch
+                                                 (tests/plan_cpu.py::signature)
+  tests/golden/temporal_attention_parent_sha.npz (--sha, on the GPU)  sha256 of the outputs of moca_temporal_attention_f16 and of the
+                                                 non-causal MOCA_EP_TATTN launch on the host-generated operands of
+                                                 tests/temporal_variants_ref.py
+
+    git worktree add ../base <commit> && make -C ../base/moca_video_amd/csrc
+    python tools/record_parent_fixtures.py --tree ../base --plans          (any host)
+    python tools/record_parent_fixtures.py --tree ../base --sha            (on the MI355X)
+
+The package is imported from --tree, the helpers (tests/plan_cpu.py, tests/temporal_variants_ref.py) and the output directory are this
+checkout's.  A tree older than the host-recordable plan (no `UNetModel._pack(dev)`, a stream created unconditionally) is recorded
+through two stand-ins defined here; nothing of it is modified."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(HERE, "tests", "golden")
+
+
+def record_plans():
+    import inspect
+    from moca_video_amd import UNetModel, ops
+    import moca_video_amd.unet as U
+    if "dev" not in inspect.signature(UNetModel._pack).parameters:          # a tree from before the host-recordable plan
+        class _NoStream:
+            def __init__(self, *a, **k):
+                pass
+        torch.cuda.Stream = _NoStream
+
+        def _pack(self, dev=None):
+            P, self._emb_cols, self._kv_cols = U.pack_tree(self, dev)
+            f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+            for sq in (self.time_embed,) + ((self.fps_embedding,) if self.fps_cond else ()):
+                for m in (sq[0], sq[2]):
+                    P[id(m)] = ops.pack_linear(m.weight.detach(), m.bias.detach(), device=dev)
+            cin = self.input_blocks[0][0]
+            P[id(cin)] = ops.pack_conv3x3(cin.weight.detach(), cin.bias.detach(), cpad=self.in_cpad, device=dev)
+            P[id(self.out[0])] = (f32(self.out[0].weight), f32(self.out[0].bias))
+            P[id(self.out[2])] = ops.pack_conv3x3(self.out[2].weight.detach(), self.out[2].bias.detach(), device=dev)
+            self._packed = P
+        UNetModel._pack = _pack
+    from helpers import FULL
+    from moca_video_amd.plan import _Plan
+    import plan_cpu
+    m = UNetModel(**FULL)
+    m._pack(torch.device("cpu"))
+    out = {}
+    for tag, args, kw in (("b1_77", (1, 16, 40, 64, 77), {}), ("cfg_shared", (2, 16, 40, 64, ((1, 77), (1, 77))), dict(shared_x=True))):
+        sig = plan_cpu.signature(_Plan(m, *args, torch.float32, torch.device("cpu"), **kw))
+        print(f"{tag}: {len(sig)} launches")
+        out[tag] = np.asarray(sig)
+    np.savez_compressed(os.path.join(GOLD, "plan_full_launches.npz"), **out)
+
+
+def record_sha():
+    from moca_video_amd import ops
+    import temporal_variants_ref as R
+    names, shas = [], []
+    for B, T, HW, heads in R.STANDALONE:
+        C = heads * 64
+        qkv = R.standalone_operands(B, T, HW, heads)
+        out = torch.zeros(B * T * HW, C, dtype=torch.float16, device="cuda")
+        ops.temporal_attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], out, B=B, T=T, HW=HW, heads=heads, ld_qkv=3 * C, ldo=C,
+                               scale=R.SCALE)
+        torch.cuda.synchronize()
+        names.append(f"standalone.{B}.{T}.{HW}.{heads}")
+        shas.append(R.sha(out))
+    for B, HW, heads, K, fold in R.FUSED:
+        x, ws, gb = R.fused_operands(B, HW, heads, K, fold)
+        out = R.fused_run(ops, x, ws, gb, B, HW, heads, False)
+        torch.cuda.synchronize()
+        names.append(f"fused.{B}.{HW}.{heads}.{K}.{int(fold)}")
+        shas.append(R.sha(out))
+    for n, s in zip(names, shas):
+        print(n, s)
+    np.savez_compressed(os.path.join(GOLD, "temporal_attention_parent_sha.npz"), names=np.asarray(names), sha256=np.asarray(shas))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tree", required=True, help="checkout (with its built library) to record from")
+    ap.add_argument("--plans", action="store_true")
+    ap.add_argument("--sha", action="store_true")
+    a = ap.parse_args()
+    tree = os.path.abspath(a.tree)
+    sys.path.insert(0, tree)
+    sys.path.insert(1, os.path.join(HERE, "tests"))
+    import moca_video_amd
+    assert os.path.abspath(moca_video_amd.__file__).startswith(tree + os.sep), f"moca_video_amd came from {moca_video_amd.__file__}"
+    if a.plans:
+        record_plans()
+    if a.sha:
+        record_sha()
+
+
+if __name__ == "__main__":
+    main()
