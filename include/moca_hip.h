@@ -320,6 +320,13 @@ int moca_ncthw_to_nhwc_f16(const void* x, int32_t x_is_f32, void* y, int32_t B, 
  * 16-byte aligned. */
 int moca_ncthw_scatter_f16(const void* x, int32_t x_is_f32, void* y, int32_t B, int32_t k, int32_t T,
                            int32_t HW, int32_t Cpad, int32_t c0, void* stream);
+/* `h = h + features_adapter[adapter_idx]` (openaimodel3d.py:562-564) in place on the channels-last rows:
+ * rows[(f*HW + p)*ld + c] = fp16(float(rows[...]) + float(src[((f % Fsrc)*C + c)*HW + p])), f < F, p < HW, c < C.  src is the NCHW
+ * map [Fsrc][C][H][W] (f32 or f16) as the caller holds it; Fsrc divides F (the branches of a shared-prefix batch read the same
+ * frames).  ld >= C: the map may be a column view of wider rows, the columns outside [0, C) keep what they hold.  C % 8 == 0,
+ * ld % 8 == 0, rows 16-byte aligned (8-channel accesses), src aligned to its element. */
+int moca_nchw_add_rows_f16(void* rows, const void* src, int32_t src_is_f32, int32_t F, int32_t Fsrc, int32_t C,
+                           int32_t HW, int32_t ld, void* stream);
 /* channels-last fp16 [B*T][H*W][ld] (first Cout columns) -> [B][Cout][T][H][W] f32/f16
  * (openaimodel3d.py:573-577) */
 int moca_nhwc_to_ncthw(const void* y, int32_t ld, void* x, int32_t x_is_f32, int32_t B,

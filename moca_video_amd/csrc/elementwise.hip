@@ -49,6 +49,48 @@ __global__ __launch_bounds__(256) void ncthw_scatter_kernel(const TIN* __restric
     }
 }
 
+// rows[(f*HW + p)*ld + c] += src[((f % Fsrc)*C + c)*HW + p]: `h = h + features_adapter[adapter_idx]` (openaimodel3d.py:562-564) on the
+// channels-last rows, the NCHW map read where the caller left it.  One block = 64 channels x 32 pixels of one frame, transposed through
+// LDS so that both sides are coalesced: the source is read along p (32 consecutive elements per channel), the rows are read and written
+// along c (16 bytes = 8 channels per lane).  The tile is fp32 [64][33].  The layout is DERIVED from the documented bank rule for 4-byte
+// LDS accesses (bank = dword address % 32, conflicts counted per 32-lane half), not measured -- no LDS-conflict counter run backs it:
+// with stride 33 bank = (c + p) % 32, so the write pass (lane = p, one channel per half) touches 32 different banks per half, and so
+// does the read pass once the lanes of a half that hold channels 32..63 are rotated by four pixels (without the rotation chunk k and
+// chunk k + 4 of one pixel would share banks).  A partial pixel tile leaves lanes idle: at HW = 40 (the 5 x 8 level) the second tile
+// uses 8 of its 32 pixel columns, so 40 of 64 columns of that level's launch do work -- the smallest of the four launches.  The sum is
+// float(rows) + float(src) rounded once to fp16.
+constexpr int ADD_TC = 64, ADD_TP = 32;
+template <typename TIN>
+__global__ __launch_bounds__(256) void nchw_add_rows_kernel(half_t* __restrict__ rows, const TIN* __restrict__ src, int Fsrc, int C,
+                                                            int HW, int ld, int ptiles, int ctiles) {
+    __shared__ float tile[ADD_TC][ADD_TP + 1];
+    int64_t b = blockIdx.x;
+    const int pt = (int)(b % ptiles); b /= ptiles;
+    const int ct = (int)(b % ctiles);
+    const int f = (int)(b / ctiles);
+    const int c0 = ct * ADD_TC, p0 = pt * ADD_TP;
+    const TIN* s = src + ((int64_t)(f % Fsrc) * C + c0) * HW + p0;
+    {
+        const int p = threadIdx.x & 31, cb = threadIdx.x >> 5;
+#pragma unroll
+        for (int i = 0; i < ADD_TC / 8; ++i) {
+            const int c = cb + 8 * i;
+            if (c0 + c < C && p0 + p < HW) tile[c][p] = (float)s[(int64_t)c * HW + p];
+        }
+    }
+    __syncthreads();
+    const int ch = threadIdx.x & 7;                               // 8-channel chunk of the tile
+    const int p = ((threadIdx.x >> 3) + 4 * (ch >> 2)) & 31;
+    const int c = ch * 8;
+    if (c0 + c < C && p0 + p < HW) {                              // (C % 8 == 0: a chunk is inside the map or outside it)
+        half_t* r = rows + ((int64_t)f * HW + p0 + p) * ld + c0 + c;
+        half8v v = *reinterpret_cast<const half8v*>(r);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = (half_t)((float)v[q] + tile[c + q][p]);
+        *reinterpret_cast<half8v*>(r) = v;
+    }
+}
+
 template <typename TOUT>
 __global__ __launch_bounds__(256) void nhwc_to_ncthw_kernel(const half_t* __restrict__ y, int ld, TOUT* __restrict__ x,
                                                             int B, int Cout, int T, int HW) {
@@ -216,6 +258,24 @@ extern "C" int moca_ncthw_scatter_f16(const void* x, int32_t x_is_f32, void* y, 
     else
         hipLaunchKernelGGL(ncthw_scatter_kernel<half_t>, dim3(g), dim3(256), 0, moca_stream(stream),
                            reinterpret_cast<const half_t*>(x), reinterpret_cast<half_t*>(y), B, k, T, HW, Cpad, c0);
+    MOCA_CHECK_LAUNCH();
+    return MOCA_OK;
+}
+
+extern "C" int moca_nchw_add_rows_f16(void* rows, const void* src, int32_t src_is_f32, int32_t F, int32_t Fsrc, int32_t C, int32_t HW,
+                                      int32_t ld, void* stream) {
+    if (!rows || !src || F <= 0 || C <= 0 || HW <= 0 || Fsrc <= 0 || F % Fsrc || ld < C) return MOCA_E_BADARG;
+    // 16-byte accesses on the rows (8 channels), element accesses on the source
+    if (C % 8 || ld % 8 || ((uintptr_t)rows & 15) || ((uintptr_t)src & (src_is_f32 ? 3 : 1))) return MOCA_E_BADARG;
+    const int ptiles = (HW + ADD_TP - 1) / ADD_TP, ctiles = (C + ADD_TC - 1) / ADD_TC;
+    const int64_t blocks = (int64_t)F * ptiles * ctiles;
+    if (blocks > 0x7fffffff) return MOCA_E_BADARG;
+    if (src_is_f32)
+        hipLaunchKernelGGL(nchw_add_rows_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, moca_stream(stream),
+                           reinterpret_cast<half_t*>(rows), reinterpret_cast<const float*>(src), Fsrc, C, HW, ld, ptiles, ctiles);
+    else
+        hipLaunchKernelGGL(nchw_add_rows_kernel<half_t>, dim3((unsigned)blocks), dim3(256), 0, moca_stream(stream),
+                           reinterpret_cast<half_t*>(rows), reinterpret_cast<const half_t*>(src), Fsrc, C, HW, ld, ptiles, ctiles);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }

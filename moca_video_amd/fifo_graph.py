@@ -357,8 +357,10 @@ class BaseEngine:
     buffer, the schedule in device tables indexed by the state block's iteration counter; the host only replays."""
 
     @staticmethod
-    def supported(model, x, cond, uc, scale):
+    def supported(model, x, cond, uc, scale, features_adapter=None):
         unet = getattr(getattr(model, "model", None), "diffusion_model", None)
+        if features_adapter is not None and getattr(getattr(model, "model", None), "conditioning_key", None) != "crossattn":
+            return False                                     # (the host-issued path's wrapper names the refusal)
         ok = isinstance(unet, UNetModel) and x.is_cuda and isinstance(cond, dict) and isinstance(uc, dict) and scale != 1.0
         if not ok or set(cond.keys()) != set(uc.keys()) or 2 * x.shape[0] > 64:
             return False
@@ -380,7 +382,7 @@ class BaseEngine:
         return set(cond.keys()) <= {"c_crossattn", "fps"} and key == "crossattn" and \
             same_fps([cond.get("fps", 16), uc.get("fps", 16)])      # (the shared prefix adds ONE fps embedding)
 
-    def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, keep_pred_x0=False):
+    def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, keep_pred_x0=False, features_adapter=None):
         self.unet = unet = model.model.diffusion_model
         dev = x.device
         self.device = dev
@@ -397,7 +399,11 @@ class BaseEngine:
         self.hybrid = getattr(model.model, "conditioning_key", None) != "crossattn"
         concat = cond.get("c_concat") if self.hybrid else None
         pieces = None if concat is None else tuple(int(c.shape[1]) for c in concat)
-        self.plan = plan = _Plan(unet, 2 * B, T, H, W, segs, torch.float32, dev, shared_x=True, pieces=pieces)
+        # features_adapter: constant over a trajectory like c_concat -- reset() writes the plan's adapter buffers, the recorded step
+        # reads them; the list length fails as in UNetModel.forward
+        unet._check_adapter(features_adapter)
+        self.plan = plan = _Plan(unet, 2 * B, T, H, W, segs, torch.float32, dev, shared_x=True, pieces=pieces,
+                                 adapter=None if features_adapter is None else unet.adapter_sites)
 
         def fps_rows(fp):
             if isinstance(fp, int):
@@ -419,7 +425,7 @@ class BaseEngine:
         self.noise = torch.zeros(n, dtype=torch.float32, device=dev)
         self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev) if keep_pred_x0 else None
         self._fps_rows = fps_rows
-        self.reset(x, cond, uc, seed)
+        self.reset(x, cond, uc, seed, features_adapter=features_adapter)
         lib = _l.load()
         eps = plan.out.reshape(2 * B, -1)
         st_ = _l.ptr(self.state)
@@ -434,9 +440,11 @@ class BaseEngine:
                                                  _l.ptr(self.coef), S, float(cfg_scale), 1 if use_scale else 0, n, S_()), "moca_base_ddim_step_f32")
         plan.steps = [pre] + plan.steps + [post]
 
-    def reset(self, x, cond, uc, seed=0):
-        """start a new trajectory on the same plan: latents x_T, contexts, fps, iteration 0, a new noise stream"""
+    def reset(self, x, cond, uc, seed=0, features_adapter=None):
+        """start a new trajectory on the same plan: latents x_T, contexts, fps, adapter maps, iteration 0, a new noise stream"""
         plan, dev = self.plan, self.device
+        if (features_adapter is None) != (plan.adapter_in is None):
+            raise ValueError("features_adapter goes with an engine built for it")
         B = self.shape[0]
         fps_c, fps_u = (16, 16) if self.hybrid else (cond.get("fps", 16), uc.get("fps", 16))
         if not same_fps([fps_c, fps_u]):
@@ -450,6 +458,8 @@ class BaseEngine:
             plan.x_in.copy_(x.to(torch.float32))
             plan.fps_rows.copy_(torch.cat([self._fps_rows(fps_c), self._fps_rows(fps_u)]))
             plan.set_context([cc, cu])
+            if features_adapter is not None:
+                plan.set_adapter(list(features_adapter))
             if plan.pieces is not None:
                 ops.set_stream(plan.stream.cuda_stream)
                 try:

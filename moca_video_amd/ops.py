@@ -414,6 +414,18 @@ def ncthw_scatter(x, y, *, B, k, T, HW, Cpad, c0):
     return y
 
 
+def nchw_add_rows(rows, src, *, F, Fsrc, Cn, HW):
+    """rows [F*HW][Cn] fp16 (row stride >= Cn: a column view works) += src [Fsrc][Cn][HW] (fp32 / fp16, contiguous), frame f of the
+    rows reading frame f % Fsrc of the source; one fp32 sum rounded to fp16 (openaimodel3d.py:562-564)"""
+    if src.dtype not in (torch.float32, torch.float16) or not src.is_contiguous() or src.numel() != Fsrc * Cn * HW:
+        raise ValueError("nchw_add_rows: src must be a contiguous fp32 / fp16 tensor of Fsrc * Cn * HW elements")
+    if rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape != (F * HW, Cn) or rows.stride(1) != 1:
+        raise ValueError("nchw_add_rows: rows must be fp16 [F * HW][Cn] with unit column stride")
+    _l.check(_l.load().moca_nchw_add_rows_f16(_l.ptr(rows), _l.ptr(src), 1 if src.dtype == torch.float32 else 0, F, Fsrc, Cn, HW,
+                                              rows.stride(0), _st()), "moca_nchw_add_rows_f16")
+    return rows
+
+
 def nhwc_to_ncthw(y, ld, x, *, B, Cout, T, HW):
     _l.check(_l.load().moca_nhwc_to_ncthw(_l.ptr(y), ld, _l.ptr(x), 1 if x.dtype == torch.float32 else 0, B, Cout, T, HW,
                                           _st()), "moca_nhwc_to_ncthw")

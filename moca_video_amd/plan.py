@@ -386,7 +386,7 @@ class _PlanBase:
 class _Plan(_PlanBase):
     _defer_slabs = True
 
-    def __init__(self, model, B, T, H, W, L, in_dtype, device, shared_x=False, pieces=None):
+    def __init__(self, model, B, T, H, W, L, in_dtype, device, shared_x=False, pieces=None, adapter=None):
         """shared_x: the B videos are `len(L)` context variants of the SAME B / len(L) latents (the two `apply_model` calls of
         classifier-free guidance, ddim.py:298-299,366-369, on one x): `x_in` holds the distinct latents only, everything up to the
         first cross-attention (conv_in, init_attn, the first ResBlock, the first SpatialTransformer's self-attention and to_q:
@@ -396,7 +396,10 @@ class _Plan(_PlanBase):
         pieces: channel counts of the c_concat tensors of a `hybrid*` call (UNetModel.forward_concat): `x_in` holds the remaining
         (latent) channels only, the first conv reads the persistent rows `x_rows` whose columns the sources are scattered into --
         x_in's by a recorded launch, the c_concat ones by `set_concat` (outside the recorded sequence: they change per call on the
-        host-issued path and once per trajectory in fifo_graph.BaseEngine)."""
+        host-issued path and once per trajectory in fifo_graph.BaseEngine).
+        adapter: None, or the number of `features_adapter` maps (openaimodel3d.py:562-564): one per input block `i` with
+        (i + 1) % 3 == 0, added to that block's output in front of `hs.append` from the plan-owned buffers `adapter_in[k]`
+        ([Bx*T, C_k, H_k, W_k] fp32, outside the pool like x_rows; written by `set_adapter`, read by a recorded launch)."""
         self.image_attn = getattr(model, "use_image_attention", False)
         if self.image_attn:
             for Ls in ([L] if isinstance(L, int) else [l for _, l in L]):
@@ -430,6 +433,10 @@ class _Plan(_PlanBase):
             raise ValueError(f"c_concat channels {self.pieces} leave no room for x in in_channels={m.in_channels}")
         self.x_in = torch.empty(self.Bx, self.kx, T, H, W, dtype=in_dtype, device=device)
         self.x_rows = None
+        self.adapter_sites = [i for i in range(len(m.input_blocks)) if (i + 1) % 3 == 0]
+        if adapter is not None and int(adapter) != len(self.adapter_sites):
+            raise ValueError(f"adapter={adapter}: this UNet has {len(self.adapter_sites)} adapter sites (input blocks {self.adapter_sites})")
+        self.adapter_in = None if adapter is None else []
         self.t_rows = torch.empty(self.BT, dtype=torch.int64, device=device)
         self.fps_rows = torch.empty(self.BT, dtype=torch.int64, device=device)
         self.ctx = torch.empty(self.ctx_rows, m.context_dim, dtype=torch.float16, device=device)
@@ -860,6 +867,8 @@ class _Plan(_PlanBase):
                     h = nh
             else:
                 h = self.run_seq(module, h)
+            if self.adapter_in is not None and (i + 1) % 3 == 0:
+                self._adapter_add(h, FT)
             hs.append(h)
             self._pinned.add(h.buf.data_ptr())
         h = self.run_seq(m.middle_block, h)
@@ -904,6 +913,19 @@ class _Plan(_PlanBase):
         self._emit(ops.nhwc_to_ncthw, o.buf, o.C, self.out, B=B, Cout=m.out_channels, T=T, HW=H * W)
         self._release(o.buf)
         self._finish_prefetch()
+
+    def _adapter_add(self, h, FT):
+        """`h = h + features_adapter[adapter_idx]` (openaimodel3d.py:562-564) in place on h's rows; both branches of a shared prefix
+        read the same FT source frames.  Whatever h's producer left behind or promised for a GroupNorm consumer (per-tile column
+        sums, a split-K reduce that could still move into the consumer) describes the tensor BEFORE the add: it is dropped -- the
+        producer goes back to its plain store loop and its own reduce -- and every consumer of the sum (the next block's GroupNorm or
+        transformer norm, the output block that reads it as skip) runs its own statistics pass."""
+        self._drop_colsum(h)
+        assert h.gstat is None and h.gstat_own is None and not h.cs_used      # (set by consumers only: h has none yet)
+        h.src, h.cs_rows = None, 0
+        src = torch.empty(FT, h.C, h.H, h.W, dtype=torch.float32, device=self.device)
+        self.adapter_in.append(src)
+        self._emit(ops.nchw_add_rows, h.buf, src, F=h.F, Fsrc=FT, Cn=h.C, HW=h.H * h.W)
 
     def _virtual_cat(self, module, h, skip):
         """torch.cat([h, skip], dim=1) (openaimodel3d.py:571) WITHOUT the copy, where both consumers can read two sources: the
@@ -989,16 +1011,33 @@ class _Plan(_PlanBase):
                               Cpad=self.x_rows.shape[1], c0=c0)
             c0 += k
 
-    def launch_async(self, x, t_rows, fps_rows, context, cur, c_concat=None):
+    def set_adapter(self, features):
+        """copy the `features_adapter` maps into the plan's buffers (on the current torch stream).  Every entry must be exactly
+        [Bx*T, C_k, H_k, W_k], fp32 or fp16: the reference's `h + feat` would broadcast other shapes, here they are refused."""
+        if self.adapter_in is None or len(features) != len(self.adapter_in):
+            raise ValueError(f"this plan was built for {0 if self.adapter_in is None else len(self.adapter_in)} features_adapter maps")
+        for k, (f, dst) in enumerate(zip(features, self.adapter_in)):
+            if not torch.is_tensor(f) or tuple(f.shape) != tuple(dst.shape):
+                raise ValueError(f"features_adapter[{k}] {tuple(f.shape) if torch.is_tensor(f) else type(f)}: expected {tuple(dst.shape)}")
+            if f.dtype not in (torch.float32, torch.float16):
+                raise ValueError(f"features_adapter[{k}] is {f.dtype}: expected float32 or float16")
+        for f, dst in zip(features, self.adapter_in):
+            dst.copy_(f, non_blocking=True)
+
+    def launch_async(self, x, t_rows, fps_rows, context, cur, c_concat=None, features_adapter=None):
         """enqueue one forward on this plan's stream (ordered after `cur`); the caller joins"""
         if (c_concat is None) != (self.pieces is None):
             raise ValueError("c_concat goes with a plan built for it (UNetModel.forward_concat)")
+        if (features_adapter is None) != (self.adapter_in is None):
+            raise ValueError("features_adapter goes with a plan built for it (UNetModel.forward(features_adapter=...))")
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             self.x_in.copy_(x, non_blocking=True)
             self.t_rows.copy_(t_rows, non_blocking=True)
             self.fps_rows.copy_(fps_rows, non_blocking=True)
             self.set_context(context)
+            if features_adapter is not None:
+                self.set_adapter(features_adapter)
             handle = self.stream.cuda_stream
             ops.set_stream(handle)
             try:
@@ -1011,9 +1050,9 @@ class _Plan(_PlanBase):
         self.n_runs += 1
         return out
 
-    def run(self, x, t_rows, fps_rows, context, c_concat=None):
+    def run(self, x, t_rows, fps_rows, context, c_concat=None, features_adapter=None):
         cur = torch.cuda.current_stream(self.device)
-        out = self.launch_async(x, t_rows, fps_rows, context, cur, c_concat=c_concat)
+        out = self.launch_async(x, t_rows, fps_rows, context, cur, c_concat=c_concat, features_adapter=features_adapter)
         out.record_stream(cur)
         cur.wait_stream(self.stream)
         return out

@@ -99,7 +99,9 @@ class DDIMSampler(object):
             cu = torch.cat(uc["c_crossattn"], 1)
             batched = cc.shape == cu.shape and set(c.keys()) == set(uc.keys()) <= {"c_crossattn", "fps"}
         unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-        if batched and self.cfg_mode == "concurrent" and hasattr(unet, "forward_concurrent") and not kwargs.get("no_concurrent"):
+        fa = kwargs.get("features_adapter")          # adapter maps (openaimodel3d.py:562-567): the same list for both branches
+        if batched and self.cfg_mode == "concurrent" and hasattr(unet, "forward_concurrent") and not kwargs.get("no_concurrent") \
+                and fa is None:
             f_c, f_u = c.get("fps", 16), uc.get("fps", 16)
             e_c, e_u = unet.forward_concurrent([dict(x=x, timesteps=t, context=cc, fps=f_c),
                                                 dict(x=x, timesteps=t, context=cu, fps=f_u)])
@@ -107,7 +109,7 @@ class DDIMSampler(object):
                 getattr(self.model.model, "conditioning_key", None) == "crossattn" and same_fps([c.get("fps", 16), uc.get("fps", 16)]):
             # both branches in ONE forward that shares everything before the first cross-attention (same x, same t)
             B = x.shape[0]
-            e = unet.forward_segments(x, t, [cc, cu], fps=[c.get("fps", 16), uc.get("fps", 16)], shared_x=True)
+            e = unet.forward_segments(x, t, [cc, cu], fps=[c.get("fps", 16), uc.get("fps", 16)], shared_x=True, features_adapter=fa)
             e_c, e_u = e[:B], e[B:]
         elif batched:
             B = x.shape[0]
@@ -123,6 +125,8 @@ class DDIMSampler(object):
                 t2 = torch.cat([tt, tt], 0)
             else:                                    # FIFO: per-frame timesteps, B == 1 -> per-(b,t) rows
                 t2 = torch.cat([tt, tt], 0)
+            if fa is not None:                       # [x, x]: the frames of every map twice
+                kwargs = dict(kwargs, features_adapter=[torch.cat([f, f], 0) for f in fa])
             e = self.model.apply_model(torch.cat([x, x], 0), t2, cond, **kwargs)
             e_c, e_u = e[:B], e[B:]
         else:
@@ -179,8 +183,11 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, eta=0., x_T=None, verbose=False,
-               unconditional_guidance_scale=1., unconditional_conditioning=None, latents_dir=None, noises=None, **kwargs):
-        """ddim.py:109-181 -> ddim_sampling (:183-252): the base 'N DDIM steps, single prompt' loop"""
+               unconditional_guidance_scale=1., unconditional_conditioning=None, latents_dir=None, noises=None,
+               features_adapter=None, **kwargs):
+        """ddim.py:109-181 -> ddim_sampling (:183-252): the base 'N DDIM steps, single prompt' loop.  `features_adapter` (a list of
+        maps, entry k [batch*T, C_k, h_k, w_k]) is what the reference's `sample(**kwargs)` hands down to `apply_model` and the UNet
+        (openaimodel3d.py:562-567): constant over the trajectory, the same for both guidance branches."""
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         size = (batch_size,) + tuple(shape)
         device = self.model.betas.device
@@ -190,24 +197,25 @@ class DDIMSampler(object):
         time_range = np.flip(self.ddim_timesteps)
         total_steps = self.ddim_timesteps.shape[0]
         kwargs.pop("temporal_length", None); kwargs.pop("conditional_guidance_scale_temporal", None)
-        fps_kwargs = {}
+        unet_kwargs = {} if features_adapter is None else {"features_adapter": list(features_adapter)}
         from .fifo_graph import BaseEngine
         if self.use_graph and self.share_prefix and BaseEngine.supported(self.model, img, conditioning, unconditional_conditioning,
-                                                                         unconditional_guidance_scale):
+                                                                         unconditional_guidance_scale, features_adapter=features_adapter):
             # the loop body as one hipGraph per step (fifo_graph.BaseEngine): latents, schedule and noise stay on the device
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())                  # the host generator seeds the device stream
             cu, cn = conditioning["c_crossattn"], unconditional_conditioning["c_crossattn"]
             key = (tuple(img.shape), sum(c.shape[1] for c in cu), sum(c.shape[1] for c in cn), float(unconditional_guidance_scale),
                    self.ddim_timesteps.tobytes(), np.asarray(self.ddim_sigmas).tobytes(), str(img.device),
-                   tuple(int(c.shape[1]) for c in conditioning.get("c_concat") or ()))
+                   tuple(int(c.shape[1]) for c in conditioning.get("c_concat") or ()),
+                   None if features_adapter is None else tuple(tuple(f.shape) for f in features_adapter))
             if self._base_engine is not None and self._base_engine[0] != key:
                 self._base_engine[1].close()
                 self._base_engine = None
             if self._base_engine is None:
                 self._base_engine = (key, BaseEngine(self.model, self, img, conditioning, unconditional_conditioning,
-                                                     unconditional_guidance_scale, seed=seed))
+                                                     unconditional_guidance_scale, seed=seed, features_adapter=features_adapter))
             else:
-                self._base_engine[1].reset(img, conditioning, unconditional_conditioning, seed)
+                self._base_engine[1].reset(img, conditioning, unconditional_conditioning, seed, features_adapter=features_adapter)
             eng = self._base_engine[1]
             for i in range(total_steps):
                 eng.step(noise=None if noises is None else noises[i])
@@ -219,7 +227,7 @@ class DDIMSampler(object):
             img, pred_x0 = self.p_sample_ddim(img, conditioning, ts, index=index,
                                               unconditional_guidance_scale=unconditional_guidance_scale,
                                               unconditional_conditioning=unconditional_conditioning,
-                                              noise=None if noises is None else noises[i], **fps_kwargs)
+                                              noise=None if noises is None else noises[i], **unet_kwargs)
         if latents_dir is not None:
             torch.save(img, f"{latents_dir}/{total_steps}.pt")        # :249-250
         return img, {}

@@ -507,8 +507,7 @@ class UNetModel(nn.Module):
     def _prepare(self, x, timesteps, context, features_adapter, fps, check_context=True, concat_channels=0):
         """argument checks + per-(b,t) timestep / fps rows shared by forward() and forward_concurrent(); `concat_channels`: channels
         that reach the first conv beside x's (forward_concat)"""
-        if features_adapter is not None:
-            raise NotImplementedError("features_adapter is always None on the MoCA path")
+        self._check_adapter(features_adapter)
         if context is None:
             raise ValueError("context is required (conditioning_key='crossattn')")
         if x.dim() != 5 or not x.is_cuda:
@@ -545,21 +544,39 @@ class UNetModel(nn.Module):
             raise ValueError("context batch must equal x batch")
         return t_rows, fps_rows
 
-    def _plan_for(self, x, L, replica=0, shared_x=False, pieces=None):
+    @property
+    def adapter_sites(self):
+        """number of `features_adapter` maps a forward consumes: input blocks with (id + 1) % 3 == 0 (openaimodel3d.py:562)"""
+        return len(self.input_blocks) // 3
+
+    def _check_adapter(self, features_adapter):
+        """the reference's failure modes for the list length (openaimodel3d.py:562-567): one map per input block with
+        (id + 1) % 3 == 0, indexed in order (too few: IndexError from `features_adapter[adapter_idx]`), the count asserted behind the
+        loop (too many).  None passes."""
+        if features_adapter is not None:
+            if len(features_adapter) < self.adapter_sites:
+                raise IndexError("list index out of range")
+            assert len(features_adapter) == self.adapter_sites, 'Wrong features_adapter'
+
+    def _plan_for(self, x, L, replica=0, shared_x=False, pieces=None, adapter=False):
         """L: context tokens, or a tuple of (videos, tokens) segments (see _Plan.segs); shared_x: x holds the distinct latents of
-        a batch that repeats them once per segment; pieces: channel counts of the c_concat tensors (forward_concat)"""
+        a batch that repeats them once per segment; pieces: channel counts of the c_concat tensors (forward_concat); adapter: the
+        plan adds `features_adapter` maps (forward / forward_segments)"""
         B, _, T, H, W = x.shape
         if shared_x:
             B *= len(L)
         key = (B, T, H, W, L, x.dtype, x.device.index, replica, shared_x)
         if pieces is not None:
             key += (pieces,)
+        if adapter:
+            key += ("adapter",)
         plan = self._plans.get(key)
         if plan is None and getattr(self, "_packed_only", False):
             raise RuntimeError("this rank received the packed operand set of the plans built before dist.broadcast_packed and holds no "
                                "parameters to pack a new plan from")
         if plan is None:
-            plan = _Plan(self, B, T, H, W, L, x.dtype, x.device, shared_x=shared_x, pieces=pieces)
+            plan = _Plan(self, B, T, H, W, L, x.dtype, x.device, shared_x=shared_x, pieces=pieces,
+                         adapter=self.adapter_sites if adapter else None)
             self._plans[key] = plan
         return plan
 
@@ -567,16 +584,22 @@ class UNetModel(nn.Module):
     def forward(self, x, timesteps, context=None, features_adapter=None, fps=16, **kwargs):
         """openaimodel3d.py:534-578.  x [B,C,T,h,w]; timesteps int64 [B] (or [T] with B == 1: the
         FIFO per-frame-timestep path, :535; or [B*T] per-(b,t), an extension); context [B,L,ctx];
-        fps int or [B]; unknown kwargs (clean_cond, gamma, ...) are ignored exactly as upstream."""
+        fps int or [B]; features_adapter: None or the list of maps added behind every third input block (:562-567), entry k exactly
+        [B*T, C_k, h_k, w_k] fp32 / fp16 (ValueError otherwise: the reference would broadcast); unknown kwargs (clean_cond, gamma,
+        ...) are ignored exactly as upstream."""
         t_rows, fps_rows = self._prepare(x, timesteps, context, features_adapter, fps)
-        return self._plan_for(x, context.shape[1]).run(x, t_rows, fps_rows, context)
+        fa = None if features_adapter is None else list(features_adapter)
+        return self._plan_for(x, context.shape[1], adapter=fa is not None).run(x, t_rows, fps_rows, context, features_adapter=fa)
 
     @torch.no_grad()
-    def forward_concat(self, x, c_concat, timesteps, context=None, fps=16, **kwargs):
+    def forward_concat(self, x, c_concat, timesteps, context=None, fps=16, features_adapter=None, **kwargs):
         """forward(torch.cat([x] + c_concat, dim=1), ...) without the concat (the `hybrid*` keys of DiffusionWrapper, ddpm3d.py:713-759):
         x [B,kx,T,h,w] and every c_concat entry [B,k_i,T,h,w] are written straight into their channel columns of the first conv's
         input rows (moca_ncthw_scatter_f16); kx + sum k_i must be `in_channels`.  Same kernels on the same operands as the plain
-        forward of the materialised concat from the first conv on."""
+        forward of the materialised concat from the first conv on.  `features_adapter` is refused here (the adapter-guided checkpoints
+        are `crossattn` models)."""
+        if features_adapter is not None:
+            raise NotImplementedError("features_adapter with c_concat (the hybrid keys): use forward()")
         c_concat = list(c_concat)
         pieces = tuple(int(c.shape[1]) for c in c_concat)
         if x.dim() != 5 or any(c.dim() != 5 or c.shape[:1] + c.shape[2:] != x.shape[:1] + x.shape[2:] for c in c_concat):
@@ -590,7 +613,7 @@ class UNetModel(nn.Module):
         return self._plan_for(x, context.shape[1], pieces=pieces).run(x, t_rows, fps_rows, context, c_concat=c_concat)
 
     @torch.no_grad()
-    def forward_segments(self, x, timesteps, contexts, fps=16, shared_x=False):
+    def forward_segments(self, x, timesteps, contexts, fps=16, shared_x=False, features_adapter=None):
         """One forward over a batch whose videos carry contexts of DIFFERENT lengths: `contexts` = list of [n_i, L_i, D]
         tensors in batch order (sum n_i = B), e.g. the 2n conditional FIFO windows with two prompts (154 tokens) followed
         by their unconditional copies (77 tokens).  Same values as one forward() per segment: every UNet op is per-sample
@@ -600,33 +623,40 @@ class UNetModel(nn.Module):
         guidance (ddim.py:298-299,366-369).  x [n, ...], timesteps and fps describe the n distinct videos, every context is
         [n, L_i, D]; returns [len(contexts) * n, ...] (segment-major).  Everything before the first cross-attention is computed
         once (see _Plan) with the fps embedding of the first segment, so a per-segment fps list must hold EQUAL entries
-        (ValueError otherwise: `same_fps`)."""
+        (ValueError otherwise: `same_fps`).
+        features_adapter: as in forward(), one list for the videos of x ([n*T, C_k, h_k, w_k] per entry): with shared_x every
+        segment reads the same maps."""
         n = x.shape[0]
+        fa = None if features_adapter is None else list(features_adapter)
         if shared_x:
             if any(c.shape[0] != n for c in contexts):
                 raise ValueError("shared_x: every context must have one row block per latent video")
             segs = tuple((n, int(c.shape[1])) for c in contexts)
             fps_list = list(fps) if isinstance(fps, (list, tuple)) else [fps] * len(contexts)
-            rows = [self._prepare(x, timesteps, contexts[0], None, f, check_context=False) for f in fps_list]
+            rows = [self._prepare(x, timesteps, contexts[0], fa, f, check_context=False) for f in fps_list]
             if not same_fps(fps_list):
                 # the shared prefix (conv_in .. the first ResBlock) adds ONE fps embedding to the rows both branches read
                 raise ValueError("shared_x: the segments share everything before the first cross-attention, so their fps must be "
                                  "equal (use shared_x=False for branches with different fps)")
             t_rows = torch.cat([r[0] for r in rows])
             fps_rows = torch.cat([r[1] for r in rows])
-            return self._plan_for(x, segs, shared_x=True).run(x, t_rows, fps_rows, list(contexts))
+            return self._plan_for(x, segs, shared_x=True, adapter=fa is not None).run(x, t_rows, fps_rows, list(contexts),
+                                                                                      features_adapter=fa)
         segs = tuple((int(c.shape[0]), int(c.shape[1])) for c in contexts)
         if sum(nv for nv, _ in segs) != n:
             raise ValueError("contexts must cover the batch of x")
-        t_rows, fps_rows = self._prepare(x, timesteps, contexts[0], None, fps, check_context=False)
-        return self._plan_for(x, segs).run(x, t_rows, fps_rows, list(contexts))
+        t_rows, fps_rows = self._prepare(x, timesteps, contexts[0], fa, fps, check_context=False)
+        return self._plan_for(x, segs, adapter=fa is not None).run(x, t_rows, fps_rows, list(contexts), features_adapter=fa)
 
     @torch.no_grad()
     def forward_concurrent(self, calls):
         """Several independent forwards (e.g. the conditional and unconditional CFG branch) launched as
         separate hipGraphs on separate streams so the GPU overlaps them: one chain's partial last round of
         tiles, kernel prologues/epilogues and launch gaps are filled by the other chain's kernels.
-        calls: list of dicts(x, timesteps, context, fps).  Returns the list of outputs (same values as forward)."""
+        calls: list of dicts(x, timesteps, context, fps).  Returns the list of outputs (same values as forward).  A call with
+        `features_adapter` is refused."""
+        if any(c.get("features_adapter") is not None for c in calls):
+            raise NotImplementedError("features_adapter in forward_concurrent: use forward() / forward_segments()")
         prepared = []
         for i, c in enumerate(calls):
             t_rows, fps_rows = self._prepare(c["x"], c["timesteps"], c["context"], None, c.get("fps", 16))

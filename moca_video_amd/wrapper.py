@@ -69,7 +69,8 @@ class DiffusionWrapper(nn.Module):
     """lvdm/models/ddpm3d.py:696-763: `crossattn` and the five `hybrid*` keys (x and the `c_concat` latents concatenated along the
     channel axis, `c_crossattn` as the context).  The hybrid branches keep the reference's argument handling: `**kwargs` (so a
     `fps` of the conditioning dict) are NOT forwarded and the UNet runs with its default fps=16; `y=` / `s=` / `mask=` are passed
-    and ignored by the UNet as upstream.  The concat is not materialised for our UNet (`UNetModel.forward_concat`)."""
+    and ignored by the UNet as upstream.  The concat is not materialised for our UNet (`UNetModel.forward_concat`).
+    `features_adapter=` (openaimodel3d.py:562-567) rides in `**kwargs`: `crossattn` hands it to the UNet, the hybrid keys refuse it."""
 
     def __init__(self, diff_model_config, conditioning_key):
         super().__init__()
@@ -77,6 +78,10 @@ class DiffusionWrapper(nn.Module):
         self.conditioning_key = conditioning_key
 
     def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, c_adm=None, s=None, mask=None, **kwargs):
+        if self.conditioning_key in HYBRID_KEYS and kwargs.get("features_adapter") is not None:
+            # (upstream drops **kwargs on these branches, so the maps would silently not be applied: refused instead)
+            raise NotImplementedError(f"features_adapter with conditioning_key={self.conditioning_key!r}: the adapter maps reach the UNet "
+                                      "through the 'crossattn' key only")
         if self.conditioning_key == 'crossattn':
             cc = torch.cat(c_crossattn, 1)                                   # :711
             out = self.diffusion_model(x, t, context=cc, **kwargs)           # :712

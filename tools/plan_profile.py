@@ -21,7 +21,9 @@ roofline floor of the step = max(FLOP / 1.7 PFLOP/s, bytes / 5.5 TB/s) -- 1.7 PF
 fp16 data on this chip (tools/micro/mfma_peak.hip), 5.5 TB/s a streaming kernel's HBM rate -- and the slack each - floor.
 A JSON copy (PP_JSON=path) carries the per-key numbers for tools/ingraph_vs_hot.py.
 PP_CAUSAL=1: the same model and weights with use_causal_attention (every TemporalTransformer flagged before the plan is built): the
-fused q|k|v launches then carry the mask and print as "+tattn causal" -- same operands as the plain run's "+tattn" lines."""
+fused q|k|v launches then carry the mask and print as "+tattn causal" -- same operands as the plain run's "+tattn" lines.
+PP_ADAPTER=1: the forward with `features_adapter` maps (random, at the four site shapes): the four nchw_add_rows launches, and the
+statistics passes that replace what the producers of the summed maps no longer leave behind (groupnorm, gstat_accum lines)."""
 import collections
 import json
 import os
@@ -52,12 +54,20 @@ n = B // 2 if SHARED else B
 x = torch.randn(n, 4, 16, 40, 64, device=dev, generator=g)
 ctx = torch.randn(B, 77, 1024, device=dev, generator=g)
 ts = torch.full((n,), 500, device=dev, dtype=torch.long)
+maps = None
+if os.environ.get("PP_ADAPTER", "0") == "1":
+    maps, hw = [], (40, 64)
+    for i, blk in enumerate(unet.input_blocks):
+        if (i + 1) % 3 == 0:
+            res = [m for m in blk if hasattr(m, "cout")]
+            maps.append(torch.randn(n * 16, res[0].cout, *hw, device=dev, generator=g))
+            hw = ((hw[0] - 1) // 2 + 1, (hw[1] - 1) // 2 + 1)
 with torch.no_grad():
     for _ in range(2):
         if SHARED:
-            unet.forward_segments(x, ts, [ctx[:n], ctx[n:]], fps=torch.tensor([10] * n, device=dev), shared_x=True)
+            unet.forward_segments(x, ts, [ctx[:n], ctx[n:]], fps=torch.tensor([10] * n, device=dev), shared_x=True, features_adapter=maps)
         else:
-            unet(x, ts, ctx, fps=torch.tensor([10] * B, device=dev))
+            unet(x, ts, ctx, fps=torch.tensor([10] * B, device=dev), features_adapter=maps)
 torch.cuda.synchronize()
 plan = next(iter(unet._plans.values()))
 st = plan.stream
@@ -103,6 +113,10 @@ def describe(s):
             (" +x" if kw.get("write_x") else ""), 0.0, 4.0 * kw["splits"] * kw["M"] * pw.N + 2.0 * kw["M"] * pw.N * (2 if kw.get("write_x") else 1)
     if fn == "gstat_accum":
         return f"gstat_accum F={kw['F']} HW={kw['HW']} C={kw['Cn']}", 0.0, 2.0 * kw["F"] * kw["HW"] * kw["Cn"]
+    if fn == "nchw_add_rows":
+        src = s.args[1]
+        return f"nchw_add_rows F={kw['F']} Fsrc={kw['Fsrc']} HW={kw['HW']} C={kw['Cn']}", 0.0, \
+            4.0 * kw["F"] * kw["HW"] * kw["Cn"] + float(src.element_size()) * kw["F"] * kw["HW"] * kw["Cn"]
     if fn == "layernorm":
         return f"layernorm M={kw['M']} C={kw['Cn']}", 0.0, 4.0 * kw["M"] * kw["Cn"]
     if fn == "attention":
