@@ -402,6 +402,13 @@ int moca_ddim_update_f32(const float* x, const float* e, const float* noise, flo
                          float* pred_x0, float a_t, float a_prev, float sigma_t,
                          float sqrt_one_minus_at, int32_t use_scale, float scale_t,
                          float scale_prev, int64_t n, void* stream);
+/* q_sample at per-sample schedule indices (`stochastic_encode`, ddim.py:652-671; `extract_into_tensor` :665-668):
+ *   out[b][p] = coef_x[t[b]] * x0[b][p] + coef_n[t[b]] * noise[b][p],  b < B, p < per, fp32: two rounded products, one rounded sum.
+ * coef_x / coef_n [n_tab] and t [B] (int64) are DEVICE memory and gathered in the kernel: no host read, the launch can be captured.
+ * out may alias x0.  per need not be a multiple of 4 and samples need not start 16-byte aligned.  t[b] outside [0, n_tab) reads no
+ * table entry: sample b comes back as NaN (the Python layer raises IndexError where it holds t on the host). */
+int moca_q_sample_f32(const float* x0, const float* noise, float* out, const float* coef_x, const float* coef_n,
+                      const int64_t* t, int32_t B, int32_t n_tab, int64_t per, void* stream);
 /* MoCA FIFO step (ddim.py:405-430,556-609 arithmetic): per-frame coefficients, momentum
  * EMA along the frame axis, x_prev, mask injection into pred_x0, gamma blend.  All latent
  * tensors [B][C][F][HW] f32.  coef[F][6] = {sqrt(a_t), sqrt(a_prev), sigma_t, sqrt(1-a_t),

@@ -4,10 +4,12 @@ Public surface mirrors the reference interfaces for this path only:
   UNetModel            lvdm/modules/networks/openaimodel3d.py:279-578
   DiffusionWrapper     lvdm/models/ddpm3d.py:696-763
   DenoiseModel         the slice of LatentDiffusion the samplers use (apply_model + schedule buffers)
-  DDIMSampler          lvdm/models/samplers/ddim.py (make_schedule, p_sample_ddim, unet, ddim_step, fifo_onestep)
+  DDIMSampler          lvdm/models/samplers/ddim.py (make_schedule, p_sample_ddim, unet, ddim_step, fifo_onestep,
+                       stochastic_encode, decode, ddim_inversion)
   freq_mix_3d, get_freq_filter   utils/freeinit_utils.py
   prepare_latents, shift_latents, fifo_ddim_sampling, base_ddim_sampling   scripts/evaluation/funcs.py
   fifo_ddim_sampling_multiprompts   funcs.py:375-468 (one video, prompts switched inside the one-graph loop)
+  v2v_ddim_sampling    DDIMSampler.stochastic_encode + decode (ddim.py:652-692): noise a clip's latents, denoise under a new prompt
   load_multiprompts, run_multiprompts   its prompt file and driver (moca_video_amd.io)
   instantiate_from_config       utils/utils.py:27-42
   AutoencoderKL                 lvdm/models/autoencoder.py:13-107 + lvdm/modules/networks/ae_modules.py:364-579
@@ -30,9 +32,9 @@ from .tokenizer import SimpleTokenizer  # noqa: E402
 from .image_proj import ImageProjModel, Resampler  # noqa: E402
 from .clip_vision import FrozenOpenCLIPImageEmbedder, FrozenOpenCLIPImageEmbedderV2  # noqa: E402
 from .wrapper import LatentVisualDiffusion  # noqa: E402
-from .fifo import fifo_ddim_sampling_multiprompts  # noqa: E402
+from .fifo import fifo_ddim_sampling_multiprompts, v2v_ddim_sampling  # noqa: E402
 from .io import load_multiprompts, run_multiprompts  # noqa: E402
 
 __all__ = ["UNetModel", "DiffusionWrapper", "DenoiseModel", "AutoencoderKL", "FrozenOpenCLIPEmbedder", "SimpleTokenizer", "ImageProjModel", "Resampler",
            "FrozenOpenCLIPImageEmbedder", "FrozenOpenCLIPImageEmbedderV2", "LatentVisualDiffusion", "instantiate_from_config",
-           "load_unet_config", "fifo_ddim_sampling_multiprompts", "load_multiprompts", "run_multiprompts"]
+           "load_unet_config", "fifo_ddim_sampling_multiprompts", "v2v_ddim_sampling", "load_multiprompts", "run_multiprompts"]

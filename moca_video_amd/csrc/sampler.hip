@@ -122,6 +122,57 @@ __global__ void gaussian_sample_kernel(const float* __restrict__ mom, const floa
     }
 }
 
+// q_sample over per-sample schedule indices (ddim.py:652-671 `stochastic_encode`): out[b][p] = ca[t[b]] * x0[b][p] + cb[t[b]] * noise[b][p].
+// The gather of both tables runs here (t and the tables are device memory: nothing for the host to read, the launch can be captured).
+// mul, mul, add with no contraction = the torch expression bit for bit.  One thread per group of four consecutive elements of the FLAT
+// [B * per] range: a group that lies inside one sample (and the pointers being 16-byte aligned) moves as float4, a group that straddles
+// two samples (per % 4 != 0) or the end goes element by element, each with its own sample's coefficients -- nothing is read or written
+// past B * per.  out may alias x0 (every element is read before it is written, by the same thread).  An index outside [0, n_tab) reads
+// no table entry: that sample's output is NaN.
+__device__ __forceinline__ void q_coef(const float* __restrict__ ca, const float* __restrict__ cb, const int64_t* __restrict__ t, int64_t b,
+                                       int n_tab, float& a, float& c, bool& bad) {
+    const int64_t tb = t[b];
+    bad = tb < 0 || tb >= (int64_t)n_tab;
+    a = bad ? 0.f : ca[tb];
+    c = bad ? 0.f : cb[tb];
+}
+
+__global__ __launch_bounds__(256) void q_sample_kernel(const float* x0, const float* __restrict__ noise, float* out,
+                                                       const float* __restrict__ ca, const float* __restrict__ cb,
+                                                       const int64_t* __restrict__ t, int B, int n_tab, int64_t per, int vec_ok) {
+    const int64_t total = (int64_t)B * per;
+    const int64_t n4 = (total + 3) / 4;
+    const float qnan = __builtin_nanf("");
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
+        const int64_t e0 = q * 4;
+        const int64_t b0 = e0 / per;
+        if (vec_ok && e0 + 3 < total && (e0 + 3) / per == b0) {
+            float a, c;
+            bool bad;
+            q_coef(ca, cb, t, b0, n_tab, a, c, bad);
+            const float4 xv = *reinterpret_cast<const float4*>(x0 + e0);
+            const float4 nv = *reinterpret_cast<const float4*>(noise + e0);
+            float4 o;
+            o.x = a * xv.x + c * nv.x;
+            o.y = a * xv.y + c * nv.y;
+            o.z = a * xv.z + c * nv.z;
+            o.w = a * xv.w + c * nv.w;
+            if (bad) o = make_float4(qnan, qnan, qnan, qnan);
+            *reinterpret_cast<float4*>(out + e0) = o;
+        } else {
+            for (int j = 0; j < 4; ++j) {
+                const int64_t e = e0 + j;
+                if (e >= total) break;
+                float a, c;
+                bool bad;
+                q_coef(ca, cb, t, e / per, n_tab, a, c, bad);
+                const float v = a * x0[e] + c * noise[e];
+                out[e] = bad ? qnan : v;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int moca_cfg_combine_f32(const float* e_c, const float* e_u, float* out, float scale,
@@ -175,6 +226,17 @@ extern "C" int moca_gaussian_sample_f32(const float* moments, const float* noise
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(gaussian_sample_kernel, dim3(blocks), dim3(256), 0, moca_stream(stream), moments, noise, out, n, z, hw, scale);
+    MOCA_CHECK_LAUNCH();
+    return MOCA_OK;
+}
+
+extern "C" int moca_q_sample_f32(const float* x0, const float* noise, float* out, const float* coef_x, const float* coef_n,
+                                 const int64_t* t, int32_t B, int32_t n_tab, int64_t per, void* stream) {
+    if (!x0 || !noise || !out || !coef_x || !coef_n || !t || B <= 0 || per <= 0 || n_tab <= 0) return MOCA_E_BADARG;
+    const int vec_ok = (((uintptr_t)x0 | (uintptr_t)noise | (uintptr_t)out) & 15) == 0;
+    const int64_t n4 = ((int64_t)B * per + 3) / 4;
+    hipLaunchKernelGGL(q_sample_kernel, dim3(grid_for(n4)), dim3(256), 0, moca_stream(stream), x0, noise, out, coef_x, coef_n, t, B, n_tab,
+                       per, vec_ok);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }

@@ -1,5 +1,5 @@
 """Latent-queue side of the FIFO / MoCA loop (`scripts/evaluation/funcs.py`): `prepare_latents`
-(:21-82), `shift_latents` (:86-99), `base_ddim_sampling` (:177-241) and the window scheduling of
+(:21-82), `shift_latents` (:86-99), `base_ddim_sampling` (:177-241), `v2v_ddim_sampling` (its start-from-a-clip sibling) and the window scheduling of
 `fifo_ddim_sampling` (:243-373).  The queue stays resident in HBM; VAE decoding of emitted frames
 (funcs.py:359-365) is outside the hot path: the loop hands each emitted latent to `emit`.
 Noise is an optional explicit argument wherever the reference calls torch.randn*."""
@@ -14,7 +14,7 @@ from . import lib as _l
 from . import ops
 from .fifo_graph import FifoEngine, fifo_windows
 from .freeinit import freq_mix_3d, get_freq_filter
-from .sampler import DDIMSampler
+from .sampler import DDIMSampler, sqrt_f32
 
 
 def prepare_latents(args, input_path, sampler, model=None, data=None, initial_latents=None, noises=None):
@@ -38,7 +38,7 @@ def prepare_latents(args, input_path, sampler, model=None, data=None, initial_la
     # reference's 0-dim fp32 tensors (alpha ** 0.5, (1 - alpha) ** 0.5); the arithmetic over the latents is one kernel
     alphas = torch.as_tensor(np.asarray(sampler.ddim_alphas), dtype=torch.float32)
     j_alpha = torch.cat([alphas[:1].expand(n_look), alphas[:N]])
-    coef_z, coef_n = j_alpha ** 0.5, (1 - j_alpha) ** 0.5
+    coef_z, coef_n = sqrt_f32(j_alpha), sqrt_f32(1 - j_alpha)        # (correctly rounded: torch's host sqrt differs between CPU vendors)
     fidx = torch.tensor([0] * n_look + [max(0, i - (N - tz)) for i in range(N)], dtype=torch.int32)
     if noises is None:
         noise = torch.randn(b, c, Q, h, w, device=z.device)          # the Q torch.randn_like draws of :62,72, one tensor
@@ -116,6 +116,23 @@ def uncond_embedding(model, c_emb, uc_emb):
     raise NotImplementedError(f"uncond_type {utype!r}")
 
 
+def base_uncond(model, cond, batch, cfg_scale, uc_emb=None):
+    """the unconditional branch of funcs.py:197-216 (None without guidance): `model.uncond_type`'s context -- for an image-conditioned
+    model followed by the image tokens of a zero image (:207-210) -- in a copy of `cond` that replaces `c_crossattn` only (:211-214)"""
+    if cfg_scale == 1.0:
+        return None
+    c_emb = cond["c_crossattn"][0] if isinstance(cond, dict) else cond
+    uc_emb = uncond_embedding(model, c_emb, uc_emb)       # model.uncond_type (:199-206)
+    if hasattr(model, "embedder"):                        # image-conditioned model (:207-210): + the embedding of a zero image
+        uc_img = model.get_image_embeds(torch.zeros(batch, 3, 224, 224, device=model.device))
+        uc_emb = torch.cat([uc_emb, uc_img], dim=1)
+    if isinstance(cond, dict):
+        uc = {key: cond[key] for key in cond.keys()}
+        uc.update({'c_crossattn': [uc_emb]})
+        return uc
+    return uc_emb
+
+
 def base_ddim_sampling(model, cond, noise_shape, ddim_steps=50, ddim_eta=1.0, cfg_scale=1.0, uc_emb=None,
                        latents_dir=None, x_T=None, noises=None, use_graph=True):
     """funcs.py:177-241: returns (batch_images, ddim_sampler, samples) like the reference; batch_images is the VAE
@@ -123,22 +140,39 @@ def base_ddim_sampling(model, cond, noise_shape, ddim_steps=50, ddim_eta=1.0, cf
     model.get_learned_conditioning([""]) (the text encoder is out of scope)."""
     sampler = DDIMSampler(model)
     sampler.use_graph = use_graph            # one hipGraph per DDIM step (fifo_graph.BaseEngine) vs host-issued p_sample_ddim
-    uc = None
-    if cfg_scale != 1.0:
-        c_emb = cond["c_crossattn"][0] if isinstance(cond, dict) else cond
-        uc_emb = uncond_embedding(model, c_emb, uc_emb)   # model.uncond_type (:199-206)
-        if hasattr(model, "embedder"):                    # image-conditioned model (:207-210): + the embedding of a zero image
-            uc_img = model.get_image_embeds(torch.zeros(noise_shape[0], 3, 224, 224, device=model.device))
-            uc_emb = torch.cat([uc_emb, uc_img], dim=1)
-        if isinstance(cond, dict):
-            uc = {key: cond[key] for key in cond.keys()}
-            uc.update({'c_crossattn': [uc_emb]})
-        else:
-            uc = uc_emb
+    uc = base_uncond(model, cond, noise_shape[0], cfg_scale, uc_emb)
     samples, _ = sampler.sample(S=ddim_steps, conditioning=cond, batch_size=noise_shape[0], shape=noise_shape[1:],
                                 verbose=False, unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc,
                                 eta=ddim_eta, x_T=x_T, latents_dir=latents_dir, noises=noises)
     sampler.release()                        # the step graph's buffers: the FIFO stage that follows builds its own plan
+    images = model.decode_first_stage_2DAE(samples) if getattr(model, "first_stage_model", None) is not None else None
+    return images, sampler, samples
+
+
+def v2v_ddim_sampling(model, cond, latents=None, frames=None, ddim_steps=50, t_start=25, ddim_eta=1.0, cfg_scale=1.0, uc_emb=None,
+                      noise=None, noises=None, use_graph=True):
+    """Video-to-video: noise a clip's latents to schedule index `t_start` (`DDIMSampler.stochastic_encode`, ddim.py:652-671) and
+    denoise them under `cond` for t_start steps (`DDIMSampler.decode`, :674-692) -- the upstream img2img convention, so
+    1 <= t_start <= ddim_steps - 1.  Exactly one of `latents` [B,4,T,h,w] and `frames` [B,3,T,H,W] (VAE-encoded first,
+    `encode_first_stage_2DAE`).  The unconditional branch is `base_ddim_sampling`'s.  `noise` fixes the encode draw, `noises[i]` the
+    draw of decode step i.  Returns (images, sampler, samples) like `base_ddim_sampling`."""
+    if (latents is None) == (frames is None):
+        raise ValueError("v2v_ddim_sampling wants exactly one of latents= and frames=")
+    if not 1 <= int(t_start) <= int(ddim_steps) - 1:
+        raise ValueError(f"t_start = {t_start}: the clip is encoded at schedule index t_start and decoded over t_start steps, "
+                         f"so 1 <= t_start <= ddim_steps - 1 = {int(ddim_steps) - 1}")
+    t_start = int(t_start)
+    if frames is not None:
+        latents = model.encode_first_stage_2DAE(frames.to(model.device))
+    x0 = latents.to(model.device)
+    sampler = DDIMSampler(model)
+    sampler.use_graph = use_graph
+    sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_eta=ddim_eta, verbose=False)
+    uc = base_uncond(model, cond, x0.shape[0], cfg_scale, uc_emb)
+    t = torch.full((x0.shape[0],), t_start, dtype=torch.long)
+    x_enc = sampler.stochastic_encode(x0, t, noise=noise)
+    samples = sampler.decode(x_enc, cond, t_start, unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc, noises=noises)
+    sampler.release()
     images = model.decode_first_stage_2DAE(samples) if getattr(model, "first_stage_model", None) is not None else None
     return images, sampler, samples
 

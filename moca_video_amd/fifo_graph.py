@@ -354,7 +354,12 @@ class BaseEngine:
     """One step of base sampling -- `DDIMSampler.ddim_sampling`'s loop body (ddim.py:226-252: two UNet calls on the same latents, guidance,
     the DDIM update with `use_scale`, fresh noise) -- as ONE hipGraph: [timestep rows of step i] + the shared-prefix UNet forward of
     the B latents x (conditional, unconditional) + [noise, guidance + update in place, i += 1].  The latents live in the plan's input
-    buffer, the schedule in device tables indexed by the state block's iteration counter; the host only replays."""
+    buffer, the schedule in device tables indexed by the state block's iteration counter; the host only replays.
+
+    `n_rows` (default: the whole schedule) builds the tables over the FIRST n_rows schedule rows, so that the S of the captured kernels
+    is n_rows and step i uses row n_rows - 1 - i: `DDIMSampler.decode(x, c, t_start)` (ddim.py:674-692) is this engine with
+    n_rows = t_start.  `encode` noises a clean latent into the plan's input buffer (`stochastic_encode`, ddim.py:652-671) with the
+    tables of the WHOLE schedule, so a video-to-video run is reset -> encode(x0, t_start) -> t_start steps, all on the device."""
 
     @staticmethod
     def supported(model, x, cond, uc, scale, features_adapter=None):
@@ -382,7 +387,7 @@ class BaseEngine:
         return set(cond.keys()) <= {"c_crossattn", "fps"} and key == "crossattn" and \
             same_fps([cond.get("fps", 16), uc.get("fps", 16)])      # (the shared prefix adds ONE fps embedding)
 
-    def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, keep_pred_x0=False, features_adapter=None):
+    def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, keep_pred_x0=False, features_adapter=None, n_rows=None):
         self.unet = unet = model.model.diffusion_model
         dev = x.device
         self.device = dev
@@ -390,7 +395,9 @@ class BaseEngine:
             unet._pack()
         B, Cc, T, H, W = x.shape
         self.shape = (B, Cc, T, H, W)
-        S = len(sampler.ddim_timesteps)
+        S = len(sampler.ddim_timesteps) if n_rows is None else int(n_rows)
+        if not 1 <= S <= len(sampler.ddim_timesteps):
+            raise ValueError(f"n_rows = {n_rows}: the schedule has {len(sampler.ddim_timesteps)} rows")
         self.S = S
         cc, cu = torch.cat(cond["c_crossattn"], 1), torch.cat(uc["c_crossattn"], 1)
         segs = ((B, int(cc.shape[1])), (B, int(cu.shape[1])))
@@ -419,8 +426,10 @@ class BaseEngine:
             coef[i, 5] = f32(sampler.ddim_scale_arr[i]) if use_scale else 1.0
             coef[i, 6] = f32(sampler.ddim_scale_arr_prev[i]) if use_scale else 1.0
         self.coef = torch.from_numpy(coef).to(dev)
-        self.t_table = torch.from_numpy(np.asarray(sampler.ddim_timesteps, dtype=np.int64)).to(dev)
+        self.t_table = torch.from_numpy(np.ascontiguousarray(np.asarray(sampler.ddim_timesteps, dtype=np.int64)[:S])).to(dev)
+        self.enc_coef = tuple(c.to(dev) for c in sampler.encode_tables())     # `encode`: the whole schedule's q_sample tables
         self.state = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.enc_state = torch.zeros(8, dtype=torch.int32, device=dev)        # the noise stream of `encode`: same seed, iteration -1
         n = x.numel()
         self.noise = torch.zeros(n, dtype=torch.float32, device=dev)
         self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev) if keep_pred_x0 else None
@@ -455,6 +464,8 @@ class BaseEngine:
         plan.stream.wait_stream(cur)
         with torch.cuda.stream(plan.stream):
             self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
+            st.iter = -1                                         # (no step ever draws at this iteration: steps count up from 0)
+            self.enc_state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
             plan.x_in.copy_(x.to(torch.float32))
             plan.fps_rows.copy_(torch.cat([self._fps_rows(fps_c), self._fps_rows(fps_u)]))
             plan.set_context([cc, cu])
@@ -468,6 +479,40 @@ class BaseEngine:
                     ops.set_stream(None)
         cur.wait_stream(plan.stream)
         self.n_iter = 0
+
+    def encode(self, x0, t_index, noise=None):
+        """`stochastic_encode` (ddim.py:652-671) into the plan's input buffer: x_in = sqrt(a)[t] x0 + sqrt(1 - a)[t] noise on the plan's
+        stream (enqueued, not synchronised), the start of a video-to-video trajectory.  `t_index`: one schedule index for all samples or
+        a [B] tensor of them, on either device (host values are range-checked; the kernel gathers).  `noise` None: drawn by
+        `moca_fifo_randn_f32` from the engine's own Philox stream (this trajectory's seed at iteration -1, which no step uses), so
+        nothing moves through the host."""
+        plan, dev = self.plan, self.device
+        B = self.shape[0]
+        if tuple(x0.shape) != tuple(self.shape):
+            raise ValueError(f"x0 {tuple(x0.shape)} does not match the engine's latents {tuple(self.shape)}")
+        t = torch.as_tensor(t_index)
+        t = t.reshape(1).expand(B) if t.dim() == 0 else t
+        n_tab = int(self.enc_coef[0].shape[0])
+        if t.dim() != 1 or t.shape[0] != B:
+            raise ValueError(f"t_index must be one schedule index or [{B}] of them, got {tuple(t.shape)}")
+        if not t.is_cuda and (int(t.min()) < 0 or int(t.max()) >= n_tab):
+            raise IndexError(f"index {t.tolist()} is out of bounds for the {n_tab}-entry schedule table")
+        lib = _l.load()
+        n = self.noise.numel()
+        cur = torch.cuda.current_stream(dev)
+        plan.stream.wait_stream(cur)
+        with torch.cuda.stream(plan.stream):
+            h = C.c_void_p(plan.stream.cuda_stream)
+            src = x0.to(dev, torch.float32).contiguous()
+            t_d = t.to(dev, torch.int64).contiguous()
+            if noise is not None:
+                self.noise.copy_(noise.reshape(-1).to(dev, torch.float32))
+            else:
+                _l.check(lib.moca_fifo_randn_f32(_l.ptr(self.enc_state), _l.ptr(self.noise), n, h), "moca_fifo_randn_f32")
+            _l.check(lib.moca_q_sample_f32(_l.ptr(src), _l.ptr(self.noise), _l.ptr(plan.x_in), _l.ptr(self.enc_coef[0]), _l.ptr(self.enc_coef[1]),
+                                           _l.ptr(t_d), B, n_tab, n // B, h), "moca_q_sample_f32")
+        src.record_stream(plan.stream)
+        t_d.record_stream(plan.stream)
 
     def step(self, noise=None):
         """one DDIM step (enqueued, not synchronised); `noise` [B,C,T,H,W] fixes the draw"""

@@ -122,6 +122,7 @@ SIGNATURES = {
     "moca_gaussian_sample_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "moca_cfg_combine_f32": (C.c_int, [_vp, _vp, _vp, _f32, _i64, _vp]),
     "moca_ddim_update_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _i64, _vp]),
+    "moca_q_sample_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp]),
     "moca_fifo_ddim_step_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "moca_fifo_randn_f32": (C.c_int, [_vp, _vp, _i64, _vp]),

@@ -1,7 +1,8 @@
 """MI355X host-side mirror of `lvdm.models.samplers.ddim.DDIMSampler` for the hot path:
 `make_schedule` (ddim.py:62-106), `sample`/`ddim_sampling` (:109-252), `p_sample_ddim`
-(:274-359), `fifo_onestep` (:255-271), `unet` (:362-374) and the MoCA `ddim_step`
-(:377-649).  All per-element arithmetic runs in the fp32 HIP kernels of
+(:274-359), `fifo_onestep` (:255-271), `unet` (:362-374), the MoCA `ddim_step`
+(:377-649) and the start-from-a-video path: `stochastic_encode` (:652-671), `decode` (:674-692) and
+`ddim_inversion` (:972-1032).  All per-element arithmetic runs in the fp32 HIP kernels of
 csrc/sampler.hip; only O(steps) scalar schedule math stays on the host (numpy, as in
 the reference).
 
@@ -49,6 +50,15 @@ def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
     return sigmas, alphas, alphas_prev
 
 
+def sqrt_f32(t):
+    """fp32 square root of a host tensor, correctly rounded on every host (numpy's: the hardware instruction).  torch's own CPU sqrt /
+    `** 0.5` is not correctly rounded and its last bit differs between CPU vendors (an Intel and an AMD EPYC host disagree on a fifth
+    of the 1000 `alphas_cumprod`), so schedule coefficients taken with it -- and the latents they scale -- would depend on the host;
+    the reference's `torch.sqrt(ddim_alphas)` / `alpha ** 0.5` mean this value."""
+    t = torch.as_tensor(t, dtype=torch.float32).detach().cpu().contiguous()
+    return torch.from_numpy(np.sqrt(t.numpy()))
+
+
 def _st():
     return C.c_void_p(ops.current_stream())
 
@@ -87,6 +97,9 @@ class DDIMSampler(object):
         sig, al, alp = make_ddim_sampling_parameters(alphacums=ac, ddim_timesteps=self.ddim_timesteps, eta=ddim_eta, verbose=verbose)
         self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev = sig, al, alp
         self.ddim_sqrt_one_minus_alphas = np.sqrt(1. - al)
+        # q(x_t | x_0) tables over the DDPM steps (:89-90), read by stochastic_encode(use_original_steps=True): numpy's fp32 sqrt, like the reference's
+        self.sqrt_alphas_cumprod = torch.as_tensor(np.sqrt(ac.numpy()), dtype=torch.float32)
+        self.sqrt_one_minus_alphas_cumprod = torch.as_tensor(np.sqrt(1. - ac.numpy()), dtype=torch.float32)
 
     # ---- UNet with classifier-free guidance ----------------------------------------------
     def _cfg_eps(self, x, t, c, uc, scale, **kwargs):
@@ -175,6 +188,26 @@ class DDIMSampler(object):
             x.numel(), _st()), "moca_ddim_update_f32")
         return x_prev, pred_x0
 
+    def _engine_for(self, img, cond, uc, scale, seed, n_rows, features_adapter=None):
+        """the cached step graph (fifo_graph.BaseEngine) for this call, reset to a new trajectory; built when the key changes.  `n_rows`:
+        the rows of the schedule tables the captured kernels index (all of them for `sample`, the first t_start for `decode`): part of
+        the key, so neither picks up the other's engine"""
+        from .fifo_graph import BaseEngine
+        cu, cn = cond["c_crossattn"], uc["c_crossattn"]
+        key = (tuple(img.shape), sum(c.shape[1] for c in cu), sum(c.shape[1] for c in cn), float(scale),
+               self.ddim_timesteps.tobytes(), np.asarray(self.ddim_sigmas).tobytes(), str(img.device),
+               tuple(int(c.shape[1]) for c in cond.get("c_concat") or ()),
+               None if features_adapter is None else tuple(tuple(f.shape) for f in features_adapter), int(n_rows))
+        if self._base_engine is not None and self._base_engine[0] != key:
+            self._base_engine[1].close()
+            self._base_engine = None
+        if self._base_engine is None:
+            self._base_engine = (key, BaseEngine(self.model, self, img, cond, uc, scale, seed=seed, features_adapter=features_adapter,
+                                                 n_rows=n_rows))
+        else:
+            self._base_engine[1].reset(img, cond, uc, seed, features_adapter=features_adapter)
+        return self._base_engine[1]
+
     def release(self):
         """free the cached step graph of `sample` (plan buffers + hipGraph)"""
         if self._base_engine is not None:
@@ -203,20 +236,8 @@ class DDIMSampler(object):
                                                                          unconditional_guidance_scale, features_adapter=features_adapter):
             # the loop body as one hipGraph per step (fifo_graph.BaseEngine): latents, schedule and noise stay on the device
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())                  # the host generator seeds the device stream
-            cu, cn = conditioning["c_crossattn"], unconditional_conditioning["c_crossattn"]
-            key = (tuple(img.shape), sum(c.shape[1] for c in cu), sum(c.shape[1] for c in cn), float(unconditional_guidance_scale),
-                   self.ddim_timesteps.tobytes(), np.asarray(self.ddim_sigmas).tobytes(), str(img.device),
-                   tuple(int(c.shape[1]) for c in conditioning.get("c_concat") or ()),
-                   None if features_adapter is None else tuple(tuple(f.shape) for f in features_adapter))
-            if self._base_engine is not None and self._base_engine[0] != key:
-                self._base_engine[1].close()
-                self._base_engine = None
-            if self._base_engine is None:
-                self._base_engine = (key, BaseEngine(self.model, self, img, conditioning, unconditional_conditioning,
-                                                     unconditional_guidance_scale, seed=seed, features_adapter=features_adapter))
-            else:
-                self._base_engine[1].reset(img, conditioning, unconditional_conditioning, seed, features_adapter=features_adapter)
-            eng = self._base_engine[1]
+            eng = self._engine_for(img, conditioning, unconditional_conditioning, unconditional_guidance_scale, seed, total_steps,
+                                   features_adapter=features_adapter)
             for i in range(total_steps):
                 eng.step(noise=None if noises is None else noises[i])
             img = eng.latents().to(img.dtype)
@@ -231,6 +252,119 @@ class DDIMSampler(object):
         if latents_dir is not None:
             torch.save(img, f"{latents_dir}/{total_steps}.pt")        # :249-250
         return img, {}
+
+    # ---- start from an existing latent: noise it, denoise it ---------------------------------------------------------------
+    def encode_tables(self, use_original_steps=False):
+        """the two coefficient tables of `stochastic_encode` (ddim.py:655-660) as fp32 host tensors, evaluated as the reference evaluates
+        them: `torch.sqrt(ddim_alphas)` (taken with `sqrt_f32`: the same on every host) and `ddim_sqrt_one_minus_alphas` over the DDIM
+        steps, or the sampler's own 1000-entry `sqrt_alphas_cumprod` / `sqrt_one_minus_alphas_cumprod` (:89-90).  `scale_arr` plays no
+        part, `use_scale` or not."""
+        if use_original_steps:
+            return self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod
+        return (sqrt_f32(np.asarray(self.ddim_alphas)),
+                torch.as_tensor(np.asarray(self.ddim_sqrt_one_minus_alphas), dtype=torch.float32))
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+        """ddim.py:652-671: x_t = a[t_b] x0 + b[t_b] noise per sample b.  `t` [B] holds schedule INDICES (into the DDIM tables, or into
+        the 1000 DDPM steps with `use_original_steps`), on either device: a host tensor is range-checked here (IndexError, as `gather`),
+        a device tensor is gathered by the kernel without a host read (an index out of range gives that sample NaN)."""
+        x0 = _f32c(x0)
+        if not x0.is_cuda:
+            raise ValueError("stochastic_encode runs on the GPU: x0 must be a cuda tensor")
+        ca, cb = self.encode_tables(use_original_steps)
+        t = torch.as_tensor(t)
+        B = x0.shape[0]
+        if t.dim() != 1 or t.shape[0] != B:
+            raise ValueError(f"t must hold one schedule index per sample, shape [{B}], got {tuple(t.shape)}")
+        if not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) >= ca.shape[0]):
+            raise IndexError(f"index {t.tolist()} is out of bounds for the {ca.shape[0]}-entry schedule table")
+        noise = torch.randn_like(x0) if noise is None else _f32c(noise.to(x0.device))                    # :662-663
+        if noise.shape != x0.shape:
+            raise ValueError(f"noise {tuple(noise.shape)} does not match x0 {tuple(x0.shape)}")
+        ca_d, cb_d, t_d = ca.to(x0.device), cb.to(x0.device), t.to(x0.device, torch.int64).contiguous()
+        out = torch.empty_like(x0)
+        _l.check(_l.load().moca_q_sample_f32(_l.ptr(x0), _l.ptr(noise), _l.ptr(out), _l.ptr(ca_d), _l.ptr(cb_d), _l.ptr(t_d), B,
+                                             int(ca.shape[0]), x0.numel() // B, _st()), "moca_q_sample_f32")
+        return out
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
+               use_original_steps=False, noises=None, use_graph=None):
+        """ddim.py:674-692: `t_start` calls of p_sample_ddim (temperature 1, fresh noise per step) over `ddim_timesteps[:t_start]`
+        flipped -- step i at schedule index t_start - 1 - i -- returning the latents only.  `noises[i]` fixes step i's draw; `use_graph`
+        (default: `self.use_graph`) as in `sample`: where `BaseEngine.supported` holds, one hipGraph per step on an engine over the first
+        t_start rows of the schedule tables, else (no guidance pair among the rest) the host-issued p_sample_ddim loop."""
+        if use_original_steps:
+            raise NotImplementedError(
+                "decode(use_original_steps=True) cannot run in the reference: p_sample_ddim reads self.model.ddim_sigmas_for_original_num_steps "
+                "(ddim.py:325), which exists only on the sampler, and self.model.scale_arr_prev (ddim.py:352), which is never registered")
+        timesteps = self.ddim_timesteps[:t_start]                     # :677-678 (numpy slicing: a t_start past the schedule is the whole of it)
+        time_range = np.flip(timesteps)
+        total_steps = timesteps.shape[0]
+        x_dec = x_latent
+        use_graph = self.use_graph if use_graph is None else use_graph
+        from .fifo_graph import BaseEngine
+        if total_steps > 0 and use_graph and self.share_prefix and BaseEngine.supported(
+                self.model, x_dec, cond, unconditional_conditioning, unconditional_guidance_scale):
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            eng = self._engine_for(x_dec, cond, unconditional_conditioning, unconditional_guidance_scale, seed, total_steps)
+            for i in range(total_steps):
+                eng.step(noise=None if noises is None else noises[i])
+            return eng.latents().to(x_latent.dtype)
+        for i, step in enumerate(time_range):
+            index = total_steps - i - 1
+            ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
+            x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
+                                          unconditional_guidance_scale=unconditional_guidance_scale,
+                                          unconditional_conditioning=unconditional_conditioning,
+                                          noise=None if noises is None else noises[i])
+        return x_dec
+
+    @staticmethod
+    def inversion_frame_index(num_inference_steps, n_frames):
+        """ddim.py:1014: the input frame behind output frame i, idx(i) = max(0, i - (num_inference_steps - n_frames))"""
+        return [max(0, i - (num_inference_steps - n_frames)) for i in range(num_inference_steps)]
+
+    @torch.no_grad()
+    def ddim_inversion(self, frames, num_inference_steps, eta=1.0, latents_dir=None, noises=None, anchor_noise=None):
+        """ddim.py:972-1032.  Despite the name a NOISING queue: output frame i = ddim_alphas[i] ** 0.5 * z[:, :, idx(i)] +
+        (1 - ddim_alphas[i]) ** 0.5 * randn with z = encode_first_stage_2DAE(frames) (RGBA cut to RGB, a 3-channel z padded with a zero
+        fourth channel) and idx(i) = max(0, i - (num_inference_steps - T)) -- `prepare_latents` (funcs.py:53-79) without lookahead over
+        this sampler's tables, one `moca_fifo_prepare_queue_f32` launch.  `eta` is unused, as upstream; needs a prior `make_schedule`.
+        `noises[i]` [B,C,1,h,w] fix the per-frame draws, `anchor_noise` [B,4,T,h,w] the VAE posterior draw."""
+        if frames.dim() != 5:
+            raise ValueError(f"Expected frames to have 5 dimensions [B, C, T, H, W], got {frames.dim()}")
+        if frames.shape[1] == 4:                                      # RGBA -> RGB (:990-991)
+            frames = frames[:, :3]
+        kw = {} if anchor_noise is None else {"noise": anchor_noise}
+        latents = self.model.encode_first_stage_2DAE(frames, **kw)
+        if latents.dim() != 5:
+            raise ValueError(f"Expected latents to have 5 dimensions [B, C, T, H, W], got {latents.dim()}")
+        if latents.shape[1] == 3:                                     # :1001-1003
+            latents = torch.cat([latents, torch.zeros_like(latents[:, :1])], dim=1)
+        N = int(num_inference_steps)
+        z = latents.to("cuda", torch.float32).contiguous()
+        b, c, tz, h, w = z.shape
+        alphas = torch.as_tensor(np.asarray(self.ddim_alphas), dtype=torch.float32)[:N]
+        if alphas.shape[0] != N:
+            raise IndexError(f"num_inference_steps = {N} runs past the {alphas.shape[0]}-step schedule (ddim.py:1010)")
+        coef_z, coef_n = sqrt_f32(alphas), sqrt_f32(1 - alphas)       # the 0-dim fp32 tensors alpha ** 0.5, beta ** 0.5 of :1010-1011,1021
+        fidx = torch.tensor(self.inversion_frame_index(N, frames.shape[2]), dtype=torch.int32)
+        if int(fidx.max()) >= tz:
+            raise IndexError(f"frame index {int(fidx.max())} is out of range for {tz} latent frames (ddim.py:1017)")
+        if noises is None:
+            noise = torch.randn(b, c, N, h, w, device=z.device)       # the N torch.randn_like draws of :1020 as one tensor
+        else:
+            noise = torch.cat([n.to(z.device, torch.float32).reshape(b, c, 1, h, w) for n in noises[:N]], dim=2).contiguous()
+        out = torch.empty(b, c, N, h, w, dtype=torch.float32, device=z.device)
+        cz, cn, fi = coef_z.to(z.device), coef_n.to(z.device), fidx.to(z.device)
+        _l.check(_l.load().moca_fifo_prepare_queue_f32(_l.ptr(z), _l.ptr(noise), _l.ptr(out), _l.ptr(cz), _l.ptr(cn), _l.ptr(fi), b * c, tz, N,
+                                                       h * w, _st()), "moca_fifo_prepare_queue_f32")
+        if latents_dir is not None:
+            for i in range(N):
+                torch.save(out[:, :, [i]].clone(), f"{latents_dir}/step_{i}.pt")          # :1024-1025
+        return out
 
     @torch.no_grad()
     def unet_windows(self, windows, c, ts_list, unconditional_guidance_scale=1., unconditional_conditioning=None, **kwargs):
