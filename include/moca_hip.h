@@ -268,7 +268,13 @@ int moca_layernorm_f16(const void* x, void* y, const float* gamma, const float* 
  * row strides ldk, ldv; kv batch index = q batch index / kv_div (cross-attention
  * shares one context per video: openaimodel3d.py:547).  out: [Bq][Nq][ldo].
  * Replaces CrossAttention.forward (attention.py:92-114) in its spatial self /
- * spatial cross roles.                                                           */
+ * spatial cross roles.
+ * Limits (the widest access of the three kernels behind this entry: 16-byte loads
+ * and LDS-DMA of q / k / v, 16-byte stores of out): q, k, v, out 16-byte aligned;
+ * ldq, ldk, ldv, ldo multiples of 8 halves, all >= heads * 64; Bq % kv_div == 0;
+ * Bq * heads <= 65535; (Nk rounded up to 64) * max(ldk, ldv) * 2 bytes < 2^31 (the
+ * long-key kernel addresses one video's K / V by 32-bit byte offsets).
+ * MOCA_E_BADARG otherwise.                                                       */
 int moca_attention_f16(const void* q, const void* k, const void* v, void* out,
                        int32_t Bq, int32_t heads, int32_t Nq, int32_t Nk,
                        int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
@@ -288,7 +294,9 @@ int moca_attention_ip_f16(const void* q, const void* k, const void* v, const voi
                           int32_t kv_div, float scale, float ip_scale, void* stream);
 
 /* Causal self-attention, head dim 64: query i attends to keys 0..i (the text tower of the OpenCLIP encoder,
- * condition.py:205-212: `text_transformer_forward(x, attn_mask=self.model.attn_mask)`); q/k/v/out as above, N = Nq = Nk. */
+ * condition.py:205-212: `text_transformer_forward(x, attn_mask=self.model.attn_mask)`); q/k/v/out as above, N = Nq = Nk.
+ * Limits (16-byte loads, 8-byte stores): q, k, v 16-byte aligned, out 8-byte aligned; ldq, ldk, ldv multiples of 8 and ldo of 4
+ * halves, all >= heads * 64; B * heads <= 65535.  MOCA_E_BADARG otherwise.                                              */
 int moca_attention_causal_f16(const void* q, const void* k, const void* v, void* out,
                               int32_t B, int32_t heads, int32_t N, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
                               float scale, void* stream);
@@ -297,14 +305,17 @@ int moca_attention_causal_f16(const void* q, const void* k, const void* v, void*
  * attend over the T (<=16) frames.  qkv rows are channels-last tokens
  * [(b*T+t)*HW + p][ld]; q/k/v point at their first column.  Replaces
  * CrossAttention.forward inside TemporalTransformer (attention.py:331-352) incl.
- * the (b t) c h w <-> (b h w) t c reshuffles (attention.py:335-338,367).          */
+ * the (b t) c h w <-> (b h w) t c reshuffles (attention.py:335-338,367).
+ * out rows are [(b*T+t)*HW + p][ldo].  Limits (16-byte loads, 8-byte stores):
+ * 1 <= T <= 16; q, k, v 16-byte aligned, out 8-byte aligned; ld_qkv a multiple of
+ * 8 and ldo of 4 halves, both >= heads * 64.  MOCA_E_BADARG otherwise.            */
 int moca_temporal_attention_f16(const void* q, const void* k, const void* v, void* out,
                                 int32_t B, int32_t T, int32_t HW, int32_t heads,
                                 int32_t ld_qkv, int32_t ldo, float scale, void* stream);
 /* The same with the causal mask of TemporalTransformer(causal_attention=True): frame t attends to frames <= t.  Replaces
  * `self.mask = torch.tril(torch.ones([1, temporal_length, temporal_length]))` (attention.py:309-311), its repeat over the
  * (b h w) batch (:342-346) and `sim.masked_fill_(~(mask>0.5), max_neg_value)` in front of the softmax (:101-105, reached
- * through BasicTransformerBlock._forward :217-218 for attn1 AND attn2).  scale > 0.                                          */
+ * through BasicTransformerBlock._forward :217-218 for attn1 AND attn2).  scale > 0; the other limits as above.               */
 int moca_temporal_attention_causal_f16(const void* q, const void* k, const void* v, void* out,
                                        int32_t B, int32_t T, int32_t HW, int32_t heads,
                                        int32_t ld_qkv, int32_t ldo, float scale, void* stream);

@@ -795,6 +795,10 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(
     }
 }
 
+// Entry checks follow the widest access a kernel makes on an operand: 16-byte loads / LDS-DMA on q, k, v everywhere; 16-byte row
+// stores of `out` in the short and long-key kernels, 8-byte stores in attention_kernel and the temporal kernel.
+inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+
 template <bool IP>
 void launch_short(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* out, int Bq, int heads, int Nq,
                   int Nt, int Nk, int ldq, int ldk, int ldv, int ldk_ip, int ldv_ip, int ldo, int kv_div, float scale, float ip_scale,
@@ -821,9 +825,13 @@ extern "C" int moca_attention_f16(const void* q, const void* k, const void* v, v
                                   int32_t kv_div, float scale, void* stream) {
     if (!q || !k || !v || !out) return MOCA_E_BADARG;
     if (Bq <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0 || kv_div <= 0 || Bq % kv_div) return MOCA_E_BADARG;
-    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4) return MOCA_E_BADARG;
+    // the short and the long-key kernel store whole 16-byte pieces of an output row: ldo % 8 and a 16-byte aligned `out` on every route
+    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(out, 16)) return MOCA_E_BADARG;
+    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) return MOCA_E_BADARG;
     if (ldq < heads * D || ldk < heads * D || ldv < heads * D || ldo < heads * D) return MOCA_E_BADARG;
     if ((int64_t)Bq * heads > 65535) return MOCA_E_BADARG;
+    // the long-key kernel addresses K and V of one video by 32-bit byte offsets (buffer descriptor, whole 64-key tiles)
+    if (((int64_t)Nk + KT - 1) / KT * KT * (ldk > ldv ? ldk : ldv) * 2 > INT32_MAX) return MOCA_E_BADARG;
     const dim3 grid((Nq + QB - 1) / QB, Bq * heads), block(256);
     if (Nk >= 2 * KT) {
         // (an 8-wave form, 256 queries per block, measured -2.8 % at 2560 tokens in isolation and -0.1 % on the whole step in round 2:
@@ -852,9 +860,9 @@ extern "C" int moca_attention_ip_f16(const void* q, const void* k, const void* v
                                      int32_t Bq, int32_t heads, int32_t Nq, int32_t Nt, int32_t Ni,
                                      int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldk_ip, int32_t ldv_ip, int32_t ldo,
                                      int32_t kv_div, float scale, float ip_scale, void* stream) {
-    auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
     if (!q || !k || !v || !k_ip || !v_ip || !out) return MOCA_E_BADARG;
-    if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(k_ip) || misaligned(v_ip) || misaligned(out)) return MOCA_E_BADARG;
+    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(k_ip, 16) || misaligned(v_ip, 16) || misaligned(out, 16))
+        return MOCA_E_BADARG;
     if (Bq <= 0 || heads <= 0 || Nq <= 0 || Nt < 1 || Ni < 0 || Nt + Ni > KS96 || kv_div <= 0 || Bq % kv_div) return MOCA_E_BADARG;
     if (Ni > 0 && (Nt > IP_ROW0 || Ni > KS96 - IP_ROW0)) return MOCA_E_BADARG;     // the fixed text / image rows of the tile
     if (ldq % 8 || ldk % 8 || ldv % 8 || ldk_ip % 8 || ldv_ip % 8 || ldo % 8) return MOCA_E_BADARG;
@@ -875,6 +883,7 @@ extern "C" int moca_attention_causal_f16(const void* q, const void* k, const voi
                                          int32_t B, int32_t heads, int32_t N, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
                                          float scale, void* stream) {
     if (!q || !k || !v || !out || B <= 0 || heads <= 0 || N <= 0) return MOCA_E_BADARG;
+    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(out, 8)) return MOCA_E_BADARG;   // attention_kernel: 8-byte stores
     if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4) return MOCA_E_BADARG;
     if (ldq < heads * D || ldk < heads * D || ldv < heads * D || ldo < heads * D) return MOCA_E_BADARG;
     if ((int64_t)B * heads > 65535) return MOCA_E_BADARG;
@@ -891,6 +900,7 @@ static int launch_temporal_attention(bool causal, const void* q, const void* k, 
                                      int32_t heads, int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
     if (!q || !k || !v || !out) return MOCA_E_BADARG;
     if (B <= 0 || T <= 0 || T > 16 || HW <= 0 || heads <= 0) return MOCA_E_BADARG;
+    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(out, 8)) return MOCA_E_BADARG;   // 16-byte loads, 8-byte stores
     if (ld_qkv % 8 || ldo % 4 || ld_qkv < heads * D || ldo < heads * D) return MOCA_E_BADARG;
     const int64_t total = (int64_t)B * HW * heads;
     const dim3 grid((unsigned)((total + 3) / 4)), block(256);

@@ -83,6 +83,52 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert l.moca_groupnorm_ws_bytes(16, 2560, 320) > 0
     with pytest.raises(lib.MocaHipError):
         lib.check(-1, "x")
+    # attention entries: the checks follow the widest access of the kernels on each operand (include/moca_hip.h).  Every call below
+    # differs from an acceptable one (fake 4 KiB-aligned pointers, C = 2 heads x 64) in exactly the named argument and must return
+    # before any launch.
+    P = lambda off=0: C.c_void_p(0x10000 + off)
+    Cc = 128
+
+    def attn(q=P(), k=P(), v=P(), out=P(), Bq=4, heads=2, Nq=130, Nk=77, ldq=Cc, ldk=Cc, ldv=Cc, ldo=Cc, kv_div=2, scale=0.125):
+        return l.moca_attention_f16(q, k, v, out, Bq, heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale, None)
+
+    def attn_ip(q=P(), k=P(), v=P(), ki=P(), vi=P(), out=P(), Bq=4, heads=2, ldo=Cc, kv_div=2):
+        return l.moca_attention_ip_f16(q, k, v, ki, vi, out, Bq, heads, 130, 77, 16, Cc, Cc, Cc, Cc, Cc, ldo, kv_div, 0.125, 1.0, None)
+
+    def causal(q=P(), k=P(), v=P(), out=P(), B=2, heads=2, ldq=Cc, ldo=Cc):
+        return l.moca_attention_causal_f16(q, k, v, out, B, heads, 77, ldq, Cc, Cc, ldo, 0.125, None)
+
+    def temporal(fn, q=P(), k=P(), v=P(), out=P(), T=16, ld=3 * Cc, ldo=Cc, scale=0.125):
+        return fn(q, k, v, out, 1, T, 4, 2, ld, ldo, scale, None)
+
+    def d80(q=P(), k=P(), v=P(), out=P(), B=2, heads=2, ldo=160):
+        return l.moca_attention_d80_f16(q, k, v, out, B, heads, 257, 480, 480, 480, ldo, 80 ** -0.5, None)
+
+    for Nk in (77, 120, 200):                                      # short, generic and long-key route alike: 16-byte row stores
+        assert attn(Nk=Nk, ldo=Cc + 4) == -1
+        for name in ("q", "k", "v", "out"):
+            assert attn(Nk=Nk, **{name: P(8)}) == -1, (Nk, name)
+    assert attn(ldq=Cc + 4) == -1 and attn(ldk=Cc + 4) == -1 and attn(ldv=Cc + 4) == -1
+    assert attn(Bq=3) == -1 and attn(Bq=65536, heads=1, kv_div=1) == -1 and attn(Bq=32768, heads=2, kv_div=1) == -1
+    assert attn(Nk=1 << 20, ldk=4096) == -1 and attn(Nk=1 << 20, ldv=4096) == -1          # 2^33-byte offsets would wrap
+    assert attn(Nk=(1 << 18) - 63, ldk=4096) == -1                                        # the last whole 64-key tile ends at 2^31
+    assert attn_ip(ldo=Cc + 4) == -1 and attn_ip(Bq=3) == -1 and attn_ip(Bq=32768, kv_div=1) == -1
+    for name in ("q", "k", "v", "ki", "vi", "out"):
+        assert attn_ip(**{name: P(8)}) == -1, name
+    for name in ("q", "k", "v"):
+        assert causal(**{name: P(8)}) == -1, name
+    assert causal(out=P(4)) == -1 and causal(ldo=Cc + 2) == -1 and causal(ldq=Cc + 4) == -1       # 8-byte stores: ldo % 4, out % 8
+    assert causal(B=32768) == -1
+    for fn in (l.moca_temporal_attention_f16, l.moca_temporal_attention_causal_f16):
+        assert temporal(fn, T=0) == -1 and temporal(fn, T=17) == -1
+        for name in ("q", "k", "v"):
+            assert temporal(fn, **{name: P(8)}) == -1, name
+        assert temporal(fn, out=P(4)) == -1 and temporal(fn, ldo=Cc + 2) == -1 and temporal(fn, ld=3 * Cc + 4) == -1
+    assert temporal(l.moca_temporal_attention_causal_f16, scale=0.0) == -1
+    assert temporal(l.moca_temporal_attention_causal_f16, scale=-0.125) == -1
+    for name in ("q", "k", "v"):
+        assert d80(**{name: P(8)}) == -1, name
+    assert d80(out=P(4)) == -1 and d80(ldo=162) == -1 and d80(B=32768) == -1
 
 
 def test_unet_state_dict_surface_matches_reference_counts():
