@@ -1,0 +1,376 @@
+"""Operands, route table and float64 torch restatements for tests/test_gemm_edges_gpu.py and tests/test_gemm_edges_cpu.py.
+
+Every reference works on the fp16-rounded operands it is handed and returns float64 [M][N]; the metric is taken per block of 64
+output rows so that a wrong tile cannot hide under another tile's maximum.  Nothing here touches a GPU by itself: the builders make
+their tensors on the CPU from a seeded generator and the caller moves them."""
+import torch
+import torch.nn.functional as F
+
+from moca_video_amd import lib as L
+
+TOL16 = 3e-3                    # tests/test_kernels_gpu.py: one fp16-output kernel against torch on the same fp16 operands
+TOL32 = 1e-3                    # tests/test_kernels_gpu.py::test_gemm_rowadd_f32out
+NAN = float("nan")
+BK = 64                         # k-tile depth of every kernel (csrc/gemm.hip)
+
+
+def gen(seed):
+    return torch.Generator(device="cpu").manual_seed(seed)
+
+
+def randh(g, *shape, scale=1.0):
+    return (torch.randn(*shape, generator=g) * scale).half()
+
+
+# ---------------------------------------------------------------- route table
+W80, G4, SQ256, WIDE, G4P, MF32, SQP, WS = (L.MOCA_TUNE_GEMM_W80, L.MOCA_TUNE_GEMM_G4, L.MOCA_TUNE_GEMM_SQ256, L.MOCA_TUNE_GEMM_WIDE,
+                                            L.MOCA_TUNE_GEMM_G4P, L.MOCA_TUNE_GEMM_MF32, L.MOCA_TUNE_GEMM_SQP, L.MOCA_TUNE_GEMM_WS)
+_M_SMALL, _M_256, _M_320 = (1, 77, 128, 300), (129, 256, 257, 513), (161, 320, 321, 641)
+# name -> knobs; N = the column count that selects the instantiation, N2 = a second one with more column tiles (5 x 64, 5 x 128, 6 x 160,
+# 2 x 320: a wrong column-tile offset of bias / row add / residual, or a store from column tile > 0, shows only there); the M set (one
+# full tile, an off-by-one tail, two tiles); the gather modes / paths the route has; its signature = (gemm_colsum_rows, gemm_rowsum_cols,
+# gemm_lnfold_ok) of a plain linear on it.  The entry needs N % 64 == 0, so 160 and 480 cannot be launched: the 160-column tiles are
+# reached at N = 320 (two tiles) and at 960, the next width that is a multiple of 160 and 64 but not of 128.
+# The small kernels take M > 128 only with MOCA_FORCE_SMALL_TILE (needs_force_small).
+ROUTES = {
+    "small64": dict(knobs={WS: 0}, N=64, N2=320, M=_M_SMALL, conv=True, slow=True, sig=(0, 0, False)),
+    "small128": dict(knobs={WS: 0}, N=128, N2=640, M=_M_SMALL, conv=True, slow=True, sig=(0, 0, False)),
+    "glds128": dict(knobs={W80: 0, G4: 0, WS: 0}, N=128, N2=640, M=_M_256, conv=True, slow=True, sig=(256, 128, True)),
+    "glds160": dict(knobs={W80: 0, G4: 0, WS: 0}, N=320, N2=960, M=_M_256, conv=True, slow=True, sig=(256, 160, True)),
+    "g4": dict(knobs={W80: 0, G4: 2, WS: 0}, N=128, N2=640, M=_M_256, conv=True, slow=True, sig=(0, 0, True)),
+    "w80": dict(knobs={W80: 2, WIDE: 0, WS: 0}, N=320, N2=960, M=_M_320, conv=True, slow=False, sig=(320, 160, True)),
+    "w80w": dict(knobs={W80: 2, WIDE: 2, WS: 0}, N=320, N2=640, M=_M_320, conv=True, slow=False, sig=(160, 320, True)),
+    # the weight-stationary kernel: N = K = 320, M % 32 == 0, M >= 8192 (M = 32 is the documented fall-through to the small kernel).
+    # Its signature is asked WITH MOCA_EP_GSTAT (strips of 32 rows); one row partial per wave of 80 columns.
+    "ws": dict(knobs={WS: 2}, N=320, K=320, M=(8192 + 32,), conv=False, slow=False, sig=(32, 80, None)),
+}
+BIG_ROUTES = ("glds128", "glds160", "g4", "w80", "w80w")
+CONV_ROUTES = ("small64", "small128") + BIG_ROUTES
+SPLIT_ROUTES = ("small128", "glds128", "glds160", "g4", "w80", "w80w")
+# the persistent kernels (tests/test_kernels_gpu.py::test_gemm_g4p / test_gemm_sq256): knobs and the smallest tile counts they take
+PERSISTENT = {
+    "g4p": dict(knobs={SQP: 0, G4P: 2, MF32: 0, WS: 0}, tile=(256, 128), min_tiles=512),
+    "g4q": dict(knobs={SQP: 0, G4P: 2, MF32: 1, WS: 0}, tile=(256, 128), min_tiles=512),
+    "sqp": dict(knobs={SQP: 2, G4P: 0, WS: 0}, tile=(256, 256), min_tiles=256),
+    "sq256": dict(knobs={SQ256: 2, SQP: 0, G4P: 0, WS: 0}, tile=(256, 256), min_tiles=200),
+}
+# (M, N, K) per persistent kernel: the existing tests' minimum tile counts with an M tail, K = 64
+PERSISTENT_SHAPE = {"g4p": (8200, 2048, 64), "g4q": (8200, 2048, 64), "sqp": (8200, 2048, 64), "sq256": (4100, 3072, 64)}
+# (k-tiles, requested splits) -> the factor normalise_splits leaves
+SPLIT_CASES = {(5, 4): 3, (3, 8): 3, (2, 2): 2, (7, 3): 3}
+
+
+FAST_KS, SLOW_KS = (64, 192), (8, 72, 328)
+
+
+def route_Ns(route):
+    spec = ROUTES[route]
+    return (spec["N"],) + ((spec["N2"],) if "N2" in spec else ())
+
+
+def route_Ks(route):
+    spec = ROUTES[route]
+    return (spec["K"],) if "K" in spec else FAST_KS + (SLOW_KS if spec["slow"] else ())
+
+
+def persistent_ok(name, M, N, K, lda, *, geglu=False, residual=False, rowadd=False, splits=1, other_flags=False):
+    """g4p_ok / sqp_ok / takes_sq256 of csrc/gemm.hip restated.  No host query tells a persistent kernel from the kernel the call would
+    fall to (both carry the LayerNorm fold, neither column sums on the persistent side), so the GPU file asserts the preconditions."""
+    tm, tn = PERSISTENT[name]["tile"]
+    if splits != 1 or other_flags or K % 64 or N % tn or a_span_bytes_linear(M, lda) >= 1 << 31 or N * ((K + 63) // 64 * 64) * 2 >= 1 << 31:
+        return False
+    if name == "sq256":
+        return N >= 2560 and M >= 512 and persistent_tiles(name, M, N) >= 200 and not (N % 160 == 0 and not geglu)
+    if geglu and (residual or rowadd):
+        return False
+    return persistent_tiles(name, M, N) >= PERSISTENT[name]["min_tiles"]
+
+
+def persistent_tiles(name, M, N):
+    tm, tn = PERSISTENT[name]["tile"]
+    return ((M + tm - 1) // tm) * (N // tn)
+
+
+def needs_force_small(route, M):
+    return route.startswith("small") and M > 128
+
+
+def normalise_splits(K, splits):
+    """csrc/gemm.hip normalise_splits: no more splits than k-tiles, then no empty k range"""
+    nkt = (K + BK - 1) // BK
+    s = max(1, min(splits, nkt))
+    if s > 1:
+        kts = (nkt + s - 1) // s
+        s = (nkt + kts - 1) // kts
+    return s
+
+
+def a_span_bytes_linear(M, lda):
+    """csrc/gemm.hip a_span_bytes (MOCA_A_LINEAR): the buffer-addressed kernels need it below 2^31"""
+    return (M * lda + 64) * 2
+
+
+def lda_at_span_limit(M):
+    """smallest lda % 8 == 0 whose span reaches 2^31 bytes"""
+    lda = ((1 << 30) - 64 + M - 1) // M
+    lda = (lda + 7) // 8 * 8
+    assert a_span_bytes_linear(M, lda) >= 1 << 31 and a_span_bytes_linear(M, lda - 8) < 1 << 31
+    return lda
+
+
+# ---------------------------------------------------------------- references (float64)
+def gelu64(x):
+    return 0.5 * x * (1.0 + torch.erf(x * 0.7071067811865476))
+
+
+def ref_linear(a, w):
+    return a.double() @ w.double().T
+
+
+def ref_conv(x, w, stride=1, up=0, nopad=0, wrong=None):
+    """x [Fr][H][W][C] channels-last, w [N][C][3][3] -> [Fr oH oW][N].  `wrong` selects one deliberately wrong restatement."""
+    xi = x.double().permute(0, 3, 1, 2)
+    if up:
+        if wrong == "up_axis":                                      # halved along x only: rows taken modulo H
+            H2, W2 = 2 * xi.shape[2], 2 * xi.shape[3]
+            xi = xi[:, :, torch.arange(H2) % xi.shape[2]][:, :, :, torch.arange(W2) // 2]
+        else:
+            xi = F.interpolate(xi, scale_factor=2, mode="nearest")
+    if wrong == "s2_offset":                                        # samples 2o + 1 instead of 2o
+        xi = F.pad(xi, (0, 1, 0, 1))[:, :, 1:, 1:]
+    if nopad and wrong != "sym_pad":
+        y = F.conv2d(F.pad(xi, (0, 1, 0, 1)), w.double(), stride=stride, padding=0)
+    else:
+        y = F.conv2d(xi, w.double(), stride=stride, padding=1)
+    return y.permute(0, 2, 3, 1).reshape(-1, w.shape[0])
+
+
+def ref_tconv(x, w, wrong=None):
+    """x [B][T][HW][C], w [N][C][3][1][1] -> [B T HW][N]"""
+    B, T, HW, C = x.shape
+    xi = x.double().permute(0, 3, 1, 2)[..., None]                  # [B][C][T][HW][1]
+    if wrong == "video_boundary":                                   # one long clip: frames leak across videos
+        xi = xi.permute(1, 0, 2, 3, 4).reshape(1, C, B * T, HW, 1)
+    y = F.conv3d(xi, w.double(), padding=(1, 0, 0))
+    if wrong == "video_boundary":
+        y = y.reshape(w.shape[0], B, T, HW, 1).permute(1, 0, 2, 3, 4)
+    return y.permute(0, 2, 3, 4, 1).reshape(B * T * HW, w.shape[0])
+
+
+def epilogue(y, bias=None, rowadd=None, rowadd_div=1, residual=None, act=None, wrong=None):
+    """include/moca_hip.h: bias, row add, residual, then GEGLU (value columns first, gate columns second) / GELU"""
+    M = y.shape[0]
+    if bias is not None:
+        y = y + bias.double()
+    if rowadd is not None:
+        idx = torch.arange(M) + (1 if wrong == "rowadd_row" else 0)
+        y = y + rowadd.double()[(idx // rowadd_div).clamp_max(rowadd.shape[0] - 1)]
+    if residual is not None:
+        y = y + residual.double()
+    if act == "geglu":
+        inner = y.shape[1] // 2
+        y = y[:, :inner] * gelu64(y[:, inner:])
+    elif act == "gelu":
+        y = gelu64(y)
+    return y
+
+
+# ---------------------------------------------------------------- metric
+def block_errors(got, ref, rows=64):
+    """max|got - ref| over each block of `rows` output rows / max|ref| of that block -> [ceil(M / rows)]"""
+    g, r = got.double().cpu(), ref.double().cpu()
+    M = r.shape[0]
+    nb = (M + rows - 1) // rows
+    d = F.pad((g - r).abs().amax(1), (0, nb * rows - M)).view(nb, rows).amax(1)
+    m = F.pad(r.abs().amax(1), (0, nb * rows - M)).view(nb, rows).amax(1)
+    return d / m.clamp_min(1e-30)
+
+
+WORST = {}                      # group -> worst block error seen (printed by the GPU tests)
+
+
+def check_blocks(got, ref, what, tol=TOL16, group=None):
+    assert torch.isfinite(got.float()).all(), f"{what}: non-finite output"
+    e = block_errors(got, ref)
+    worst = e.max().item()
+    if group is not None:
+        WORST[group] = max(WORST.get(group, 0.0), worst)
+    print(f"[parity] {what}: worst 64-row block {worst:.2e} of its max|ref| (bound {tol:.1e})")
+    assert worst <= tol, f"{what}: block errors {[f'{v:.1e}' for v in e.tolist()]}"
+    return worst
+
+
+# ---------------------------------------------------------------- geometry cases of group A
+# name -> kind, source grid, gather parameters.  M spans two row tiles with a tail on every route (330 .. 396 rows).
+GEOS = {
+    "s1": dict(kind="conv", Fr=3, H=10, W=12, stride=1, up=0, nopad=0),
+    "s2_odd": dict(kind="conv", Fr=11, H=9, W=11, stride=2, up=0, nopad=0),
+    "s2_even": dict(kind="conv", Fr=11, H=10, W=12, stride=2, up=0, nopad=0),
+    "s2_nopad": dict(kind="conv", Fr=11, H=10, W=12, stride=2, up=0, nopad=1),
+    "up": dict(kind="conv", Fr=3, H=5, W=6, stride=1, up=1, nopad=0),
+    "t1": dict(kind="tconv", B=3, T=1, HW=107),
+    "t2": dict(kind="tconv", B=3, T=2, HW=55),
+    "t3": dict(kind="tconv", B=3, T=3, HW=37),
+    "t16": dict(kind="tconv", B=3, T=16, HW=7),
+}
+PHASE_GEO = dict(kind="conv", Fr=4, H=9, W=11, stride=1, up=0, nopad=0)      # up_phase 1..4: the low-resolution grid
+# the wrong restatements that apply to a geometry (tests/test_gemm_edges_cpu.py: each must exceed TOL16 at the case's shape and seed)
+def wrongs_of(geo):
+    out = ["rowadd_row"]
+    if geo["kind"] == "tconv":
+        return out + ["video_boundary"]
+    if geo["nopad"]:
+        out.append("sym_pad")
+    if geo["stride"] == 2:
+        out.append("s2_offset")
+    if geo["up"]:
+        out.append("up_axis")
+    return out
+
+
+def geo_seed(name):
+    return 7000 + 13 * list(GEOS).index(name)
+
+
+def geo_out(geo):
+    """(outH, outW) of a conv geometry"""
+    if geo["up"]:
+        return 2 * geo["H"], 2 * geo["W"]
+    if geo["stride"] == 2:
+        return (geo["H"] - 1) // 2 + 1, (geo["W"] - 1) // 2 + 1
+    return geo["H"], geo["W"]
+
+
+def geo_M(geo):
+    if geo["kind"] == "tconv":
+        return geo["B"] * geo["T"] * geo["HW"]
+    oh, ow = geo_out(geo)
+    return geo["Fr"] * oh * ow
+
+
+def geo_rowadd_div(geo):
+    """one row-add row per frame: the time embedding of a ResBlock conv"""
+    return geo["HW"] if geo["kind"] == "tconv" else geo_out(geo)[0] * geo_out(geo)[1]
+
+
+def geo_source(geo, C):
+    return (geo["B"], geo["T"], geo["HW"], C) if geo["kind"] == "tconv" else (geo["Fr"], geo["H"], geo["W"], C)
+
+
+def geo_ref(geo, x, w, wrong=None):
+    if geo["kind"] == "tconv":
+        return ref_tconv(x, w, wrong)
+    return ref_conv(x, w, geo["stride"], geo["up"], geo["nopad"], wrong)
+
+
+def probe_case(geo, C, N):
+    """Index probe: source pixel i carries the code 1 + i (<= 2048: exact in fp16) in channel 0, zeros elsewhere; output column n has a
+    single 1.0 at tap n % taps, channel 0.  Returns (x, w, expected [M][N] float64): the shifted, zero-padded code image."""
+    shape = geo_source(geo, C)
+    npix = shape[0] * shape[1] * shape[2]
+    assert npix <= 2047
+    x = torch.zeros(shape, dtype=torch.float16)
+    x[..., 0] = (torch.arange(npix) + 1).reshape(shape[:3]).half()
+    if geo["kind"] == "tconv":
+        w = torch.zeros(N, C, 3, 1, 1, dtype=torch.float16)
+        w[torch.arange(N), 0, torch.arange(N) % 3, 0, 0] = 1.0
+    else:
+        w = torch.zeros(N, C, 3, 3, dtype=torch.float16)
+        w[torch.arange(N), 0, (torch.arange(N) % 9) // 3, torch.arange(N) % 3] = 1.0
+    return x, w, geo_ref(geo, x, w)
+
+
+def phase_probe_case(geo, C, N, phase):
+    """The same probe for up_phase = 1 + 2a + b: packed weights [N][(r, s, c)] with a single 1.0 at tap n % 4; expected
+    out[f][2i + a][2j + b][n] = in[f][i + a - 1 + r][j + b - 1 + s], zero padded (include/moca_hip.h).  Returns (x, w2d [N][4C],
+    expected [Fr][H][W][N] float64 = the rows this phase writes)."""
+    a, b = (phase - 1) >> 1, (phase - 1) & 1
+    Fr, H, W = geo["Fr"], geo["H"], geo["W"]
+    x = torch.zeros(Fr, H, W, C, dtype=torch.float16)
+    x[..., 0] = (torch.arange(Fr * H * W) + 1).reshape(Fr, H, W).half()
+    w = torch.zeros(N, 2, 2, C, dtype=torch.float16)
+    n = torch.arange(N)
+    w[n, (n % 4) >> 1, n % 4 & 1, 0] = 1.0
+    xp = F.pad(x[..., 0].double(), (1, 1, 1, 1))
+    exp = torch.stack([xp[:, a + (t >> 1):a + (t >> 1) + H, b + (t & 1):b + (t & 1) + W] for t in range(4)], -1)[..., n % 4]
+    return x, w.reshape(N, 4 * C), exp
+
+
+def ref_phase(x, w2d, phase):
+    """float64 restatement of one up_phase launch from the PACKED fp16 rows w2d [N][(r, s, c)] -> [Fr][H][W][N]"""
+    a, b = (phase - 1) >> 1, (phase - 1) & 1
+    N, C = w2d.shape[0], x.shape[-1]
+    k = w2d.double().view(N, 2, 2, C).permute(0, 3, 1, 2)
+    xp = F.pad(x.double().permute(0, 3, 1, 2), (1 - b, b, 1 - a, a))
+    return F.conv2d(xp, k).permute(0, 2, 3, 1)
+
+
+def random_geo_case(geo, C, N, seed, wrong=None):
+    """Random operands for a geometry: unit x, w of scale K^-1/2, bias / per-frame row add / residual of scale 1.
+    Returns dict(x, w, bias, rowadd, div, res, ref)."""
+    g = gen(seed)
+    M, div = geo_M(geo), geo_rowadd_div(geo)
+    x = randh(g, *geo_source(geo, C))
+    taps = 3 if geo["kind"] == "tconv" else 9
+    w = randh(g, N, C, *((3, 1, 1) if taps == 3 else (3, 3)), scale=(taps * C) ** -0.5)
+    bias = torch.randn(N, generator=g)
+    ra, res = randh(g, M // div, N), randh(g, M, N)
+    geo_wrong = wrong if wrong != "rowadd_row" else None
+    ref = epilogue(geo_ref(geo, x, w, geo_wrong), bias, ra, div, res, wrong=wrong)
+    return dict(x=x, w=w, bias=bias, rowadd=ra, div=div, res=res, ref=ref, M=M)
+
+
+def linear_case(seed, M, N, K, bias=True, rowadd_div=0, residual=False, act=None):
+    """Random linear: unit a, w of scale K^-1/2, bias / row add / residual of scale 1 (dropping or misplacing one is an O(1) error).
+    GEGLU: w is [2 inner][K] (value rows, then gate rows), N = 2 inner.  Returns dict(a, w, bias, rowadd, div, res, ref, M)."""
+    g = gen(seed)
+    a, w = randh(g, M, K), randh(g, N, K, scale=K ** -0.5)
+    b = torch.randn(N, generator=g) if bias else None
+    ra = randh(g, (M + rowadd_div - 1) // rowadd_div, N) if rowadd_div else None
+    res = randh(g, M, N) if residual else None
+    ref = epilogue(ref_linear(a, w), b, ra, max(rowadd_div, 1), res, act)
+    return dict(a=a, w=w, bias=b, rowadd=ra, div=max(rowadd_div, 1), res=res, ref=ref, M=M)
+
+
+# ---------------------------------------------------------------- layouts
+def embed(t, pad=8, guard=1, fill=NAN, dev="cpu", dtype=None):
+    """[rows][cols] -> a [guard + rows + guard][cols + pad] buffer filled with `fill`, the data at row `guard`, column 0.
+    Returns (buffer, view [rows][cols])."""
+    rows, cols = t.shape
+    buf = torch.full((rows + 2 * guard, cols + pad), fill, dtype=dtype or t.dtype)
+    buf[guard:guard + rows, :cols] = t
+    buf = buf.to(dev)
+    return buf, buf[guard:guard + rows, :cols]
+
+
+def canary_out(rows, cols, dev, pad=8, guard=1, dtype=torch.float16):
+    buf = torch.full((rows + 2 * guard, cols + pad), NAN, dtype=dtype, device=dev)
+    return buf, buf[guard:guard + rows, :cols]
+
+
+def assert_canary(buf, rows, cols, what, guard=1):
+    assert torch.isnan(buf[:guard]).all(), f"{what}: a store landed in the guard rows before the output"
+    assert torch.isnan(buf[guard + rows:]).all(), f"{what}: a store landed in the guard rows after the output"
+    assert torch.isnan(buf[guard:guard + rows, cols:]).all(), f"{what}: a store landed in the pad columns"
+
+
+# ---------------------------------------------------------------- host queries (no device: they read pointers, never memory)
+def signature(route, a, pw, **kw):
+    """(gemm_colsum_rows, gemm_rowsum_cols, gemm_lnfold_ok) of this call under the knobs in force; the weight-stationary route asks
+    the column statistics WITH MOCA_EP_GSTAT (one statistics group per 32-row strip), as its kernel has no other form"""
+    from moca_video_amd import ops
+    kw = {k: v for k, v in kw.items() if k not in ("colsum", "rowsum", "gstat", "prefetch")}
+    if route == "ws":
+        gst = torch.empty(1, dtype=torch.int64)
+        return ops.gemm_colsum_rows(a, pw, gstat=(gst, 32), **kw), ops.gemm_rowsum_cols(a, pw, rowsum=True, **kw), None
+    linear = kw.get("mode", L.MOCA_A_LINEAR) == L.MOCA_A_LINEAR
+    return (ops.gemm_colsum_rows(a, pw, **kw), ops.gemm_rowsum_cols(a, pw, rowsum=True, **kw),
+            ops.gemm_lnfold_ok(a, pw, lnfold=(None, 1, 1e-5), **kw) if linear else None)
+
+
+def expected_signature(route, *, linear=True, plain=True):
+    """the route's signature for a call whose epilogue can carry the statistics (`plain`: fp16 output, no split-K, no GEGLU / GELU)"""
+    cs, rs, lf = ROUTES[route]["sig"]
+    if not plain:
+        cs, rs, lf = 0, 0, lf
+    return cs, rs, (lf if linear else None)
