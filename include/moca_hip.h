@@ -186,6 +186,21 @@ int moca_gemm_wgroup_ok(const moca_gemm_params* p);
 /* 1 when this call (a2 / lda2 / k1 set) can read its A operand from two sources (see moca_gemm_params.a2); else 0 (the caller
  * then materialises the concat with moca_concat_channels*_f16).                                                          */
 int moca_gemm_cat_ok(const moca_gemm_params* p);
+/* The kernel family moca_gemm_f16 would run this call on (MOCA_ROUTE_*), or 0 where it would return MOCA_E_BADARG: everything
+ * moca_gemm_f16 does up to, but not including, the launch.  The queries above answer from the same decision.               */
+#define MOCA_ROUTE_SMALL64   1   /* 128 x 64 tiles, register-staged (any M, N % 64 == 0)                    */
+#define MOCA_ROUTE_SMALL128  2   /* 128 x 128 tiles, register-staged                                        */
+#define MOCA_ROUTE_GLDS128   3   /* 256 x 128 tiles, direct-to-LDS, 8 waves                                 */
+#define MOCA_ROUTE_GLDS160   4   /* 256 x 160 tiles, direct-to-LDS, 8 waves                                 */
+#define MOCA_ROUTE_G4        5   /* 256 x 128 tiles, 4 waves, two blocks per CU                             */
+#define MOCA_ROUTE_W80       6   /* staggered kernel, 320 x 160 tiles                                       */
+#define MOCA_ROUTE_W80W      7   /* staggered kernel, 160 x 320 tiles                                       */
+#define MOCA_ROUTE_SQ256     8   /* staggered kernel, 256 x 256 tiles                                       */
+#define MOCA_ROUTE_G4P       9   /* persistent 256 x 128 kernel (either MFMA shape)                         */
+#define MOCA_ROUTE_SQP       10  /* persistent 256 x 256 kernel                                             */
+#define MOCA_ROUTE_TATTN     11  /* staggered kernel, 320 x 192 tiles, temporal attention in the epilogue   */
+#define MOCA_ROUTE_WS        12  /* weight-stationary streaming kernel (320 -> 320 linears)                 */
+int moca_gemm_route(const moca_gemm_params* p);
 /* The split-K reduce of a MOCA_EP_SLABS call AND the GroupNorm(32)(+SiLU) that consumes its output (openaimodel3d.py:149-153,173-178,
  * 252-263 at the 5 x 8-latent level, where every conv runs split-K) in one launch: x = fp16(sum of slabs + bias + row add + residual)
  * exactly as moca_gemm_f16 would have stored it, y [M][N] = GroupNorm(x) over frames_per_stat frames of HW rows; x itself is written to

@@ -7,14 +7,23 @@
 // all nn.Linear layers; the A operand is gathered on the fly from channels-last fp16
 // activations ([frame][y][x][c]), so no im2col buffer and no layout shuffles exist.
 //
-// Tiling (CDNA4): 256 threads = 4 wavefronts (2 x 2), block tile 128 x BN x 64
-// (BN = 128 or 64), each wave owns a 64 x BN/2 sub-tile as 2 x (BN/64)
-// v_mfma_f32_32x32x16_f16 accumulators.  A/B k-tiles are staged through registers
-// (the gather needs zero fill) into double-buffered LDS with 128-byte rows and an
-// XOR swizzle on the 16-byte chunk index (chunk ^ ((row>>1)&7)) so that the
-// ds_read_b128 fragment reads are bank-conflict free.  The epilogue goes through an
-// fp32 LDS tile so that bias / time-embedding / residual are applied in fp32 and the
-// result leaves as full 16-byte coalesced stores.
+// The kernels (k-tiles of 64 everywhere; which one runs a call: route_of() at the tail of this file):
+//   gemm_f16_kernel<BN, AMODE>      128 x BN (BN = 128 or 64), 4 waves (2 x 2) of 2 x (BN/64) v_mfma_f32_32x32x16_f16
+//                                   accumulators.  A/B k-tiles are staged through registers (the gather needs zero fill) into
+//                                   double-buffered LDS with 128-byte rows and an XOR swizzle on the 16-byte chunk index
+//                                   (chunk ^ ((row>>1)&7)) so that the ds_read_b128 fragment reads are bank-conflict free.  The
+//                                   epilogue goes through an fp32 LDS tile so that bias / time-embedding / residual are applied in
+//                                   fp32 and the result leaves as full 16-byte coalesced stores.  Any M, fp32 output, plain GELU.
+//   gemm_glds_kernel<BN, AMODE, FAST>  256 x BN (128 or 160), 8 waves, direct-to-LDS 3-slot ring; column / row statistics,
+//                                   LayerNorm fold, fp32 output, split-K slabs (fp32 or fp16)
+//   gemm_g4_kernel<AMODE, FAST>     256 x 128, 4 waves, two blocks per CU: one block's epilogue under the other's MFMAs
+//   gemm_w80s_kernel<AMODE, SHAPE>  (gemm_w80s_kernel.inc) the staggered, buffer-addressed 8-wave kernel on 320 x 160, 160 x 320
+//                                   (LayerNorm store loop), 256 x 256 and 320 x 192 (temporal attention in the epilogue, also
+//                                   gemm_w80s_causal_kernel) tiles; two-source A, per-row-group weights, every statistics epilogue
+//   gemm_g4p_kernel / gemm_g4q_kernel<GEGLU>, gemm_sqp_kernel<GEGLU>  the persistent forms of g4 (either MFMA shape) and of the
+//                                   256 x 256 staggered kernel: register epilogue, bias / LayerNorm fold / GEGLU / row add / residual
+//   splitk_reduce_kernel, splitk_gn_kernel<CPT>  the split-K reduce, alone or with the GroupNorm that consumes it
+// (The weight-stationary kernel of the 320 -> 320 linears is gemm_ws.hip; it is dispatched from here.)
 #include "common.h"
 
 namespace {
@@ -2878,12 +2887,12 @@ __global__ __launch_bounds__(512, 2) void gemm_sqp_kernel(const moca_gemm_params
 #endif
 }
 
-// XCD partition (xm x xn = 8, xn returned; 1 = the 1-D partition) of a tiles_m x tiles_n grid of TM x BN tiles of a LINEAR
+// XCD partition (xm x xn = 8, xn returned; 1 = the 1-D partition) of a tiles_m x tiles_n grid of row tiles x BN-column tiles of a LINEAR
 // launch: estimated fabric bytes = W part + A part.  W: an XCD whose W sub-range ((tiles_n / xn) BN x K) fits its L2 (<= 3 MB)
 // fetches it once -> xm |W| in total; one that does not streams it again for every M tile it owns -> tiles_m |W| whatever
 // the partition.  A is consumed row tile by row tile -> xn |A|.  Only partitions that divide both tile counts; a 2-D partition is
 // taken when it saves >= 20 %.
-static int choose_xcd_n(const moca_gemm_params& p, int tiles_m, int tiles_n, int TM, int BN) {
+static int choose_xcd_n(const moca_gemm_params& p, int tiles_m, int tiles_n, int BN) {
     if (p.splits != 1 || p.a_mode != MOCA_A_LINEAR) return 1;
     const double Wtot = (double)p.N * p.K * 2, Atot = (double)p.M * p.K * 2;
     auto cost = [&](int xn) {
@@ -2898,7 +2907,6 @@ static int choose_xcd_n(const moca_gemm_params& p, int tiles_m, int tiles_n, int
         const double c = cost(xn);
         if (c < 0.8 * best) { best = c; best_xn = xn; }
     }
-    (void)TM;
     return best_xn;
 }
 
@@ -2913,7 +2921,7 @@ int launch_gemm_w80s(const moca_gemm_params& p, hipStream_t st) {
     const int tiles_m = (p.M + TM - 1) / TM, tiles_n = p.N / BN;
     const int nblk = tiles_m * tiles_n * p.splits;
     moca_gemm_params pl = p;
-    pl.reserved4_ = (pl.reserved4_ & 0xff) | ((SHAPE == 3 ? 1 : choose_xcd_n(p, tiles_m, tiles_n, TM, BN)) << 8);
+    pl.reserved4_ = (pl.reserved4_ & 0xff) | ((SHAPE == 3 ? 1 : choose_xcd_n(p, tiles_m, tiles_n, BN)) << 8);
     constexpr int lds = 5 * (TM + BN) * 64;              // 150 KiB (160 KiB for 256 x 256); the fp16 epilogue tile fits inside the ring
     static bool attr_set = false;
     if (!attr_set) {
@@ -2924,97 +2932,6 @@ int launch_gemm_w80s(const moca_gemm_params& p, hipStream_t st) {
     hipLaunchKernelGGL(kernel, dim3(nblk + prefetch_blocks(pl)), dim3(512), lds, st, pl);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
-}
-
-// bytes spanned by the A operand / the W operand: the buffer-addressed kernels need every in-range offset below 2^31
-static inline int64_t a_span_bytes(const moca_gemm_params& p) {
-    if (p.a_mode == MOCA_A_LINEAR) return ((int64_t)p.M * p.lda + 64) * 2;
-    if (p.a_mode == MOCA_A_CONV3X3) return ((int64_t)(p.M / (p.outH * p.outW)) * p.inH * p.inW * p.C + 64) * 2;
-    return ((int64_t)p.M * p.C + 64) * 2;
-}
-static inline bool buffer_addressable(const moca_gemm_params& p) {
-    if (p.a2 && ((int64_t)p.M * p.lda2 + 64) * 2 >= (1ll << 31)) return false;
-    return a_span_bytes(p) < (1ll << 31) && (int64_t)p.N * p.ldw * 2 < (1ll << 31);
-}
-
-static inline int sq256_mode() { return moca_tuning_get(MOCA_TUNE_GEMM_SQ256); }
-static inline bool fast_gather(const moca_gemm_params& p);
-// g4 (4 waves, two blocks per CU): the GEGLU projections with K <= 640 -- but not the very tall ones (M >= 2^17: B = 16 forwards), where
-// the 256 x 256 staggered kernel is 4-5 % ahead (tools/bench_gemm.py geglu, BG_B=16 BG_TUNE=2:2).  MOCA_TUNE_GEMM_G4 = 0 / 2: never / always.
-static inline bool wants_g4(const moca_gemm_params& p) {
-    const int g4_mode = moca_tuning_get(MOCA_TUNE_GEMM_G4);
-    return g4_mode == 2 || (g4_mode == 1 && (p.flags & MOCA_EP_GEGLU) && p.K <= 640 && p.M < (1 << 17));
-}
-static inline bool buffer_addressable(const moca_gemm_params& p);
-static inline bool g4p_ok(const moca_gemm_params& p);
-static inline bool sqp_ok(const moca_gemm_params& p);
-// the persistent 256 x 256 kernel (MOCA_TUNE_GEMM_SQP = 0: never, 1: the GEGLU projections, 2: every linear it can run -- tests, A/B)
-static inline bool takes_sqp(const moca_gemm_params& p) {
-    const int mode = moca_tuning_get(MOCA_TUNE_GEMM_SQP);
-    if (!mode || !sqp_ok(p)) return false;
-    return mode == 2 || (p.flags & MOCA_EP_GEGLU);
-}
-// the persistent two-blocks-per-CU kernel (MOCA_TUNE_GEMM_G4P = 0: never, 1: the GEGLU projections, 2: every linear it can run -- tests, A/B)
-static inline bool takes_g4p(const moca_gemm_params& p) {
-    const int mode = moca_tuning_get(MOCA_TUNE_GEMM_G4P);
-    if (!mode || !g4p_ok(p)) return false;
-    return mode == 2 || (p.flags & MOCA_EP_GEGLU);
-}
-// the staggered kernel on 256 x 256 tiles for the wide projections (MOCA_TUNE_GEMM_SQ256 = 0: never, 1: not where g4 is preferred,
-// 2: every wide linear -- A/B runs); asked after takes_w80()
-static inline bool takes_sq256(const moca_gemm_params& p, bool use_g4) {
-    const int mode = sq256_mode();
-    return mode && p.a_mode == MOCA_A_LINEAR && p.N % 256 == 0 && p.N >= 2560 && p.M >= 512 && fast_gather(p) && buffer_addressable(p) &&
-           !(p.flags & (MOCA_EP_OUT_F32 | MOCA_FORCE_SMALL_TILE)) && ((p.M + 255) / 256) * (p.N / 256) * p.splits >= 200 &&
-           (mode == 2 || !use_g4);
-}
-static inline bool fast_gather(const moca_gemm_params& p) {
-    return (p.a_mode == MOCA_A_LINEAR) ? (p.K % BK == 0 && p.K <= 8192) : (p.C % BK == 0 && p.C <= 8192);
-}
-// the weight-stationary streaming kernel of the 320 -> 320 linears (gemm_ws.hip; MOCA_TUNE_GEMM_WS = 0: never).  Asked FIRST by every
-// predicate below: a call it takes runs on none of the tiled kernels.  (The queries -- moca_gemm_colsum_rows / _rowsum_cols / _lnfold_ok /
-// _ln_ok -- add the flag they ask about before they come here: the kernel has no column sums, no LayerNorm fold, no LayerNorm store.)
-static inline bool takes_ws(const moca_gemm_params& p) {
-    const int mode = moca_tuning_get(MOCA_TUNE_GEMM_WS);
-    if (!mode || !moca_gemm_ws_ok(p)) return false;
-    // 1: where it was measured ahead of the tiled kernel (profiles/r06_ab_gemm_ws.txt): with a residual at every size, without one from
-    // M = 2^17 up (B = 16 forwards; at M = 81920 a block's 10 strips do not amortise its start-up: W fetch + first strip).  2: wherever it applies
-    return mode == 2 || p.residual || p.M >= (1 << 17);
-}
-// does this (validated, split-normalised) call run on the 320 x 160 kernels / on their staggered buffer-addressed form?
-static inline bool takes_w80(const moca_gemm_params& p) {
-    if (takes_ws(p)) return false;
-    const int w80_mode = moca_tuning_get(MOCA_TUNE_GEMM_W80);
-    const int tiles320 = ((p.M + 319) / 320) * (p.N / 160);
-    return w80_mode && p.N % 160 == 0 && !(p.flags & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32 | MOCA_FORCE_SMALL_TILE)) && p.M > 160 &&
-           (tiles320 * p.splits >= 200 || w80_mode == 2) && fast_gather(p) && buffer_addressable(p);
-}
-static inline bool takes_w80s(const moca_gemm_params& p) {
-    return takes_w80(p);
-}
-// which form of the staggered kernel a call that takes_w80s() runs on.  The 160 x 320 tiling is required by the LayerNorm store
-// loop and taken by every N % 320 == 0 contraction: A is fetched once per 320 columns instead of once per 160 (linears: 37 vs 38 us
-// at M = 81920, N = K = 320; 99 vs 103 at K = 1280; 182 vs 193 / 366 vs 384 at M = 327680; N = 640: 22.7 vs 25.1).
-// Convs / temporal convs gain nothing from it (+-1 %, A/B on one device) and stay on the 320 x 160 form.
-// MOCA_TUNE_GEMM_WIDE = 0: only with MOCA_EP_LN; 1 (default): linears; 2: convs / temporal convs too (tests)
-static inline bool w80s_wide(const moca_gemm_params& p) {
-    if (p.flags & MOCA_EP_LN) return true;
-    const int mode = moca_tuning_get(MOCA_TUNE_GEMM_WIDE);
-    if (mode == 0 || p.N % 320) return false;
-    return p.a_mode == MOCA_A_LINEAR || mode == 2;
-}
-static inline bool takes_w80t_ln(const moca_gemm_params& pp) {     // the 160 x 320 tiling with the LayerNorm store loop
-    moca_gemm_params p = pp;
-    p.flags |= MOCA_EP_LN;
-    return p.a_mode == MOCA_A_LINEAR && p.N == 320 && p.splits == 1 && takes_w80s(p) && !(p.flags & (MOCA_EP_COLSUM | MOCA_EP_GSTAT));
-}
-
-int launch_gemm_w80_mode(const moca_gemm_params& p, hipStream_t st) {
-    const bool wide = w80s_wide(p);
-    if (p.a2) return wide ? launch_gemm_w80s<MOCA_A_LINEAR2, 1>(p, st) : launch_gemm_w80s<MOCA_A_LINEAR2, 0>(p, st);
-    if (p.a_mode == MOCA_A_LINEAR) return wide ? launch_gemm_w80s<MOCA_A_LINEAR, 1>(p, st) : launch_gemm_w80s<MOCA_A_LINEAR, 0>(p, st);
-    if (p.a_mode == MOCA_A_CONV3X3) return wide ? launch_gemm_w80s<MOCA_A_CONV3X3, 1>(p, st) : launch_gemm_w80s<MOCA_A_CONV3X3, 0>(p, st);
-    return wide ? launch_gemm_w80s<MOCA_A_TCONV3, 1>(p, st) : launch_gemm_w80s<MOCA_A_TCONV3, 0>(p, st);
 }
 
 template <int AMODE, bool FAST>
@@ -3030,21 +2947,13 @@ int launch_gemm_g4(const moca_gemm_params& p, hipStream_t st) {
         attr_set = true;
     }
     moca_gemm_params pl = p;
-    pl.reserved4_ = (pl.reserved4_ & 0xff) | (choose_xcd_n(p, tiles_m, tiles_n, 256, 128) << 8);
+    pl.reserved4_ = (pl.reserved4_ & 0xff) | (choose_xcd_n(p, tiles_m, tiles_n, 128) << 8);
     hipLaunchKernelGGL((gemm_g4_kernel<AMODE, FAST>), dim3(nblk + 2 * prefetch_blocks(pl)), dim3(256), lds, st, pl);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }
 
-// persistent two-blocks-per-CU kernel: which calls it can run (linears whose 256 x 128 tiles fill two blocks on every CU; bias,
-// LayerNorm fold, GEGLU or row add / residual -- none of the statistics epilogues)
-constexpr int G4P_BLOCKS = 512;
-static inline bool g4p_ok(const moca_gemm_params& p) {
-    if (p.a_mode != MOCA_A_LINEAR || p.splits != 1 || p.N % 128 || p.K % 64 || !buffer_addressable(p)) return false;
-    if (p.flags & ~(MOCA_EP_GEGLU | MOCA_EP_LNFOLD)) return false;
-    if ((p.flags & MOCA_EP_GEGLU) && (p.residual || p.rowadd)) return false;
-    return ((p.M + 255) / 256) * (p.N / 128) >= G4P_BLOCKS;
-}
+constexpr int G4P_BLOCKS = 512;                      // persistent two-blocks-per-CU kernel: two blocks on every CU
 template <bool GEGLU>
 int launch_gemm_g4p(const moca_gemm_params& p, hipStream_t st) {
     constexpr int lds = 3 * (256 + 128) * 64 + (2 * 256 + 2 * 128) * 4;      // 72 KiB ring + 3 KiB of tile statistics
@@ -3071,15 +2980,7 @@ int launch_gemm_g4p(const moca_gemm_params& p, hipStream_t st) {
     return MOCA_OK;
 }
 
-// persistent 256 x 256 staggered kernel: the linears whose 256 x 256 tiles give every CU at least one (bias, LayerNorm fold, GEGLU or
-// row add / residual -- none of the statistics epilogues)
-constexpr int SQP_BLOCKS = 256;
-static inline bool sqp_ok(const moca_gemm_params& p) {
-    if (p.a_mode != MOCA_A_LINEAR || p.splits != 1 || p.N % 256 || p.K % 64 || !buffer_addressable(p)) return false;
-    if (p.flags & ~(MOCA_EP_GEGLU | MOCA_EP_LNFOLD)) return false;
-    if ((p.flags & MOCA_EP_GEGLU) && (p.residual || p.rowadd)) return false;
-    return ((p.M + 255) / 256) * (p.N / 256) >= SQP_BLOCKS;
-}
+constexpr int SQP_BLOCKS = 256;                      // persistent 256 x 256 staggered kernel: one block on every CU
 template <bool GEGLU>
 int launch_gemm_sqp(const moca_gemm_params& p, hipStream_t st) {
     constexpr int lds = 5 * (256 + 256) * 64;                    // the whole 160 KiB: the ring; tile statistics live in its one free slot
@@ -3091,7 +2992,7 @@ int launch_gemm_sqp(const moca_gemm_params& p, hipStream_t st) {
     }
     moca_gemm_params pl = p;
     pl.reserved2_ = SQP_BLOCKS;
-    pl.reserved4_ = (pl.reserved4_ & 0xfd) | (choose_xcd_n(p, (p.M + 255) / 256, p.N / 256, 256, 256) << 8) |
+    pl.reserved4_ = (pl.reserved4_ & 0xfd) | (choose_xcd_n(p, (p.M + 255) / 256, p.N / 256, 256) << 8) |
                     (moca_tuning_get(MOCA_TUNE_SQP_WALK) ? 2 : 0);
     hipLaunchKernelGGL((gemm_sqp_kernel<GEGLU>), dim3(SQP_BLOCKS + prefetch_blocks(pl)), dim3(512), lds, st, pl);
     MOCA_CHECK_LAUNCH();
@@ -3136,9 +3037,19 @@ int launch_gemm(const moca_gemm_params& p, hipStream_t st) {
     return MOCA_OK;
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Dispatch.  Which kernel runs a call is decided by route_of() and nowhere else; what that kernel implements is written down in
+// route_info() / route_can() and nowhere else.  moca_gemm_f16, moca_gemm_route and every query (moca_gemm_colsum_rows, _rowsum_cols,
+// _ln_ok, _lnfold_ok, _tattn_ok, _wgroup_ok, _cat_ok, _splitk_groupnorm_ok) ask these two: a query that says yes is a launch that is
+// accepted, on the kernel the query answered for.
+enum Route : int {
+    R_NONE = 0,                                       // refused
+    R_SMALL64 = MOCA_ROUTE_SMALL64, R_SMALL128 = MOCA_ROUTE_SMALL128, R_GLDS128 = MOCA_ROUTE_GLDS128, R_GLDS160 = MOCA_ROUTE_GLDS160,
+    R_G4 = MOCA_ROUTE_G4, R_W80 = MOCA_ROUTE_W80, R_W80W = MOCA_ROUTE_W80W, R_SQ256 = MOCA_ROUTE_SQ256, R_G4P = MOCA_ROUTE_G4P,
+    R_SQP = MOCA_ROUTE_SQP, R_TATTN = MOCA_ROUTE_TATTN, R_WS = MOCA_ROUTE_WS,
+};
 
-static void normalise_splits(moca_gemm_params& p) {
+void normalise_splits(moca_gemm_params& p) {
     if (p.splits < 1) p.splits = 1;
     if (p.splits > (p.K + BK - 1) / BK) p.splits = (p.K + BK - 1) / BK;
     if (p.splits > 1) {   // no empty k range: every split writes its slab
@@ -3147,172 +3058,329 @@ static void normalise_splits(moca_gemm_params& p) {
     }
 }
 
-// does this (validated, split-normalised) call run on the 256-row direct-to-LDS kernel (gemm_glds_kernel), and with which BN?
-// (mirrors the dispatch order of moca_gemm_f16: w80 family first, then sq256, then g4, then glds)
-static int takes_glds_bn(const moca_gemm_params& p) {
-    if (takes_ws(p) || takes_w80(p)) return 0;
-    const int big_bn = (p.N % 128 == 0) ? 128 : (p.N % 160 == 0 ? 160 : 0);
-    if (!(big_bn != 0 && p.M > 128 && !(p.flags & MOCA_FORCE_SMALL_TILE))) return 0;
-    const bool use_g4 = !(p.flags & MOCA_EP_OUT_F32) && wants_g4(p);
-    if (takes_sq256(p, use_g4)) return 0;
-    if (big_bn == 128 && use_g4) return 0;
-    return big_bn;
+// bytes spanned by the A operand / the W operand: the buffer-addressed kernels need every in-range offset below 2^31
+inline int64_t a_span_bytes(const moca_gemm_params& p) {
+    if (p.a_mode == MOCA_A_LINEAR) return ((int64_t)p.M * p.lda + 64) * 2;
+    if (p.a_mode == MOCA_A_CONV3X3) return ((int64_t)(p.M / (p.outH * p.outW)) * p.inH * p.inW * p.C + 64) * 2;
+    return ((int64_t)p.M * p.C + 64) * 2;
 }
-// rows per tile of the column sums a MOCA_EP_COLSUM launch leaves behind (0: this call cannot): 320 / 160 on the staggered kernel,
-// 256 on the 256-row kernel (fp16 output, no GEGLU, no split-k)
-static int colsum_rows(const moca_gemm_params& pp) {
-    moca_gemm_params p = pp;
-    if (!(p.flags & (MOCA_EP_COLSUM | MOCA_EP_GSTAT))) p.flags |= MOCA_EP_COLSUM;      // (the question is about the call WITH column sums)
-    if (p.splits != 1) return 0;
-    if ((p.flags & MOCA_EP_GSTAT) && takes_ws(p)) return 32;      // the weight-stationary kernel: finished statistics only, strips of 32 rows
-    if (takes_w80s(p)) return w80s_wide(p) ? 160 : 320;
-    if (!(p.flags & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32)) && takes_glds_bn(p) != 0) return 256;
-    return 0;
+inline bool buffer_addressable(const moca_gemm_params& p) {
+    if (p.a2 && ((int64_t)p.M * p.lda2 + 64) * 2 >= (1ll << 31)) return false;
+    return a_span_bytes(p) < (1ll << 31) && (int64_t)p.N * p.ldw * 2 < (1ll << 31);
+}
+inline bool fast_gather(const moca_gemm_params& p) {
+    return (p.a_mode == MOCA_A_LINEAR) ? (p.K % BK == 0 && p.K <= 8192) : (p.C % BK == 0 && p.C <= 8192);
 }
 
-// columns per column tile of the row sums a MOCA_EP_ROWSUM launch leaves behind (0: this call cannot)
-static int rowsum_cols(const moca_gemm_params& pp) {
-    moca_gemm_params p = pp;
-    p.flags |= MOCA_EP_ROWSUM;
-    if (takes_ws(p)) return 80;                       // one partial per wave of the weight-stationary kernel
-    if (p.splits != 1 || (p.flags & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32 | MOCA_EP_COLSUM | MOCA_EP_GSTAT | MOCA_EP_LN | MOCA_EP_GELU | MOCA_FORCE_SMALL_TILE))) return 0;
-    if (takes_w80s(p)) return w80s_wide(p) ? 320 : 160;
-    return takes_glds_bn(p);
-}
-// does the kernel this call runs on have the MOCA_EP_LNFOLD epilogue?
-static bool lnfold_ok(const moca_gemm_params& pp) {
-    moca_gemm_params p = pp;
-    p.flags |= MOCA_EP_LNFOLD;
-    if (p.a_mode != MOCA_A_LINEAR || p.splits != 1) return false;
-    if (p.flags & (MOCA_EP_OUT_F32 | MOCA_EP_COLSUM | MOCA_EP_GSTAT | MOCA_EP_LN | MOCA_EP_ROWSUM | MOCA_EP_GELU | MOCA_FORCE_SMALL_TILE)) return false;
-    if (takes_sqp(p) || takes_g4p(p)) return true;
-    if (takes_w80(p)) return !(p.flags & MOCA_EP_GEGLU) && takes_w80s(p);
-    const int big_bn = (p.N % 128 == 0) ? 128 : (p.N % 160 == 0 ? 160 : 0);
-    if (!(big_bn != 0 && p.M > 128)) return false;
-    const bool use_g4 = wants_g4(p);
-    if (takes_sq256(p, use_g4)) return true;
-    if (big_bn == 128 && use_g4) return true;
-    return !(p.flags & MOCA_EP_GEGLU);                  // the 256-row kernel: plain epilogue only
+// which calls the persistent kernels can run: linears whose tiles (256 x 128: two blocks on every CU; 256 x 256: one) give every
+// block at least one; bias, LayerNorm fold, GEGLU or row add / residual -- none of the statistics epilogues
+bool persistent_ok(const moca_gemm_params& p, int BN, int blocks) {
+    if (p.a_mode != MOCA_A_LINEAR || p.splits != 1 || p.N % BN || p.K % 64 || !buffer_addressable(p)) return false;
+    if (p.flags & ~(MOCA_EP_GEGLU | MOCA_EP_LNFOLD)) return false;
+    if ((p.flags & MOCA_EP_GEGLU) && (p.residual || p.rowadd)) return false;
+    return ((p.M + 255) / 256) * (p.N / BN) >= blocks;
 }
 
-// MOCA_EP_TATTN: the q|k|v projection of a temporal self-attention with the attention finished in the epilogue (SHAPE 3 of the
-// staggered kernel: 320 x 192 tiles, rows = 16 frames x 20 pixels, columns = one head)
-static bool tattn_ok(const moca_gemm_params& p) {
-    if (p.a_mode != MOCA_A_LINEAR || p.splits != 1 || !fast_gather(p) || !buffer_addressable(p)) return false;
-    if (p.flags & ~(MOCA_EP_TATTN | MOCA_EP_LNFOLD)) return false;
-    if (p.residual || p.rowadd) return false;
-    if (p.N % 192 || p.T != 16 || p.HW <= 0 || p.HW % 20 || p.M % (16 * p.HW)) return false;
-    if (p.ldo % 4 || p.ldo < p.N / 3) return false;
-    // tattn_causal: 0 or 1; the mask is applied to the raw scores, so the scale must keep -inf at -inf
-    if (p.tattn_causal != 0 && (p.tattn_causal != 1 || !(p.tattn_scale > 0.f))) return false;
+// The kernel family a (validated, split-normalised) call WITH ITS FLAGS runs on.  The only reader of the MOCA_TUNE_GEMM_* kernel-choice
+// knobs and the only place that knows the order.  (MOCA_TUNE_GEMM_MF32 and MOCA_TUNE_SQP_WALK pick a variant inside a launcher.)
+Route route_of(const moca_gemm_params& p) {
+    // MOCA_EP_TATTN: the q|k|v projection of a temporal self-attention with the attention finished in the epilogue (SHAPE 3 of the
+    // staggered kernel: 320 x 192 tiles, rows = 16 frames x 20 pixels, columns = one head)
+    if (p.flags & MOCA_EP_TATTN) return R_TATTN;
+    // the weight-stationary streaming kernel of the 320 -> 320 linears (gemm_ws.hip; MOCA_TUNE_GEMM_WS = 0: never).  Asked before every
+    // tiled kernel: a call it takes runs on none of them.  (The kernel has no column sums, no LayerNorm fold, no LayerNorm store: a call
+    // with one of those flags is not its call, moca_gemm_ws_ok.)
+    // 1: where it was measured ahead of the tiled kernel (profiles/r06_ab_gemm_ws.txt): with a residual at every size, without one from
+    // M = 2^17 up (B = 16 forwards; at M = 81920 a block's 10 strips do not amortise its start-up: W fetch + first strip).  2: wherever it applies
+    const int ws_mode = moca_tuning_get(MOCA_TUNE_GEMM_WS);
+    if (ws_mode && moca_gemm_ws_ok(p) && (ws_mode == 2 || p.residual || p.M >= (1 << 17))) return R_WS;
+    // the persistent kernels (MOCA_TUNE_GEMM_SQP / _G4P = 0: never, 1: the GEGLU projections, 2: every linear they can run -- tests, A/B),
+    // 256 x 256 before 256 x 128.  Neither reads a second A source or per-row-group weights: such a call goes on to the staggered kernels.
+    if (!p.a2 && p.wgroup_rows <= 0) {
+        const int sqp_mode = moca_tuning_get(MOCA_TUNE_GEMM_SQP), g4p_mode = moca_tuning_get(MOCA_TUNE_GEMM_G4P);
+        if (sqp_mode && persistent_ok(p, 256, SQP_BLOCKS) && (sqp_mode == 2 || (p.flags & MOCA_EP_GEGLU))) return R_SQP;
+        if (g4p_mode && persistent_ok(p, 128, G4P_BLOCKS) && (g4p_mode == 2 || (p.flags & MOCA_EP_GEGLU))) return R_G4P;
+    }
+    // w80 (320 x 160 tiles, 80 x 80 wave tiles, staggered and buffer-addressed): every non-GEGLU contraction whose N is a multiple of
+    // 160 and whose 320-row tiles fill the chip.  (MOCA_TUNE_GEMM_W80: 0 never, 2 drops the tile-count rule -- tests.)
+    const int w80_mode = moca_tuning_get(MOCA_TUNE_GEMM_W80);
+    const int tiles320 = ((p.M + 319) / 320) * (p.N / 160);
+    if (w80_mode && p.N % 160 == 0 && !(p.flags & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32 | MOCA_FORCE_SMALL_TILE)) && p.M > 160 &&
+        (tiles320 * p.splits >= 200 || w80_mode == 2) && fast_gather(p) && buffer_addressable(p)) {
+        // which form of the staggered kernel.  The 160 x 320 tiling is required by the LayerNorm store loop and taken by every
+        // N % 320 == 0 contraction: A is fetched once per 320 columns instead of once per 160 (linears: 37 vs 38 us at M = 81920,
+        // N = K = 320; 99 vs 103 at K = 1280; 182 vs 193 / 366 vs 384 at M = 327680; N = 640: 22.7 vs 25.1).
+        // Convs / temporal convs gain nothing from it (+-1 %, A/B on one device) and stay on the 320 x 160 form.
+        // MOCA_TUNE_GEMM_WIDE = 0: only with MOCA_EP_LN; 1 (default): linears; 2: convs / temporal convs too (tests)
+        if (p.flags & MOCA_EP_LN) return R_W80W;
+        const int wide_mode = moca_tuning_get(MOCA_TUNE_GEMM_WIDE);
+        if (wide_mode == 0 || p.N % 320) return R_W80;
+        return (p.a_mode == MOCA_A_LINEAR || wide_mode == 2) ? R_W80W : R_W80;
+    }
+    // g4 (4 waves, two blocks per CU) wins where the epilogue is VALU-heavy and K is short (GEGLU at C = 320 / 640:
+    // one block's erf-GELU epilogue runs under the other block's MFMAs, -5 % on the same device); the 8-wave kernel's
+    // deeper pipeline wins everywhere else (K >= 1280: 1137 vs 880 TFLOP/s).  So: the GEGLU projections with K <= 640 -- but not the
+    // very tall ones (M >= 2^17: B = 16 forwards), where the 256 x 256 staggered kernel is 4-5 % ahead (tools/bench_gemm.py geglu,
+    // BG_B=16 BG_TUNE=2:2).  MOCA_TUNE_GEMM_G4 = 0 / 2 forces never / always (tests).
+    const int g4_mode = moca_tuning_get(MOCA_TUNE_GEMM_G4);
+    const bool use_g4 = !(p.flags & MOCA_EP_OUT_F32) &&
+                        (g4_mode == 2 || (g4_mode == 1 && (p.flags & MOCA_EP_GEGLU) && p.K <= 640 && p.M < (1 << 17)));
+    // the staggered kernel on 256 x 256 tiles for the wide projections (MOCA_TUNE_GEMM_SQ256 = 0: never, 1: not where g4 is preferred,
+    // 2: every wide linear -- A/B runs)
+    const int sq256_mode = moca_tuning_get(MOCA_TUNE_GEMM_SQ256);
+    if (sq256_mode && p.a_mode == MOCA_A_LINEAR && p.N % 256 == 0 && p.N >= 2560 && p.M >= 512 && fast_gather(p) && buffer_addressable(p) &&
+        !(p.flags & (MOCA_EP_OUT_F32 | MOCA_FORCE_SMALL_TILE)) && ((p.M + 255) / 256) * (p.N / 256) * p.splits >= 200 &&
+        (sq256_mode == 2 || !use_g4)) return R_SQ256;
+    // large-tile direct-to-LDS kernel whenever a 256-row tile is at least half full
+    const int big_bn = (p.N % 128 == 0) ? 128 : (p.N % 160 == 0 ? 160 : 0);
+    if (big_bn != 0 && p.M > 128 && !(p.flags & MOCA_FORCE_SMALL_TILE)) {
+        if (big_bn == 128) return use_g4 ? R_G4 : R_GLDS128;
+        return R_GLDS160;
+    }
+    return p.N % 128 == 0 ? R_SMALL128 : R_SMALL64;
+}
+
+// What a route's kernel implements: its tile (rows x columns; the weight-stationary kernel: rows per strip x columns per wave) and the
+// MOCA_EP_* epilogues it has, with the four things that are not flags as bits above them.  MOCA_FORCE_SMALL_TILE asks for a route and
+// MOCA_EP_SLABS is split-K without the reduce launch: neither is an epilogue of its own.
+constexpr int CAN_SPLITK = 1 << 16, CAN_A2 = 1 << 17, CAN_WGROUP = 1 << 18, CAN_UP_PHASE = 1 << 19;
+constexpr int EP_STATS = MOCA_EP_COLSUM | MOCA_EP_GSTAT;          // (GSTAT: the same sums, finished; same kernels)
+struct RouteInfo { int tm, tn, can; };
+RouteInfo route_info(Route r) {
+    constexpr int GLDS = MOCA_EP_GEGLU | MOCA_EP_OUT_F32 | EP_STATS | MOCA_EP_ROWSUM | MOCA_EP_LNFOLD | CAN_SPLITK | CAN_UP_PHASE;
+    constexpr int W80 = EP_STATS | MOCA_EP_ROWSUM | MOCA_EP_LNFOLD | CAN_SPLITK | CAN_UP_PHASE | CAN_A2 | CAN_WGROUP;
+    switch (r) {
+        // the plain-GELU epilogue (CLIP text MLP) exists in the 128-row kernel only
+        case R_SMALL64: return {BM, 64, MOCA_EP_OUT_F32 | MOCA_EP_GELU | CAN_SPLITK};
+        case R_SMALL128: return {BM, 128, MOCA_EP_GEGLU | MOCA_EP_OUT_F32 | MOCA_EP_GELU | CAN_SPLITK};
+        case R_GLDS128: return {256, 128, GLDS};
+        case R_GLDS160: return {256, 160, GLDS};
+        case R_G4: return {256, 128, MOCA_EP_GEGLU | MOCA_EP_LNFOLD | CAN_SPLITK | CAN_UP_PHASE};
+        case R_W80: return {320, 160, W80};
+        case R_W80W: return {160, 320, W80 | MOCA_EP_LN};           // a block owns whole rows of N = 320: the LayerNorm store loop
+        case R_SQ256: return {256, 256, MOCA_EP_GEGLU | MOCA_EP_LNFOLD | CAN_SPLITK};
+        case R_G4P: return {256, 128, MOCA_EP_GEGLU | MOCA_EP_LNFOLD};
+        case R_SQP: return {256, 256, MOCA_EP_GEGLU | MOCA_EP_LNFOLD};
+        case R_TATTN: return {320, 192, MOCA_EP_TATTN | MOCA_EP_LNFOLD};
+        // finished statistics only (strips of 32 rows), one row partial per wave of 80 columns; deals its strips by weight group
+        case R_WS: return {32, 80, MOCA_EP_ROWSUM | MOCA_EP_GSTAT | CAN_WGROUP};
+        case R_NONE: break;
+    }
+    return {0, 0, 0};
+}
+
+// Can route r's kernel run this (validated, split-normalised) call: everything it asks for is implemented there, under the side
+// conditions each feature has.  Pointers are the launch's business (prepare), not a capability.
+bool route_can(Route r, const moca_gemm_params& p) {
+    const RouteInfo ri = route_info(r);
+    const int f = p.flags & ~(MOCA_FORCE_SMALL_TILE | MOCA_EP_SLABS);
+    const int wants = f | (p.splits > 1 ? CAN_SPLITK : 0) | (p.a2 ? CAN_A2 : 0) | (p.wgroup_rows ? CAN_WGROUP : 0) | (p.up_phase ? CAN_UP_PHASE : 0);
+    if (r == R_NONE || (wants & ~ri.can) || p.wgroup_rows < 0) return false;
+    if (r == R_WS) return true;                       // moca_gemm_ws_ok, asked by route_of, is that kernel's whole precondition
+    const bool linear1 = p.a_mode == MOCA_A_LINEAR && p.splits == 1;
+    if (r == R_TATTN) {
+        if (!linear1 || !fast_gather(p) || !buffer_addressable(p) || p.residual || p.rowadd || (p.flags & MOCA_FORCE_SMALL_TILE)) return false;
+        if (p.N % 192 || p.T != 16 || p.HW <= 0 || p.HW % 20 || p.M % (16 * p.HW)) return false;
+        if (p.ldo % 4 || p.ldo < p.N / 3) return false;
+        // tattn_causal: 0 or 1; the mask is applied to the raw scores, so the scale must keep -inf at -inf
+        return p.tattn_causal == 0 || (p.tattn_causal == 1 && p.tattn_scale > 0.f);
+    }
+    // column sums / GroupNorm statistics: fp16 output, no GEGLU, no split-k
+    if ((f & EP_STATS) && (p.splits != 1 || (f & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32)))) return false;
+    // row sums: of a plain fp16 epilogue only
+    if ((f & MOCA_EP_ROWSUM) && (p.splits != 1 || (f & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32 | EP_STATS | MOCA_EP_LN | MOCA_EP_GELU)))) return false;
+    // the LayerNorm store loop: a linear whose 320 columns one block owns, no column statistics beside it
+    if ((f & MOCA_EP_LN) && !(linear1 && p.N == 320 && !(f & EP_STATS))) return false;
+    // the LayerNorm fold: a linear with nothing else but GEGLU in the epilogue; the 256-row kernel has it in its plain epilogue only
+    if ((f & MOCA_EP_LNFOLD) && !(linear1 && !(f & (MOCA_EP_OUT_F32 | EP_STATS | MOCA_EP_LN | MOCA_EP_ROWSUM | MOCA_EP_GELU)) &&
+                                  !((r == R_GLDS128 || r == R_GLDS160) && (f & MOCA_EP_GEGLU)))) return false;
+    if ((f & MOCA_EP_GELU) && (f & MOCA_EP_GEGLU)) return false;
+    // two-source A (the virtual torch.cat in front of a ResBlock's skip_connection): a plain linear, sources split at a multiple of 64
+    // columns, nothing but bias / residual / row add / row sums / GroupNorm statistics in the epilogue
+    if (p.a2) {
+        if (!linear1 || (f & ~(EP_STATS | MOCA_EP_ROWSUM))) return false;
+        if (p.k1 <= 0 || p.k1 >= p.K || p.k1 % 64 || (p.K - p.k1) % 64 || p.lda % 8 || p.lda2 % 8 || p.lda < p.k1 || p.lda2 < p.K - p.k1) return false;
+    }
+    // per-row-group weights (wgroup_rows / wgroup_stride): a plain linear whose row tiles (160 rows on the 160 x 320 tiling, 320 on
+    // 320 x 160) lie inside one group; bias / residual / row sums / LayerNorm store loop / column statistics
+    if (p.wgroup_rows) {
+        if (!linear1 || p.a2 || p.wgroup_stride < p.N * p.ldw || (f & ~(EP_STATS | MOCA_EP_ROWSUM | MOCA_EP_LN))) return false;
+        if (p.M % p.wgroup_rows || p.wgroup_rows % ri.tm) return false;
+        if ((int64_t)(p.M / p.wgroup_rows) * p.wgroup_stride * 2 >= (1ll << 31)) return false;
+    }
+    // one phase of upsample + conv: a 2 x 2 conv on the low-resolution grid, rows scattered by the plain store loop of the
+    // 256- / 320-row kernels (fast gather), nothing else in the epilogue but the GroupNorm statistics
+    if (p.up_phase && (p.splits != 1 || p.M <= 160 || !fast_gather(p) || p.residual || p.rowadd || (f & ~MOCA_EP_GSTAT) ||
+                       (p.N % 128 && p.N % 160))) return false;
     return true;
 }
 
-extern "C" int moca_gemm_tattn_ok(const moca_gemm_params* pp) {
-    if (!pp) return 0;
-    moca_gemm_params p = *pp;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
-    if (p.splits < 1) p.splits = 1;
-    p.flags |= MOCA_EP_TATTN;
-    return tattn_ok(p) ? 1 : 0;
+Route checked_route(const moca_gemm_params& p) {
+    const Route r = route_of(p);
+    return route_can(r, p) ? r : R_NONE;
 }
 
-// two-source A (the virtual torch.cat in front of a ResBlock's skip_connection): a plain linear on the staggered kernels, sources
-// split at a multiple of 64 columns, nothing but bias / residual / row add / row sums / GroupNorm statistics in the epilogue
-static bool cat_ok(const moca_gemm_params& p) {
-    if (!p.a2 || p.a_mode != MOCA_A_LINEAR || p.splits != 1) return false;
-    if (p.k1 <= 0 || p.k1 >= p.K || p.k1 % 64 || (p.K - p.k1) % 64 || p.lda % 8 || p.lda2 % 8 || p.lda < p.k1 || p.lda2 < p.K - p.k1) return false;
-    if (p.flags & ~(MOCA_EP_COLSUM | MOCA_EP_GSTAT | MOCA_EP_ROWSUM)) return false;
-    return takes_w80s(p);
-}
-extern "C" int moca_gemm_cat_ok(const moca_gemm_params* pp) {
-    if (!pp) return 0;
-    moca_gemm_params p = *pp;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
+// What the queries share: the shape preamble, the split count as the launch will see it, the flag asked about added (a query answers
+// for the call WITH its flag: the flag can move the call to another kernel), then route and capability.  `p` = that call.
+Route query_route(const moca_gemm_params* pp, int flag, moca_gemm_params& p) {
+    if (!pp) return R_NONE;
+    p = *pp;
+    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return R_NONE;
     normalise_splits(p);
-    return cat_ok(p) ? 1 : 0;
-}
-
-// per-row-group weights (wgroup_rows / wgroup_stride): a plain linear on the staggered kernels whose row tiles (160 rows on the
-// 160 x 320 tiling, 320 on 320 x 160) lie inside one group; bias / residual / row sums / LayerNorm store loop / column statistics
-static bool wgroup_ok(const moca_gemm_params& p) {
-    if (p.wgroup_rows <= 0 || p.wgroup_stride < p.N * p.ldw || p.a_mode != MOCA_A_LINEAR || p.a2 || p.splits != 1) return false;
-    if (takes_ws(p)) return true;                     // the weight-stationary kernel deals its strips by weight group
-    if (p.flags & ~(MOCA_EP_COLSUM | MOCA_EP_GSTAT | MOCA_EP_ROWSUM | MOCA_EP_LN)) return false;
-    if (!takes_w80s(p) || p.M % p.wgroup_rows) return false;
-    const int tm = w80s_wide(p) ? 160 : 320;
-    if (p.wgroup_rows % tm) return false;
-    return (int64_t)(p.M / p.wgroup_rows) * p.wgroup_stride * 2 < (1ll << 31);
-}
-extern "C" int moca_gemm_wgroup_ok(const moca_gemm_params* pp) {
-    if (!pp) return 0;
-    moca_gemm_params p = *pp;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
-    normalise_splits(p);
-    return wgroup_ok(p) ? 1 : 0;
-}
-
-// The queries about an epilogue flag answer for the call WITH that flag, per-group weights included: moca_gemm_f16 checks wgroup_ok() on
-// the flagged call, and the flag can move it to another kernel (MOCA_EP_LN: off the weight-stationary kernel onto the 160 x 320 tiling,
-// which needs groups of whole 160-row tiles).  A query that says yes is a launch that is accepted.
-static bool wgroup_ok_with(const moca_gemm_params& pp, int flag) {
-    if (pp.wgroup_rows == 0) return true;
-    moca_gemm_params p = pp;
     p.flags |= flag;
-    return wgroup_ok(p);
-}
-
-extern "C" int moca_gemm_rowsum_cols(const moca_gemm_params* pp) {
-    if (!pp) return 0;
-    moca_gemm_params p = *pp;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
-    normalise_splits(p);
-    return wgroup_ok_with(p, MOCA_EP_ROWSUM) ? rowsum_cols(p) : 0;
-}
-
-extern "C" int moca_gemm_lnfold_ok(const moca_gemm_params* pp) {
-    if (!pp) return 0;
-    moca_gemm_params p = *pp;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
-    normalise_splits(p);
-    return lnfold_ok(p) ? 1 : 0;
-}
-
-extern "C" int moca_gemm_colsum_rows(const moca_gemm_params* pp) {
-    if (!pp) return 0;
-    moca_gemm_params p = *pp;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
-    normalise_splits(p);
-    return wgroup_ok_with(p, (p.flags & MOCA_EP_GSTAT) ? 0 : MOCA_EP_COLSUM) ? colsum_rows(p) : 0;
-}
-
-extern "C" int moca_gemm_ln_ok(const moca_gemm_params* pp) {
-    if (!pp) return 0;
-    moca_gemm_params p = *pp;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
-    normalise_splits(p);
-    return takes_w80t_ln(p) && wgroup_ok_with(p, MOCA_EP_LN) ? 1 : 0;
+    return checked_route(p);
 }
 
 // fp16 split-K slabs (MOCA_TUNE_SLAB_F16): a split-K call of the 256-row kernel with an fp16 output and no GEGLU
-static bool slab_f16(const moca_gemm_params& p) {
-    return moca_tuning_get(MOCA_TUNE_SLAB_F16) && p.splits > 1 && !(p.flags & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32)) && takes_glds_bn(p) != 0;
+bool slab_f16(Route r, const moca_gemm_params& p) {
+    return moca_tuning_get(MOCA_TUNE_SLAB_F16) && p.splits > 1 && !(p.flags & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32)) && (r == R_GLDS128 || r == R_GLDS160);
 }
 // can moca_gemm_splitk_groupnorm_f16 finish this (validated, split-normalised) MOCA_EP_SLABS call?  fp16 plain epilogue, one block per
 // (statistics group, channel group) slab with the slab in registers
-static bool splitk_gn_ok(const moca_gemm_params& p, int HW, int fps) {
+bool splitk_gn_ok(const moca_gemm_params& p, int HW, int fps) {
     if (p.splits < 2 || (p.flags & ~MOCA_EP_SLABS) || p.N % 32 || (p.N / 32) % 8 || p.N / 32 > 128 || p.up_phase) return false;
     if (HW <= 0 || fps <= 0 || p.M % (HW * fps)) return false;
     const int64_t nchunks = (int64_t)HW * fps * (p.N / 32 / 8);
     return nchunks >= 64 && nchunks <= 4096;
 }
-extern "C" int moca_gemm_splitk_groupnorm_ok(const moca_gemm_params* pp, int32_t HW, int32_t frames_per_stat) {
-    if (!pp) return 0;
-    moca_gemm_params p = *pp;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.N % 64 || p.K % 8) return 0;
+
+// Everything moca_gemm_f16 does before the launch: the argument contract, the split count, the route and its capability check, the
+// launchers' reserved fields.  Returns the route with `p` ready to launch, or R_NONE (MOCA_E_BADARG).
+Route prepare(const moca_gemm_params* pp, moca_gemm_params& p) {
+    if (!pp) return R_NONE;
+    p = *pp;
+    if (p.splits < 1) p.splits = 1;
+    if (!p.a || !p.w || !p.out) return R_NONE;
+    if (p.M <= 0 || p.N <= 0 || p.K <= 0) return R_NONE;
+    if (p.N % 64 || p.K % 8 || p.ldw % BK || p.ldw < ((p.K + BK - 1) / BK) * BK) return R_NONE;
+    const bool geglu = p.flags & MOCA_EP_GEGLU;
+    if (geglu && p.N % 128) return R_NONE;
+    if (p.ldo % 8 || (p.residual && p.ldr % 8) || (p.rowadd && (p.ld_rowadd % 8 || p.rowadd_div <= 0))) return R_NONE;
+    if (p.splits > 1 && !p.splitk_ws) return R_NONE;
+    if (p.prefetch_kib < 0 || (p.prefetch_kib > 0 && (!p.prefetch || (reinterpret_cast<uintptr_t>(p.prefetch) & 15)))) return R_NONE;
+    // the plain-GELU epilogue: asked for with the small tile (or at M <= 128, where nothing else runs) and without split-K as given
+    if ((p.flags & MOCA_EP_GELU) && (p.splits != 1 || !((p.flags & MOCA_FORCE_SMALL_TILE) || p.M <= 128))) return R_NONE;
     normalise_splits(p);
-    return splitk_gn_ok(p, HW, frames_per_stat) ? 1 : 0;
+    if ((p.flags & MOCA_EP_SLABS) && (p.splits < 2 || (p.flags & ~MOCA_EP_SLABS))) return R_NONE;   // ask moca_gemm_splitk_groupnorm_ok() first
+    if (p.up_phase && p.a_mode != MOCA_A_CONV3X3) return R_NONE;
+    switch (p.a_mode) {
+        case MOCA_A_LINEAR:
+            if (!p.a2 && (p.lda % 8 || p.lda < p.K)) return R_NONE;      // (two sources: route_can; ask moca_gemm_cat_ok() first)
+            break;
+        case MOCA_A_CONV3X3:
+            if (p.up_phase < 0 || p.up_phase > 4) return R_NONE;
+            if (p.C % 8 || p.K != (p.up_phase ? 4 : 9) * p.C || p.inH <= 0 || p.inW <= 0 || p.outH <= 0 || p.outW <= 0) return R_NONE;
+            if (p.up_phase && (p.stride != 1 || p.up || p.nopad_lo)) return R_NONE;
+            if (p.stride != 1 && p.stride != 2) return R_NONE;
+            if (p.nopad_lo != 0 && (p.nopad_lo != 1 || p.stride != 2 || p.up || (p.inH | p.inW) & 1)) return R_NONE;
+            if (p.up && (p.stride != 1 || p.outH != 2 * p.inH || p.outW != 2 * p.inW)) return R_NONE;
+            if (!p.up && p.stride == 1 && (p.outH != p.inH || p.outW != p.inW)) return R_NONE;
+            if (p.stride == 2 && (p.outH != (p.inH - 1) / 2 + 1 || p.outW != (p.inW - 1) / 2 + 1)) return R_NONE;
+            if (p.M % (p.outH * p.outW)) return R_NONE;
+            break;
+        case MOCA_A_TCONV3:
+            if (p.C % 8 || p.K != 3 * p.C || p.T <= 0 || p.HW <= 0 || p.M % (p.T * p.HW)) return R_NONE;
+            break;
+        default:
+            return R_NONE;
+    }
+    if (p.a2 && p.a_mode != MOCA_A_LINEAR) return R_NONE;
+    if (p.gstat_cpg < 0 || p.gstat_coff < 0 || ((p.gstat_cpg || p.gstat_coff) && !(p.flags & MOCA_EP_GSTAT))) return R_NONE;
+    if (p.tattn_causal && !(p.flags & MOCA_EP_TATTN)) return R_NONE;         // (the mask exists in the MOCA_EP_TATTN epilogue only)
+    const Route r = checked_route(p);                 // ask the flag's query first: moca_gemm_colsum_rows(), _ln_ok(), _rowsum_cols(), ...
+    if (r == R_NONE) return R_NONE;
+    // the outputs and inputs the epilogues need
+    if ((p.flags & MOCA_EP_COLSUM) && !p.colsum) return R_NONE;
+    if ((p.flags & MOCA_EP_LN) && !(p.ln_gamma && p.ln_beta && p.ln_out && p.ld_ln % 8 == 0)) return R_NONE;
+    if ((p.flags & MOCA_EP_ROWSUM) && !p.rowsum) return R_NONE;
+    if ((p.flags & MOCA_EP_LNFOLD) && !(p.lnf_part && p.lnf_wsum && p.lnf_nparts >= 1)) return R_NONE;
+    // MOCA_EP_GSTAT: a row tile must lie inside one statistics group
+    if ((p.flags & MOCA_EP_GSTAT) &&
+        !(p.gstat && !(p.flags & MOCA_EP_COLSUM) && p.gstat_rows > 0 && p.gstat_rows % route_info(r).tm == 0 && p.M % p.gstat_rows == 0 &&
+          (p.gstat_cpg > 0 ? (p.gstat_coff + p.N - 1) / p.gstat_cpg < 32 : (p.N % 32 == 0 && p.gstat_coff == 0)))) return R_NONE;
+    p.reserved4_ = 0;                                 // (bits 8.. carry the XCD partition chosen by the launcher)
+    // bit 0: output rows leave with non-temporal stores when the output is at least half the 256 MiB Infinity Cache (see out_streams)
+    if ((int64_t)p.M * (geglu ? p.N / 2 : p.N) * 2 >= (128ll << 20)) p.reserved4_ |= 1;
+    if (slab_f16(r, p)) p.reserved4_ |= 4;            // bit 2: fp16 split-K slabs (MOCA_TUNE_SLAB_F16; the 256-row kernel only)
+    return r;
 }
+
+// a_mode / fast_gather as template arguments: f(int_c<AMODE>, yes_t / no_t)
+template <typename F>
+int with_gather(const moca_gemm_params& p, F f) {
+    const bool fast = fast_gather(p);
+    if (p.a_mode == MOCA_A_LINEAR) return fast ? f(int_c<MOCA_A_LINEAR>{}, yes_t{}) : f(int_c<MOCA_A_LINEAR>{}, no_t{});
+    if (p.a_mode == MOCA_A_CONV3X3) return fast ? f(int_c<MOCA_A_CONV3X3>{}, yes_t{}) : f(int_c<MOCA_A_CONV3X3>{}, no_t{});
+    return fast ? f(int_c<MOCA_A_TCONV3>{}, yes_t{}) : f(int_c<MOCA_A_TCONV3>{}, no_t{});
+}
+
+int launch_route(Route r, const moca_gemm_params& p, hipStream_t st) {
+    const bool geglu = p.flags & MOCA_EP_GEGLU;
+    switch (r) {
+        case R_TATTN: return p.tattn_causal ? launch_gemm_w80s<MOCA_A_LINEAR, 3, true>(p, st) : launch_gemm_w80s<MOCA_A_LINEAR, 3>(p, st);
+        case R_WS: return moca_gemm_ws_launch(p, st);
+        case R_SQP: return geglu ? launch_gemm_sqp<true>(p, st) : launch_gemm_sqp<false>(p, st);
+        case R_G4P: return geglu ? launch_gemm_g4p<true>(p, st) : launch_gemm_g4p<false>(p, st);
+        case R_W80:
+            if (p.a2) return launch_gemm_w80s<MOCA_A_LINEAR2, 0>(p, st);
+            return with_gather(p, [&](auto am, auto) { return launch_gemm_w80s<decltype(am)::value, 0>(p, st); });
+        case R_W80W:
+            if (p.a2) return launch_gemm_w80s<MOCA_A_LINEAR2, 1>(p, st);
+            return with_gather(p, [&](auto am, auto) { return launch_gemm_w80s<decltype(am)::value, 1>(p, st); });
+        case R_SQ256: return launch_gemm_w80s<MOCA_A_LINEAR, 2>(p, st);
+        case R_G4: return with_gather(p, [&](auto am, auto fast) { return launch_gemm_g4<decltype(am)::value, decltype(fast)::value>(p, st); });
+        case R_GLDS128: return with_gather(p, [&](auto am, auto fast) { return launch_gemm_glds<128, decltype(am)::value, decltype(fast)::value>(p, st); });
+        case R_GLDS160: return with_gather(p, [&](auto am, auto fast) { return launch_gemm_glds<160, decltype(am)::value, decltype(fast)::value>(p, st); });
+        case R_SMALL128: return with_gather(p, [&](auto am, auto) { return launch_gemm<128, decltype(am)::value>(p, st); });
+        case R_SMALL64: return with_gather(p, [&](auto am, auto) { return launch_gemm<64, decltype(am)::value>(p, st); });
+        case R_NONE: break;
+    }
+    return MOCA_E_BADARG;
+}
+
+}  // namespace
+
+extern "C" int moca_gemm_route(const moca_gemm_params* pp) {
+    moca_gemm_params p;
+    return prepare(pp, p);
+}
+
+// rows per tile of the column sums a MOCA_EP_COLSUM launch leaves behind (0: this call cannot): 320 / 160 on the staggered kernel,
+// 256 on the 256-row kernel, strips of 32 rows (MOCA_EP_GSTAT only) on the weight-stationary kernel
+extern "C" int moca_gemm_colsum_rows(const moca_gemm_params* pp) {
+    moca_gemm_params p;
+    return route_info(query_route(pp, (pp && (pp->flags & MOCA_EP_GSTAT)) ? 0 : MOCA_EP_COLSUM, p)).tm;
+}
+// columns per column tile of the row sums a MOCA_EP_ROWSUM launch leaves behind (0: this call cannot)
+extern "C" int moca_gemm_rowsum_cols(const moca_gemm_params* pp) {
+    moca_gemm_params p;
+    return route_info(query_route(pp, MOCA_EP_ROWSUM, p)).tn;
+}
+extern "C" int moca_gemm_ln_ok(const moca_gemm_params* pp) {
+    moca_gemm_params p;
+    return query_route(pp, MOCA_EP_LN, p) != R_NONE;
+}
+extern "C" int moca_gemm_lnfold_ok(const moca_gemm_params* pp) {
+    moca_gemm_params p;
+    return query_route(pp, MOCA_EP_LNFOLD, p) != R_NONE;
+}
+extern "C" int moca_gemm_tattn_ok(const moca_gemm_params* pp) {
+    moca_gemm_params p;
+    return query_route(pp, MOCA_EP_TATTN, p) != R_NONE;
+}
+extern "C" int moca_gemm_cat_ok(const moca_gemm_params* pp) {
+    moca_gemm_params p;
+    return query_route(pp, 0, p) != R_NONE && p.a2;
+}
+extern "C" int moca_gemm_wgroup_ok(const moca_gemm_params* pp) {
+    moca_gemm_params p;
+    return query_route(pp, 0, p) != R_NONE && p.wgroup_rows > 0;
+}
+extern "C" int moca_gemm_splitk_groupnorm_ok(const moca_gemm_params* pp, int32_t HW, int32_t frames_per_stat) {
+    moca_gemm_params p;
+    return query_route(pp, 0, p) != R_NONE && splitk_gn_ok(p, HW, frames_per_stat);
+}
+
 extern "C" int moca_gemm_splitk_groupnorm_f16(const moca_gemm_params* pp, void* y, const float* gamma, const float* beta, int32_t HW,
                                               int32_t frames_per_stat, float eps, int32_t silu, int32_t write_x, void* stream) {
     if (!pp || !y || !gamma || !beta) return MOCA_E_BADARG;
@@ -3321,7 +3389,7 @@ extern "C" int moca_gemm_splitk_groupnorm_f16(const moca_gemm_params* pp, void* 
     if (p.ldo % 8 || (p.residual && p.ldr % 8) || (p.rowadd && (p.ld_rowadd % 8 || p.rowadd_div <= 0))) return MOCA_E_BADARG;
     normalise_splits(p);
     if (!splitk_gn_ok(p, HW, frames_per_stat)) return MOCA_E_BADARG;
-    p.reserved4_ = slab_f16(p) ? 4 : 0;
+    p.reserved4_ = slab_f16(route_of(p), p) ? 4 : 0;
     const int cpg = p.N / 32, R = HW * frames_per_stat;
     const int nchunks = R * (cpg / 8);
     const int cpt = (nchunks + 1023) / 1024;
@@ -3342,121 +3410,16 @@ extern "C" int64_t moca_gemm_splitk_ws_bytes(int32_t M, int32_t N, int32_t split
     return splits > 1 ? (int64_t)splits * M * N * 4 : 0;
 }
 
+// validate, route, check (prepare), launch
 extern "C" int moca_gemm_f16(const moca_gemm_params* pp, void* stream) {
-    if (!pp) return MOCA_E_BADARG;
-    moca_gemm_params p = *pp;
-    if (p.splits < 1) p.splits = 1;
-    if (!p.a || !p.w || !p.out) return MOCA_E_BADARG;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0) return MOCA_E_BADARG;
-    if (p.N % 64 || p.K % 8 || p.ldw % BK || p.ldw < ((p.K + BK - 1) / BK) * BK) return MOCA_E_BADARG;
-    const bool geglu = p.flags & MOCA_EP_GEGLU;
-    if (geglu && p.N % 128) return MOCA_E_BADARG;
-    if (p.ldo % 8 || (p.residual && p.ldr % 8) || (p.rowadd && (p.ld_rowadd % 8 || p.rowadd_div <= 0))) return MOCA_E_BADARG;
-    if (p.splits > 1 && !p.splitk_ws) return MOCA_E_BADARG;
-    if (p.prefetch_kib < 0 || (p.prefetch_kib > 0 && (!p.prefetch || (reinterpret_cast<uintptr_t>(p.prefetch) & 15)))) return MOCA_E_BADARG;
-    // the plain-GELU epilogue (CLIP text MLP) exists in the 128-row kernel only
-    if ((p.flags & MOCA_EP_GELU) && (geglu || p.splits != 1 || !((p.flags & MOCA_FORCE_SMALL_TILE) || p.M <= 128))) return MOCA_E_BADARG;
-    normalise_splits(p);
-    if ((p.flags & MOCA_EP_SLABS) && (p.splits < 2 || (p.flags & ~MOCA_EP_SLABS))) return MOCA_E_BADARG;   // ask moca_gemm_splitk_groupnorm_ok() first
-    if (p.up_phase && p.a_mode != MOCA_A_CONV3X3) return MOCA_E_BADARG;
-    switch (p.a_mode) {
-        case MOCA_A_LINEAR:
-            if (p.a2) {                               // ask moca_gemm_cat_ok() first
-                if (!cat_ok(p)) return MOCA_E_BADARG;
-            } else if (p.lda % 8 || p.lda < p.K) return MOCA_E_BADARG;
-            break;
-        case MOCA_A_CONV3X3:
-            if (p.up_phase < 0 || p.up_phase > 4) return MOCA_E_BADARG;
-            if (p.C % 8 || p.K != (p.up_phase ? 4 : 9) * p.C || p.inH <= 0 || p.inW <= 0 || p.outH <= 0 || p.outW <= 0) return MOCA_E_BADARG;
-            // one phase of upsample + conv: a 2 x 2 conv on the low-resolution grid, rows scattered by the plain store loop of the
-            // 256- / 320-row kernels (fast gather), nothing else in the epilogue
-            if (p.up_phase && (p.stride != 1 || p.up || p.nopad_lo || p.splits != 1 || p.M <= 160 || !fast_gather(p) || p.residual || p.rowadd ||
-                               (p.flags & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32 | MOCA_EP_COLSUM | MOCA_EP_ROWSUM | MOCA_EP_LN | MOCA_EP_LNFOLD |
-                                          MOCA_EP_TATTN | MOCA_EP_GELU | MOCA_FORCE_SMALL_TILE)) || (p.N % 128 && p.N % 160))) return MOCA_E_BADARG;
-            if (p.stride != 1 && p.stride != 2) return MOCA_E_BADARG;
-            if (p.nopad_lo != 0 && (p.nopad_lo != 1 || p.stride != 2 || p.up || (p.inH | p.inW) & 1)) return MOCA_E_BADARG;
-            if (p.up && (p.stride != 1 || p.outH != 2 * p.inH || p.outW != 2 * p.inW)) return MOCA_E_BADARG;
-            if (!p.up && p.stride == 1 && (p.outH != p.inH || p.outW != p.inW)) return MOCA_E_BADARG;
-            if (p.stride == 2 && (p.outH != (p.inH - 1) / 2 + 1 || p.outW != (p.inW - 1) / 2 + 1)) return MOCA_E_BADARG;
-            if (p.M % (p.outH * p.outW)) return MOCA_E_BADARG;
-            break;
-        case MOCA_A_TCONV3:
-            if (p.C % 8 || p.K != 3 * p.C || p.T <= 0 || p.HW <= 0 || p.M % (p.T * p.HW)) return MOCA_E_BADARG;
-            break;
-        default:
-            return MOCA_E_BADARG;
-    }
-    if (p.a2 && p.a_mode != MOCA_A_LINEAR) return MOCA_E_BADARG;
-    if (p.gstat_cpg < 0 || p.gstat_coff < 0 || ((p.gstat_cpg || p.gstat_coff) && !(p.flags & MOCA_EP_GSTAT))) return MOCA_E_BADARG;
+    moca_gemm_params p;
+    const Route r = prepare(pp, p);
+    if (r == R_NONE) return MOCA_E_BADARG;
     hipStream_t st = moca_stream(stream);
-    const bool wide = (p.N % 128 == 0);
-    int rc;
-    // large-tile direct-to-LDS kernel whenever a 256-row tile is at least half full
-    const int big_bn = (p.N % 128 == 0) ? 128 : (p.N % 160 == 0 ? 160 : 0);
-    const bool use_big = big_bn != 0 && p.M > 128 && !(p.flags & MOCA_FORCE_SMALL_TILE);
-    const bool fastp = fast_gather(p);
-    // g4 (4 waves, two blocks per CU) wins where the epilogue is VALU-heavy and K is short (GEGLU at C = 320 / 640:
-    // one block's erf-GELU epilogue runs under the other block's MFMAs, -5 % on the same device); the 8-wave kernel's
-    // deeper pipeline wins everywhere else (K >= 1280: 1137 vs 880 TFLOP/s).  MOCA_TUNE_GEMM_G4 = 0 / 2 forces never / always (tests).
-    const bool use_g4 = !(p.flags & MOCA_EP_OUT_F32) && wants_g4(p);
-    // w80 (320 x 160 tiles, 80 x 80 wave tiles): every non-GEGLU contraction whose N is a multiple of 160 and whose
-    // 320-row tiles fill the chip.  (MOCA_TUNE_GEMM_W80: 0 never, 2 drops the tile-count rule -- tests.)
-    const bool use_w80 = takes_w80(p);
-    if ((p.flags & MOCA_EP_COLSUM) && !(p.colsum && colsum_rows(p) != 0)) return MOCA_E_BADARG;   // ask moca_gemm_colsum_rows() first
-    if ((p.flags & MOCA_EP_LN) && !(p.ln_gamma && p.ln_beta && p.ln_out && p.ld_ln % 8 == 0 && takes_w80t_ln(p))) return MOCA_E_BADARG;   // ask moca_gemm_ln_ok() first
-    if (p.flags & MOCA_EP_GSTAT) {                    // same kernels as MOCA_EP_COLSUM; a row tile must lie inside one statistics group
-        const int rows = colsum_rows(p);
-        if (!(p.gstat && rows != 0 && !(p.flags & MOCA_EP_COLSUM) && p.gstat_rows > 0 && p.gstat_rows % rows == 0 && p.M % p.gstat_rows == 0 &&
-              (p.gstat_cpg > 0 ? (p.gstat_coff + p.N - 1) / p.gstat_cpg < 32 : (p.N % 32 == 0 && p.gstat_coff == 0)))) return MOCA_E_BADARG;
-    }
-    if ((p.flags & MOCA_EP_ROWSUM) && !(p.rowsum && rowsum_cols(p) != 0)) return MOCA_E_BADARG;             // ask moca_gemm_rowsum_cols() first
-    if (p.wgroup_rows < 0 || (p.wgroup_rows > 0 && !wgroup_ok(p))) return MOCA_E_BADARG;                    // ask moca_gemm_wgroup_ok() first
-    p.reserved4_ = 0;                                 // (bits 8.. carry the XCD partition chosen by the launcher)
-    // bit 0: output rows leave with non-temporal stores when the output is at least half the 256 MiB Infinity Cache (see out_streams)
-    if ((int64_t)p.M * (geglu ? p.N / 2 : p.N) * 2 >= (128ll << 20)) p.reserved4_ |= 1;
-    if (slab_f16(p)) p.reserved4_ |= 4;               // bit 2: fp16 split-K slabs (MOCA_TUNE_SLAB_F16; the 256-row kernel only)
-    if (p.flags & MOCA_EP_TATTN) {                    // ask moca_gemm_tattn_ok() first
-        if (!tattn_ok(p) || ((p.flags & MOCA_EP_LNFOLD) && !(p.lnf_part && p.lnf_wsum && p.lnf_nparts >= 1))) return MOCA_E_BADARG;
-        return p.tattn_causal ? launch_gemm_w80s<MOCA_A_LINEAR, 3, true>(p, st) : launch_gemm_w80s<MOCA_A_LINEAR, 3>(p, st);
-    }
-    if (p.tattn_causal) return MOCA_E_BADARG;         // (the mask exists in the MOCA_EP_TATTN epilogue only)
-    if ((p.flags & MOCA_EP_LNFOLD) && !(p.lnf_part && p.lnf_wsum && p.lnf_nparts >= 1 && lnfold_ok(p))) return MOCA_E_BADARG;   // ask moca_gemm_lnfold_ok() first
-    if (takes_ws(p)) {
-        rc = moca_gemm_ws_launch(p, st);
-    } else if (p.a2) {                                // (cat_ok: a staggered-kernel call)
-        rc = launch_gemm_w80_mode(p, st);
-    } else if (takes_sqp(p)) {
-        rc = (p.flags & MOCA_EP_GEGLU) ? launch_gemm_sqp<true>(p, st) : launch_gemm_sqp<false>(p, st);
-    } else if (takes_g4p(p)) {
-        rc = (p.flags & MOCA_EP_GEGLU) ? launch_gemm_g4p<true>(p, st) : launch_gemm_g4p<false>(p, st);
-    } else if (use_w80) {
-        rc = launch_gemm_w80_mode(p, st);
-    } else if (takes_sq256(p, use_g4)) {
-        rc = launch_gemm_w80s<MOCA_A_LINEAR, 2>(p, st);
-    } else if (use_big && big_bn == 128 && use_g4) {
-        if (p.a_mode == MOCA_A_LINEAR) rc = fastp ? launch_gemm_g4<MOCA_A_LINEAR, true>(p, st) : launch_gemm_g4<MOCA_A_LINEAR, false>(p, st);
-        else if (p.a_mode == MOCA_A_CONV3X3) rc = fastp ? launch_gemm_g4<MOCA_A_CONV3X3, true>(p, st) : launch_gemm_g4<MOCA_A_CONV3X3, false>(p, st);
-        else rc = fastp ? launch_gemm_g4<MOCA_A_TCONV3, true>(p, st) : launch_gemm_g4<MOCA_A_TCONV3, false>(p, st);
-    } else if (use_big && big_bn == 128) {
-        if (p.a_mode == MOCA_A_LINEAR) rc = fastp ? launch_gemm_glds<128, MOCA_A_LINEAR, true>(p, st) : launch_gemm_glds<128, MOCA_A_LINEAR, false>(p, st);
-        else if (p.a_mode == MOCA_A_CONV3X3) rc = fastp ? launch_gemm_glds<128, MOCA_A_CONV3X3, true>(p, st) : launch_gemm_glds<128, MOCA_A_CONV3X3, false>(p, st);
-        else rc = fastp ? launch_gemm_glds<128, MOCA_A_TCONV3, true>(p, st) : launch_gemm_glds<128, MOCA_A_TCONV3, false>(p, st);
-    } else if (use_big) {
-        if (p.a_mode == MOCA_A_LINEAR) rc = fastp ? launch_gemm_glds<160, MOCA_A_LINEAR, true>(p, st) : launch_gemm_glds<160, MOCA_A_LINEAR, false>(p, st);
-        else if (p.a_mode == MOCA_A_CONV3X3) rc = fastp ? launch_gemm_glds<160, MOCA_A_CONV3X3, true>(p, st) : launch_gemm_glds<160, MOCA_A_CONV3X3, false>(p, st);
-        else rc = fastp ? launch_gemm_glds<160, MOCA_A_TCONV3, true>(p, st) : launch_gemm_glds<160, MOCA_A_TCONV3, false>(p, st);
-    } else if (wide) {
-        if (p.a_mode == MOCA_A_LINEAR) rc = launch_gemm<128, MOCA_A_LINEAR>(p, st);
-        else if (p.a_mode == MOCA_A_CONV3X3) rc = launch_gemm<128, MOCA_A_CONV3X3>(p, st);
-        else rc = launch_gemm<128, MOCA_A_TCONV3>(p, st);
-    } else {
-        if (p.a_mode == MOCA_A_LINEAR) rc = launch_gemm<64, MOCA_A_LINEAR>(p, st);
-        else if (p.a_mode == MOCA_A_CONV3X3) rc = launch_gemm<64, MOCA_A_CONV3X3>(p, st);
-        else rc = launch_gemm<64, MOCA_A_TCONV3>(p, st);
-    }
+    const int rc = launch_route(r, p, st);
     if (rc != MOCA_OK) return rc;
     if (p.splits > 1 && !(p.flags & MOCA_EP_SLABS)) {
-        const int out_n = geglu ? p.N / 2 : p.N;
+        const int out_n = (p.flags & MOCA_EP_GEGLU) ? p.N / 2 : p.N;
         const int64_t total = (int64_t)p.M * (out_n / 8);
         int blocks = (int)((total + 255) / 256);
         if (blocks > 2048) blocks = 2048;

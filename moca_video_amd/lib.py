@@ -25,6 +25,8 @@ MOCA_EP_ROWSUM, MOCA_EP_LNFOLD, MOCA_EP_GSTAT, MOCA_EP_TATTN, MOCA_EP_SLABS = 64
 MOCA_TUNE_GEMM_W80, MOCA_TUNE_GEMM_G4, MOCA_TUNE_GEMM_SQ256, MOCA_TUNE_GEMM_WIDE, MOCA_TUNE_GN_SLAB, MOCA_TUNE_GEMM_G4P, MOCA_TUNE_GEMM_MF32, MOCA_TUNE_GEMM_SQP, MOCA_TUNE_SQP_WALK = 0, 1, 2, 3, 4, 5, 6, 7, 8
 MOCA_TUNE_SLAB_F16 = 9
 MOCA_TUNE_GEMM_WS = 10
+(MOCA_ROUTE_SMALL64, MOCA_ROUTE_SMALL128, MOCA_ROUTE_GLDS128, MOCA_ROUTE_GLDS160, MOCA_ROUTE_G4, MOCA_ROUTE_W80, MOCA_ROUTE_W80W,
+ MOCA_ROUTE_SQ256, MOCA_ROUTE_G4P, MOCA_ROUTE_SQP, MOCA_ROUTE_TATTN, MOCA_ROUTE_WS) = range(1, 13)
 
 _ERR = {0: "ok", -1: "bad argument (shape/alignment contract)", -2: "HIP launch/runtime error",
         -3: "no gfx950 device", -4: "graph capture/replay failed"}
@@ -88,6 +90,7 @@ SIGNATURES = {
     "moca_gemm_tattn_ok": (C.c_int, [C.POINTER(GemmParams)]),
     "moca_gemm_cat_ok": (C.c_int, [C.POINTER(GemmParams)]),
     "moca_gemm_wgroup_ok": (C.c_int, [C.POINTER(GemmParams)]),
+    "moca_gemm_route": (C.c_int, [C.POINTER(GemmParams)]),
     "moca_groupnorm_fold_weights_f16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _f32, _vp]),
     "moca_gemm_splitk_groupnorm_ok": (C.c_int, [C.POINTER(GemmParams), _i32, _i32]),
     "moca_gemm_splitk_groupnorm_f16": (C.c_int, [C.POINTER(GemmParams), _vp, _vp, _vp, _i32, _i32, _f32, _i32, _i32, _vp]),

@@ -252,6 +252,12 @@ def gemm_wgroup_ok(a, pw: PackedWeight, **kw):
     return bool(_l.load().moca_gemm_wgroup_ok(C.byref(p)))
 
 
+def gemm_route(a, pw: PackedWeight, out=None, **kw):
+    """the kernel family gemm(a, pw, out, **kw) would run on (lib.MOCA_ROUTE_*), 0 where it would be refused (without `out`: always)"""
+    p = _gemm_params(a, pw, out, **kw)
+    return int(_l.load().moca_gemm_route(C.byref(p)))
+
+
 def groupnorm_fold_weights(pw: PackedWeight, gamma, beta, gstat, wg, bg, *, n_sg, count, eps):
     """wg fp16 [n_sg * N][ldw], bg f32 [n_sg * N] = the weights / bias of `Linear(GroupNorm(x))` per statistics group, from the finished
     statistics of a MOCA_EP_GSTAT producer (include/moca_hip.h); returns them as a PackedWeight for `gemm(..., wgroup=(rows, N * ldw))`"""

@@ -56,6 +56,15 @@ PERSISTENT = {
 }
 # (M, N, K) per persistent kernel: the existing tests' minimum tile counts with an M tail, K = 64
 PERSISTENT_SHAPE = {"g4p": (8200, 2048, 64), "g4q": (8200, 2048, 64), "sqp": (8200, 2048, 64), "sq256": (4100, 3072, 64)}
+# ops.gemm_route's answer per route; tile = (rows, columns) as gemm_colsum_rows / gemm_rowsum_cols report it (the weight-stationary
+# kernel: rows per strip, columns per wave)
+ROUTE_ID = {"small64": L.MOCA_ROUTE_SMALL64, "small128": L.MOCA_ROUTE_SMALL128, "glds128": L.MOCA_ROUTE_GLDS128, "glds160": L.MOCA_ROUTE_GLDS160,
+            "g4": L.MOCA_ROUTE_G4, "w80": L.MOCA_ROUTE_W80, "w80w": L.MOCA_ROUTE_W80W, "ws": L.MOCA_ROUTE_WS,
+            "g4p": L.MOCA_ROUTE_G4P, "g4q": L.MOCA_ROUTE_G4P, "sqp": L.MOCA_ROUTE_SQP, "sq256": L.MOCA_ROUTE_SQ256}
+ROUTE_TILE = {L.MOCA_ROUTE_SMALL64: (128, 64), L.MOCA_ROUTE_SMALL128: (128, 128), L.MOCA_ROUTE_GLDS128: (256, 128),
+              L.MOCA_ROUTE_GLDS160: (256, 160), L.MOCA_ROUTE_G4: (256, 128), L.MOCA_ROUTE_W80: (320, 160), L.MOCA_ROUTE_W80W: (160, 320),
+              L.MOCA_ROUTE_SQ256: (256, 256), L.MOCA_ROUTE_G4P: (256, 128), L.MOCA_ROUTE_SQP: (256, 256), L.MOCA_ROUTE_TATTN: (320, 192),
+              L.MOCA_ROUTE_WS: (32, 80)}
 # (k-tiles, requested splits) -> the factor normalise_splits leaves
 SPLIT_CASES = {(5, 4): 3, (3, 8): 3, (2, 2): 2, (7, 3): 3}
 
@@ -71,19 +80,6 @@ def route_Ns(route):
 def route_Ks(route):
     spec = ROUTES[route]
     return (spec["K"],) if "K" in spec else FAST_KS + (SLOW_KS if spec["slow"] else ())
-
-
-def persistent_ok(name, M, N, K, lda, *, geglu=False, residual=False, rowadd=False, splits=1, other_flags=False):
-    """g4p_ok / sqp_ok / takes_sq256 of csrc/gemm.hip restated.  No host query tells a persistent kernel from the kernel the call would
-    fall to (both carry the LayerNorm fold, neither column sums on the persistent side), so the GPU file asserts the preconditions."""
-    tm, tn = PERSISTENT[name]["tile"]
-    if splits != 1 or other_flags or K % 64 or N % tn or a_span_bytes_linear(M, lda) >= 1 << 31 or N * ((K + 63) // 64 * 64) * 2 >= 1 << 31:
-        return False
-    if name == "sq256":
-        return N >= 2560 and M >= 512 and persistent_tiles(name, M, N) >= 200 and not (N % 160 == 0 and not geglu)
-    if geglu and (residual or rowadd):
-        return False
-    return persistent_tiles(name, M, N) >= PERSISTENT[name]["min_tiles"]
 
 
 def persistent_tiles(name, M, N):
@@ -374,3 +370,165 @@ def expected_signature(route, *, linear=True, plain=True):
     if not plain:
         cs, rs, lf = 0, 0, lf
     return cs, rs, (lf if linear else None)
+
+
+# ---------------------------------------------------------------- the query sweep (host only)
+SWEEP_M = tuple(sorted({m for spec in ROUTES.values() for m in spec["M"]} | {v[0] for v in PERSISTENT_SHAPE.values()} | {1 << 16, 1 << 17}))
+SWEEP_N = (64, 128, 320, 640, 960, 1280, 2048, 3072)
+SWEEP_K = (8, 64, 72, 192, 320, 328)
+SWEEP_K_EPI = (64, 192, 328)                      # the epilogue / side-input variants: one k-tile, three, and a slow-gather K
+SWEEP_EPILOGUES = ("colsum", "gstat", "rowsum", "ln", "lnfold", "geglu", "gelu", "out_f32", "force_small", "splits2", "splits3",
+                   "residual", "rowadd", "a2", "wgroup640", "wgroup4096")
+FLAG_QUERIES = {"colsum_rows": L.MOCA_EP_COLSUM, "rowsum_cols": L.MOCA_EP_ROWSUM, "ln_ok": L.MOCA_EP_LN, "lnfold_ok": L.MOCA_EP_LNFOLD,
+                "tattn_ok": L.MOCA_EP_TATTN}
+QUERIES = tuple(FLAG_QUERIES) + ("wgroup_ok", "cat_ok", "splitk_groupnorm_ok")
+_SCRATCH = {}
+
+
+def sweep_knob_sets():
+    """the defaults, then each distinct knob set of ROUTES and PERSISTENT"""
+    out = [{}]
+    for spec in list(ROUTES.values()) + list(PERSISTENT.values()):
+        if spec["knobs"] not in out:
+            out.append(spec["knobs"])
+    return out
+
+
+def _t(n=8, dtype=torch.float16):
+    """a small host tensor: the queries and gemm_route read pointers and strides, never memory"""
+    key = (n, dtype)
+    if key not in _SCRATCH:
+        _SCRATCH[key] = torch.empty(1, n, dtype=dtype)
+    return _SCRATCH[key]
+
+
+def _pw(N, K, geglu=False):
+    return _ops().PackedWeight(_t((K + BK - 1) // BK * BK), _t(N, torch.float32), N, K, N // 2 if geglu else N, geglu)
+
+
+def _ops():
+    from moca_video_amd import ops
+    return ops
+
+
+def sweep_calls():
+    """(label, GemmParams of the launch: every pointer set) over the grid both the permanent test and the differential walk:
+    linears M x N x K plain, M x N x SWEEP_K_EPI under each epilogue / split count / side input, helpers.wgroup_cases' shapes at
+    N = K = 320, and the conv / tconv geometries of GEOS x N x C in (64, 8) x (plain, colsum, gstat, out_f32, force_small, splits2)"""
+    from helpers import wgroup_cases
+    ops = _ops()
+    f32 = torch.float32
+
+    def linear(M, N, K, epi):
+        kw, geglu = dict(M=M), epi == "geglu"
+        if epi == "colsum":
+            kw["colsum"] = _t(8, f32)
+        elif epi == "gstat":
+            kw["gstat"] = (_t(8, torch.int64), M)
+        elif epi == "rowsum":
+            kw["rowsum"] = _t(8, f32)
+        elif epi == "ln":
+            kw["ln"] = (_t(N, f32), _t(N, f32), _t(N), 1e-5)
+        elif epi == "lnfold":
+            kw["lnfold"] = (_t(8, f32), 1, 1e-5)
+        elif epi in ("gelu", "out_f32", "force_small"):
+            kw[epi] = True
+        elif epi in ("splits2", "splits3"):
+            kw.update(splits=int(epi[-1]), splitk_ws=_t(8, f32))
+        elif epi in ("residual", "rowadd"):
+            kw[epi] = _t(N)
+        elif epi == "a2":
+            kw["a2"] = (_t(max(K - 64, 8)), 64)
+        elif epi.startswith("wgroup"):
+            kw["wgroup"] = (int(epi[6:]), N * ((K + BK - 1) // BK * BK))
+        pw = _pw(N, K, geglu)
+        pw.wsum = _t(N, f32)
+        p = ops._gemm_params(_t(K), pw, _t(N // 2 if geglu else N, f32 if epi == "out_f32" else torch.float16), **kw)
+        p.T, p.HW, p.tattn_scale = 16, 20, 0.125          # (read by the MOCA_EP_TATTN question alone)
+        return p
+
+    for M in SWEEP_M:
+        for N in SWEEP_N:
+            for K in SWEEP_K:
+                yield ("linear", M, N, K, "plain"), linear(M, N, K, "plain")
+            for K in SWEEP_K_EPI:
+                for epi in SWEEP_EPILOGUES:
+                    yield ("linear", M, N, K, epi), linear(M, N, K, epi)
+    for rows, M, res, _, flag in sorted(set((c[0], c[1], c[2], 0, c[4]) for c in wgroup_cases())):
+        kw = dict(M=M, residual=_t(320) if res else None, wgroup=(rows, 320 * 320))
+        if flag == "rowsum":
+            kw["rowsum"] = _t(8, f32)
+        elif flag == "ln":
+            kw["ln"] = (_t(320, f32), _t(320, f32), _t(320), 1e-5)
+        elif flag == "colsum":
+            kw["colsum"] = _t(8, f32)
+        yield ("wgroup", M, rows, res, flag), ops._gemm_params(_t(320), _pw(320, 320), _t(320), **kw)
+    for name, geo in GEOS.items():
+        M = geo_M(geo)
+        for N in SWEEP_N:
+            for C in (64, 8):
+                for epi in ("plain", "colsum", "gstat", "out_f32", "force_small", "splits2"):
+                    kw = dict(M=M)
+                    if geo["kind"] == "tconv":
+                        kw.update(mode=L.MOCA_A_TCONV3, tconv=(C, geo["T"], geo["HW"]))
+                        pw = _pw(N, 3 * C)
+                    else:
+                        oh, ow = geo_out(geo)
+                        kw.update(mode=L.MOCA_A_CONV3X3, conv=(C, geo["H"], geo["W"], oh, ow, geo["stride"], geo["up"], geo["nopad"]))
+                        pw = _pw(N, 9 * C)
+                    if epi == "colsum":
+                        kw["colsum"] = _t(8, f32)
+                    elif epi == "gstat":
+                        kw["gstat"] = (_t(8, torch.int64), M)
+                    elif epi == "splits2":
+                        kw.update(splits=2, splitk_ws=_t(8, f32))
+                    elif epi != "plain":
+                        kw[epi] = True
+                    yield (name, M, N, C, epi), ops._gemm_params(_t(C), pw, _t(N, f32 if epi == "out_f32" else torch.float16), **kw)
+
+
+def flagged(p, query):
+    """the call a query asks about, as a launch: its flag added, the flag's outputs / inputs pointed somewhere"""
+    q = L.GemmParams.from_buffer_copy(p)
+    ptr = _t(8, torch.float32).data_ptr()
+    if query == "colsum_rows" and not (q.flags & L.MOCA_EP_GSTAT):
+        q.flags |= L.MOCA_EP_COLSUM
+        q.colsum = ptr
+    elif query == "rowsum_cols":
+        q.flags |= L.MOCA_EP_ROWSUM
+        q.rowsum = ptr
+    elif query == "ln_ok":
+        q.flags |= L.MOCA_EP_LN
+        q.ln_gamma = q.ln_beta = q.ln_out = ptr
+        q.ld_ln = q.N
+    elif query == "lnfold_ok":
+        q.flags |= L.MOCA_EP_LNFOLD
+        q.lnf_part = q.lnf_wsum = ptr
+        q.lnf_nparts = 1
+    elif query == "tattn_ok":
+        q.flags |= L.MOCA_EP_TATTN
+    elif query == "splitk_groupnorm_ok":
+        q.flags |= L.MOCA_EP_SLABS
+    return q
+
+
+def ask(query, p):
+    """one of QUERIES on the call p, as moca_video_amd.ops asks it (splitk_groupnorm_ok: MOCA_EP_SLABS added, one statistics group of
+    M rows)"""
+    lib = L.load()
+    if query == "splitk_groupnorm_ok":
+        return int(lib.moca_gemm_splitk_groupnorm_ok(flagged(p, query), p.M, 1))
+    return int(getattr(lib, "moca_gemm_" + query)(p))
+
+
+def query_sweep(visit):
+    """visit(knobs, label, p) for every call of sweep_calls() under every knob set, the knobs set and restored around it"""
+    calls = list(sweep_calls())
+    for knobs in sweep_knob_sets():
+        old = {k: L.set_tuning(k, v) for k, v in knobs.items()}
+        try:
+            for label, p in calls:
+                visit(knobs, label, p)
+        finally:
+            for k, v in old.items():
+                L.set_tuning(k, v)

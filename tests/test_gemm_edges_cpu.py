@@ -1,8 +1,14 @@
 """CPU: the route table and the references of tests/test_gemm_edges_gpu.py check themselves (tests/gemm_edges_ref.py).
 
-  test_route_table ..................... every (route, M, gather) of the GPU file gives the host-query signature of the kernel it is
-                                         meant for under the route's knobs (a dispatch rule that changes moves the case visibly)
-  test_persistent_routes ............... the shapes of the persistent kernels hold the tile counts those kernels ask for
+  test_route_table ..................... every (route, M, gather) of the GPU file runs on the kernel it is meant for under the route's
+                                         knobs (ops.gemm_route) and gives that kernel's host-query signature (a dispatch rule that
+                                         changes moves the case visibly)
+  test_persistent_routes ............... the shapes of the persistent kernels run on those kernels, hold the tile counts they ask for,
+                                         and leave them with split-K or eight row tiles fewer
+  test_queries_follow_the_route ........ over gemm_edges_ref.query_sweep (shapes x gathers x epilogues x side inputs x knob sets): a
+                                         flag's query says yes exactly where the launch of the call with that flag is accepted, and
+                                         reports the tile of the kernel that launch runs on
+  test_wgroup_skips_persistent_kernels . per-row-group weights never run on a kernel that has none
   test_geometry_cases_tell_errors ...... at every geometry case's shape and seed each wrong float64 restatement that applies
                                          (symmetric pad, stride-2 sampling off by one, upsample halved on one axis, no zeroing across a
                                          video boundary, row add off by one row) exceeds TOL16: the shapes are not too small or symmetric
@@ -38,6 +44,11 @@ def _host_case(kind, M, N, C, geo=None):
         dict(mode=L.MOCA_A_CONV3X3, conv=(C, geo["H"], geo["W"], oh, ow, geo["stride"], geo["up"], geo["nopad"]))
 
 
+def _out(n):
+    """an output of n columns (gemm_route reads its pointer and row stride)"""
+    return torch.empty(1, n, dtype=torch.float16)
+
+
 @pytest.mark.parametrize("route", list(R.ROUTES))
 def test_route_table(route, tune):
     spec = R.ROUTES[route]
@@ -49,6 +60,7 @@ def test_route_table(route, tune):
                 a, pw, kw = _host_case("linear", M, N, K)
                 got = R.signature(route, a, pw, M=M, force_small=R.needs_force_small(route, M), **kw)
                 assert got == R.expected_signature(route), (route, M, N, K, got)
+                assert ops.gemm_route(a, pw, _out(N), M=M, force_small=R.needs_force_small(route, M), **kw) == R.ROUTE_ID[route], (route, M, N, K)
     N = spec["N"]
     if spec["conv"]:
         for name, geo in R.GEOS.items():
@@ -57,9 +69,11 @@ def test_route_table(route, tune):
                 a, pw, kw = _host_case(geo["kind"], M, N, C, geo)
                 got = R.signature(route, a, pw, M=M, force_small=R.needs_force_small(route, M), **kw)
                 assert got == R.expected_signature(route, linear=False), (route, name, C, got)
+                assert ops.gemm_route(a, pw, _out(N), M=M, force_small=R.needs_force_small(route, M), **kw) == R.ROUTE_ID[route], (route, name, C)
     if route == "ws":                                  # M = 32: refused by the weight-stationary kernel, runs on the 128-row kernel
         a, pw, kw = _host_case("linear", 32, N, spec["K"])
         assert R.signature("small128", a, pw, M=32) == (0, 0, False)
+        assert ops.gemm_route(a, pw, _out(N), M=32) == R.ROUTE_ID["small64"]      # (N = 320: 64-column tiles)
     # split-K, fp32 output: no statistics epilogue on any route
     if route in R.SPLIT_ROUTES:
         a, pw, kw = _host_case("linear", spec["M"][-1], N, 192)
@@ -77,12 +91,69 @@ def test_persistent_routes(name, tune):
     assert R.persistent_tiles(name, M, N) >= spec["min_tiles"] and M % spec["tile"][0] != 0, "enough tiles for the kernel, and an M tail"
     a, pw, kw = _host_case("linear", M, N, K)
     assert ops.gemm_lnfold_ok(a, pw, M=M, lnfold=(None, 1, 1e-5)), "every persistent kernel carries the LayerNorm fold"
-    assert R.persistent_ok(name, M, N, K, K + 24) and R.persistent_ok(name, M, N, K, K + 24, geglu=True)
-    assert not R.persistent_ok(name, M, N, K, K + 24, splits=2) and not R.persistent_ok(name, M - 8 * spec["tile"][0], N, K, K + 24)
+    want = R.ROUTE_ID[name]
+    a = torch.empty(1, K + 24, dtype=torch.float16)[:, :K]            # (lda = K + 24, as the GPU file embeds A)
+    pwg = ops.PackedWeight(pw.w, pw.bias, pw.N, pw.K, pw.N // 2, geglu=True)
+    assert ops.gemm_route(a, pw, _out(N), M=M) == want and ops.gemm_route(a, pwg, _out(N // 2), M=M) == want
+    # the call leaves the kernel, for another one, with two splits (K = 128: at K = 64 normalise_splits leaves one) or 8 row tiles fewer.
+    # (The 256 x 256 staggered kernel is not persistent: it has split-K, and its tile count takes the splits in.)
+    a2, pw2, _ = _host_case("linear", M, N, 128)
+    assert ops.gemm_route(a2, pw2, _out(N), M=M) == want
+    split = ops.gemm_route(a2, pw2, _out(N), M=M, splits=2, splitk_ws=torch.empty(1))
+    assert split == want if name == "sq256" else split not in (0, want)
+    assert ops.gemm_route(a, pw, _out(N), M=M - 8 * spec["tile"][0]) not in (0, want)
     if name == "sq256":                                # the 256 x 256 staggered kernel has no column sums; the 256-row kernel it replaces has
         assert ops.gemm_colsum_rows(a, pw, M=M) == 0
         tune(R.SQ256, 0)
         assert ops.gemm_colsum_rows(a, pw, M=M) == 256
+
+
+def test_queries_follow_the_route():
+    lib = L.load()
+    seen, routes = dict.fromkeys(R.QUERIES, 0), set()
+
+    def visit(knobs, label, p):
+        what = (knobs, label)
+        for q in R.FLAG_QUERIES:
+            ans, route = R.ask(q, p), lib.moca_gemm_route(R.flagged(p, q))
+            seen[q] += ans != 0
+            routes.add(route)
+            if q == "colsum_rows" and (p.flags & L.MOCA_EP_GSTAT) and ans and p.M % ans:
+                assert route == 0, (q, what)           # (the sweep's one statistics group of M rows is not whole row tiles)
+                continue
+            assert (ans != 0) == (route != 0), (q, ans, route, what)
+            if q == "colsum_rows":
+                assert ans == (R.ROUTE_TILE[route][0] if route else 0), (q, ans, route, what)
+            elif q == "rowsum_cols":
+                assert ans == (R.ROUTE_TILE[route][1] if route else 0), (q, ans, route, what)
+            elif q == "tattn_ok":
+                assert route in (0, L.MOCA_ROUTE_TATTN), (q, route, what)
+        route = lib.moca_gemm_route(p)
+        routes.add(route)
+        wg, cat, skgn = R.ask("wgroup_ok", p), R.ask("cat_ok", p), R.ask("splitk_groupnorm_ok", p)
+        assert wg == (p.wgroup_rows > 0 and route != 0) and cat == (bool(p.a2) and route != 0), (wg, cat, route, what)
+        assert not skgn or lib.moca_gemm_route(R.flagged(p, "splitk_groupnorm_ok")) != 0, what
+        for q, v in (("wgroup_ok", wg), ("cat_ok", cat), ("splitk_groupnorm_ok", skgn)):
+            seen[q] += v != 0
+    R.query_sweep(visit)
+    assert all(seen.values()), f"a query never said yes: {seen}"
+    assert routes == set(R.ROUTE_TILE) | {0}, f"routes the sweep never reached: {set(R.ROUTE_TILE) - routes}"
+
+
+@pytest.mark.parametrize("knobs", [{R.SQP: 2, R.G4P: 0, R.WS: 0}, {R.SQP: 0, R.G4P: 2, R.WS: 0}], ids=["sqp", "g4p"])
+def test_wgroup_skips_persistent_kernels(knobs, tune):
+    """M = 13440 = two groups of 42 x 160 rows, N = 1280, K = 64: 265 / 530 tiles, enough for either persistent kernel -- which would
+    run group 1's rows against group 0's weights.  The call runs where gemm_wgroup_ok has always said it does: the 160 x 320 tiling."""
+    for k, v in knobs.items():
+        tune(k, v)
+    M, N, K = 13440, 1280, 64
+    a, pw, _ = _host_case("linear", M, N, K)
+    name = "sqp" if knobs[R.SQP] else "g4p"
+    assert R.persistent_tiles(name, M, N) >= R.PERSISTENT[name]["min_tiles"]
+    assert ops.gemm_route(a, pw, _out(N), M=M) == R.ROUTE_ID[name]
+    wgroup = (M // 2, N * pw.w.stride(0))
+    assert ops.gemm_wgroup_ok(a, pw, M=M, wgroup=wgroup)
+    assert ops.gemm_route(a, pw, _out(N), M=M, wgroup=wgroup) == L.MOCA_ROUTE_W80W
 
 
 @pytest.mark.parametrize("name", list(R.GEOS))

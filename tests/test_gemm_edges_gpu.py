@@ -10,6 +10,7 @@ Which gap of the kernel-level suite each test closes:
   2. lda > K, ldo > N, ldr > N, ld_rowadd > N, pad columns, guard rows .. test_strides_pad_columns_guard_rows,
      (lda = 2c with fp32 output; GEGLU with ldo = N / 2 + 8;              test_strides_vae_scores_f32, test_strides_geglu,
       the persistent kernels) ..........................................  test_persistent_routes_strides_and_epilogues
+     (per-row-group weights under the persistent kernels' knobs) ...... test_wgroup_never_on_persistent_kernels
   3. row add on w80 (both tilings), g4, the 128-row kernel, the split-K
      reduce; rowadd_div straddling row tiles .......................... test_epilogue_matrix
      (the same on sq256 / g4p / g4q / sqp) ............................ test_persistent_routes_strides_and_epilogues
@@ -24,9 +25,8 @@ Which gap of the kernel-level suite each test closes:
   9. column / row statistics at an M tail ............................. test_statistics_at_m_tail
  (I) every statistics / fold flag: query 0 <-> launch refused ......... test_query_and_launch_agree
 
-Every case asserts, through the host queries, that it runs on the kernel it is meant for (gemm_edges_ref.ROUTES, checked without a device
-by tests/test_gemm_edges_cpu.py).  The persistent kernels (g4p, g4q, sqp, sq256) are the exception: no query tells them from the kernel
-a call would fall to, so their cases assert the dispatcher's preconditions restated in Python (gemm_edges_ref.persistent_ok).
+Every case asserts, through ops.gemm_route and the host queries, that it runs on the kernel it is meant for (gemm_edges_ref.ROUTES /
+PERSISTENT, checked without a device by tests/test_gemm_edges_cpu.py).
 B, C, D, G and I run every route at two column counts (gemm_edges_ref.ROUTES: N and N2, up to six column tiles)."""
 import functools
 
@@ -100,12 +100,13 @@ def pack(case, geo=None, act=None):
 
 
 def assert_route(route, a, pw, M, kw, residual=False, rowadd=False, splits=1):
-    """the plain form of this call (fp16 output, one split, no activation) has the signature of the route's kernel; a persistent
-    kernel's case meets the preconditions of that kernel (the call as it is launched)"""
+    """the plain form of this call (fp16 output, one split, no activation) runs on the route's kernel and has its signature; a
+    persistent kernel's case runs on that kernel as it is launched"""
+    d = torch.empty(1, pw.N, dtype=torch.float16)      # (output / residual / row add of the question: read for pointer and row stride only)
     if route in R.PERSISTENT:
-        other = any(k in kw for k in ("colsum", "rowsum", "gstat", "gelu", "force_small", "ln", "mode", "up_phase"))
-        assert R.persistent_ok(route, M, pw.N, pw.K, a.stride(0), geglu=pw.geglu, residual=residual, rowadd=rowadd, splits=splits,
-                               other_flags=other), f"{route}: M={M} N={pw.N} K={pw.K} does not meet the kernel's preconditions"
+        got = ops.gemm_route(a, pw, d, M=M, residual=d if residual else None, rowadd=d if rowadd else None, splits=splits,
+                             splitk_ws=d if splits > 1 else None, **kw)
+        assert got == R.ROUTE_ID[route], f"{route}: M={M} N={pw.N} K={pw.K} runs on route {got}"
         assert route != "sq256" or ops.gemm_colsum_rows(a, pw, M=M) == 0      # (the 256-row kernel it replaces would answer 256)
         return
     plain = {k: v for k, v in kw.items() if k in ("mode", "conv", "tconv", "force_small")}
@@ -115,6 +116,10 @@ def assert_route(route, a, pw, M, kw, residual=False, rowadd=False, splits=1):
     linear = "mode" not in kw
     got = R.signature(route, a, pwq, M=M, **plain)
     assert got == R.expected_signature(route, linear=linear), f"{route}: M={M} N={pw.N} K={pw.K} runs on another kernel: {got}"
+    if "up_phase" in kw:                               # (K = 4 C: a launch only as a phase; the queries do not look at the operand shape)
+        plain["up_phase"] = kw["up_phase"]
+    got = ops.gemm_route(a, pwq, d, M=M, **plain)
+    assert got == R.ROUTE_ID[route], f"{route}: M={M} N={pw.N} K={pw.K} runs on route {got}"
 
 
 def launch(route, case, *, geo=None, C=None, act=None, embed=True, splits=1, out_f32=False, alias=False, lda_pad=24, a_dev=None,
@@ -212,7 +217,7 @@ def test_index_probe(route, gather, tune):
             pw = ops.pack_linear(w2d, None)
             a = x.to(DEV).reshape(-1, C)
             kw = geo_kw(geo, C, up_phase=phase)
-            assert_route(route, a, pw, Fr * H * W, kw)
+            assert_route(route, a, pw, Fr * H * W, dict(kw, up_phase=phase))
             ops.gemm(a, pw, out.view(-1, N), M=Fr * H * W, up_phase=phase, **kw)
             assert torch.equal(out[:, a_::2, b_::2].double().cpu(), exp), f"probe {route} up_phase {phase}"
             written = torch.zeros(2 * H, 2 * W, dtype=torch.bool, device=DEV)
@@ -380,6 +385,34 @@ def test_persistent_routes_strides_and_epilogues(route, tune):
     case = lin_case(481, M, N, K, True, 0, False, "geglu")
     out, obuf, _ = launch(route, case, act="geglu")
     check(out, obuf, case, f"persistent {route} geglu", "C")
+
+
+@pytest.mark.parametrize("name", ["sqp", "g4p"])
+def test_wgroup_never_on_persistent_kernels(name, tune):
+    """Per-row-group weights under the knobs that send every linear they can run to a persistent kernel: M = 13440 = two groups of
+    6720 = 42 x 160 rows, N = 1280, K = 64 -- the smallest shape both persistent kernels accept (265 / 530 tiles against 256 / 512).
+    Neither kernel reads wgroup_rows, so the call stays on the 160 x 320 tiling, where gemm_wgroup_ok says it runs; on a persistent
+    kernel group 1's rows would meet group 0's weights (an O(1) error).  Each group against float64 of its own weights and bias."""
+    take(tune, name)
+    M, N, K = 13440, 1280, 64
+    rows = M // 2
+    g = R.gen(490)
+    a = R.randh(g, M, K)
+    w = [R.randh(g, N, K, scale=K ** -0.5) for _ in range(2)]
+    b = [torch.randn(N, generator=g) for _ in range(2)]
+    pws = [ops.pack_linear(w[i], b[i]) for i in range(2)]
+    pw = ops.PackedWeight(torch.cat([p.w for p in pws]), torch.cat([p.bias for p in pws]), N, K, N)
+    wgroup = (rows, N * pw.w.stride(0))
+    ad = a.to(DEV)
+    obuf, out = R.canary_out(M, N, DEV)
+    assert ops.gemm_route(ad, pws[0], out, M=M) == R.ROUTE_ID[name], "without the groups the persistent kernel takes the call"
+    assert ops.gemm_wgroup_ok(ad, pw, M=M, wgroup=wgroup)
+    assert ops.gemm_route(ad, pw, out, M=M, wgroup=wgroup) == L.MOCA_ROUTE_W80W
+    ops.gemm(ad, pw, out, M=M, wgroup=wgroup)
+    for i in range(2):
+        ref = R.epilogue(R.ref_linear(a[i * rows:(i + 1) * rows], w[i]), b[i])
+        R.check_blocks(out[i * rows:(i + 1) * rows], ref, f"wgroup under the {name} knobs, group {i}", group="C")
+    R.assert_canary(obuf, M, N, f"wgroup under the {name} knobs")
 
 
 # ---------------------------------------------------------------- D. split-K

@@ -8,6 +8,12 @@ stream inside the MFMA segment: what hipcc inserts when it cannot prove an LDS a
 register that is a known load destination is rewritten).
 
     python tools/isa_report.py [libmoca_hip.so] [name filter ...]
+    python tools/isa_report.py --diff OLD NEW      (two builds of the library or of one object file, e.g. csrc/gemm.o)
+
+`--diff` is the check of a host-only change: the same kernel symbols, per kernel the same instruction encodings and the same register /
+LDS / scratch figures.  Moving host code moves the kernels inside the code object, so two things may differ and are counted, not
+failed: the 32-bit literal of an `s_add_u32` (a pc-relative offset to another symbol) and the padding behind a kernel's last
+instruction.  Exit status 1 on any other difference.
 
 `analyse(lib_path)` is what tests/test_isa_cpu.py calls."""
 import os
@@ -254,8 +260,73 @@ def analyse(lib_path=None):
     return res
 
 
+_ENC = re.compile(r"^\s+(\S+)\s*(.*?)\s*//\s*[0-9A-Fa-f]+:((?:\s+[0-9A-Fa-f]{8})+)\s*$")
+_PAD = {"00000000", "BF800000", "BF9F0000"}            # zero fill, s_nop 0, s_code_end
+_FIGURES = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size",
+            "private_segment_fixed_size")
+
+
+def encodings(path):
+    """({symbol: [(mnemonic, encoding words)] without trailing padding}, {kernel: register / LDS / scratch figures}) of every gfx950
+    code object inside `path`"""
+    syms, figs = {}, {}
+    with tempfile.TemporaryDirectory() as wd:
+        for co in code_objects(path, wd):
+            for name, info in metadata(co).items():
+                figs[name] = {k: info.get(k, 0) for k in _FIGURES}
+            out = subprocess.run([f"{LLVM}/llvm-objdump", "-d", co], check=True, capture_output=True, text=True).stdout
+            cur = None
+            for line in out.splitlines():
+                m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
+                if m:
+                    cur = syms.setdefault(m.group(1), [])
+                    continue
+                m = _ENC.match(line)
+                if m and cur is not None:
+                    cur.append((m.group(1), tuple(w.upper() for w in m.group(3).split())))
+    for ins in syms.values():
+        while ins and all(w in _PAD for w in ins[-1][1]):
+            ins.pop()
+    return syms, figs
+
+
+def diff(old, new):
+    """compare two builds kernel by kernel; returns the number of differences that a host-only change cannot explain"""
+    (so, fo), (sn, fn) = encodings(old), encodings(new)
+    bad = 0
+    for name in sorted(set(so) ^ set(sn)):
+        print(f"only in {'OLD' if name in so else 'NEW'}: {name}")
+        bad += 1
+    literals = touched = 0
+    for name in sorted(set(so) & set(sn)):
+        a, b = so[name], sn[name]
+        if len(a) != len(b):
+            print(f"{name}: {len(a)} instructions -> {len(b)}")
+            bad += 1
+            continue
+        lit = 0
+        for i, ((ma, ea), (mb, eb)) in enumerate(zip(a, b)):
+            if ea == eb:
+                continue
+            if ma == mb == "s_add_u32" and len(ea) == len(eb) == 2 and ea[0] == eb[0]:
+                lit += 1                               # the same instruction with another 32-bit literal: a pc-relative symbol offset
+            else:
+                print(f"{name}: instruction {i}: {ma} {' '.join(ea)} -> {mb} {' '.join(eb)}")
+                bad += 1
+        literals += lit
+        touched += lit > 0
+        if fo.get(name) != fn.get(name):
+            print(f"{name}: figures {fo.get(name)} -> {fn.get(name)}")
+            bad += 1
+    print(f"{len(set(so) & set(sn))} symbols in both ({len(fo)} kernels with metadata), {touched} differ in {literals} s_add_u32 literals, "
+          f"{bad} other differences")
+    return bad
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if args and args[0] == "--diff":
+        sys.exit(1 if diff(args[1], args[2]) else 0)
     lib = args.pop(0) if args and args[0].endswith(".so") else None
     r = analyse(lib)
     print(f"{'kernel':46s} vgpr agpr sgpr spill | main loop: ins mfma dma dsrd barr vmcnt0(inside MFMA span) | mfma total")
