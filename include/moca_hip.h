@@ -334,6 +334,16 @@ int moca_temporal_attention_f16(const void* q, const void* k, const void* v, voi
 int moca_temporal_attention_causal_f16(const void* q, const void* k, const void* v, void* out,
                                        int32_t B, int32_t T, int32_t HW, int32_t heads,
                                        int32_t ld_qkv, int32_t ldo, float scale, void* stream);
+/* The same attention over 17 <= T <= 32 frames (the reference's TemporalTransformer.forward takes any frame count when
+ * use_relative_position is off, attention.py:331-373): one wavefront per (video, pixel, head), one 32 x 32 score tile of
+ * v_mfma_f32_32x32x16_f16, fp32 softmax, P rounded to fp16 once, the output normalised in fp32 and rounded once; no atomics,
+ * replays are bit-identical.  Operand layout of moca_temporal_attention_f16.  causal: 0, or 1 for the mask of
+ * moca_temporal_attention_causal_f16 (then scale > 0).  Limits (16-byte loads, 8-byte stores): 17 <= T <= 32 (T <= 16 belongs to
+ * the two entries above); q, k, v 16-byte aligned, out 8-byte aligned; ld_qkv a multiple of 8 and ldo of 4 halves, both
+ * >= heads * 64.  MOCA_E_BADARG otherwise, before any launch.                                                               */
+int moca_temporal_attention_long_f16(const void* q, const void* k, const void* v, void* out,
+                                     int32_t B, int32_t T, int32_t HW, int32_t heads,
+                                     int32_t ld_qkv, int32_t ldo, float scale, int32_t causal, void* stream);
 
 /* ---- layout / embedding helpers ----------------------------------------------- */
 /* x [B][Cin][T][H][W] (f32 or f16) -> channels-last fp16 [B*T][H*W][Cpad], zero padded

@@ -19,6 +19,10 @@
 //   v_mfma_f32_16x16x16_f16 (PV); gathers the T frames of a pixel straight from the
 //   channels-last token matrix, so the reference's (b t) c h w <-> (b h w) t c
 //   reshuffles (attention.py:335-338,367) never touch memory.
+//
+// moca_temporal_attention_long_f16: the same over 17 <= T <= 32 frames: one wavefront per
+//   problem, the 32 x 32 score tile of v_mfma_f32_32x32x16_f16 whose accumulator registers
+//   are the B operand of P.V (tattn_long_kernel).
 #include "common.h"
 #include <stdlib.h>
 
@@ -795,8 +799,121 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(
     }
 }
 
+// ---- temporal attention over 17 .. 32 frames: one wavefront per (video, pixel, head) -------
+// The 32 frames of a pixel are one 32 x 32 score tile.  S^T = K.Q^T by four v_mfma_f32_32x32x16_f16 over d = 64: the lane
+// (r = lane & 31, h = lane >> 5) then holds S^T[key = (reg & 3) + 8 (reg >> 2) + 4 h][query = r], i.e. the key index lies in its 16
+// registers and the query on the lane -- the softmax over keys is 15 in-lane max / adds and one exchange with lane ^ 32.  Registers
+// 8s .. 8s+7, rounded to fp16 once, ARE the B operand of k-step s of O^T = V^T.P^T (element j = key 16s + 8(j>>2) + 4h + (j&3)); the A
+// operand takes V in that same key order by two transposing 4-key LDS reads of the row-major V tile (as attention_kernel does).
+// Keys >= T get -inf before the row maximum, with CAUSAL keys above the query too (attention.py:101-105); the diagonal is never
+// masked and T >= 17 > 4h + 3, so every lane's maximum is finite.  Rows t >= T are neither loaded (zero fragments) nor stored.
+// No atomics, fixed order of every sum: replays are bit-identical.
+constexpr int TL_T = 32;     // frames of the tile
+template <bool CAUSAL>
+__global__ __launch_bounds__(256) void tattn_long_kernel(
+    const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v, half_t* __restrict__ out,
+    int B, int T, int HW, int heads, int ld, int ldo, float scale_log2e) {
+    // V row-major [key][d], 128-byte rows, chunk ^ (((row >> 1) & 1) << 2): the swizzle of attention_kernel's transposed reads
+    __shared__ __attribute__((aligned(16))) char sV[4][TL_T * ROWB];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t total = (int64_t)B * HW * heads;
+    int64_t prob = (int64_t)blockIdx.x * 4 + wave;
+    const bool active = prob < total;
+    if (!active) prob = total - 1;
+    const int head = (int)(prob % heads);
+    const int64_t bp = prob / heads;
+    const int pix = (int)(bp % HW), b = (int)(bp / HW);
+    // token row of frame t: (b*T + t)*HW + pix
+    const int64_t row0 = (int64_t)b * T * HW + pix;
+    const int64_t rstride = (int64_t)HW * ld;
+    const int64_t base = row0 * ld + head * D;
+
+    const int fr = lane & 31, fh = lane >> 5;
+    // K (A operand) and Q (B operand) fragments of S^T = K.Q^T: row fr, d = 16 ks + 8 fh + j
+    half8v kf[4], qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        half8v a = {0, 0, 0, 0, 0, 0, 0, 0}, c = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (fr < T) {
+            a = *reinterpret_cast<const half8v*>(k + base + fr * rstride + ks * 16 + fh * 8);
+            c = *reinterpret_cast<const half8v*>(q + base + fr * rstride + ks * 16 + fh * 8);
+        }
+        kf[ks] = a; qf[ks] = c;
+    }
+    // V -> LDS: lane -> rows (lane >> 3) + 8 i, 16-byte chunk lane & 7; rows >= T are zero (their P is zero: 0 * 0, never 0 * garbage)
+    char* sv = sV[wave];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = (lane >> 3) + 8 * i, ch = lane & 7;
+        half8v a = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (row < T) a = *reinterpret_cast<const half8v*>(v + base + row * rstride + ch * 8);
+        *reinterpret_cast<half8v*>(sv + row * ROWB + ((ch ^ (((row >> 1) & 1) << 2)) << 4)) = a;
+    }
+    __syncthreads();
+
+    f32x16 s;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[ks], s, 0, 0, 0);
+    // register r holds key (r & 3) + 8 (r >> 2) + 4 fh; the last key this lane's query sees is T - 1, with CAUSAL min(T - 1, fr):
+    // ONE comparison per register in both instantiations
+    const int last = (CAUSAL ? min(T - 1, fr) : T - 1) - 4 * fh;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        if ((r & 3) + 8 * (r >> 2) > last) s[r] = -INFINITY;
+        mx = fmaxf(mx, s[r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float sum = 0.f;
+    half8v pf[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        // (a masked key is zero whatever the sign of the scale: the tail keys are masked in the non-causal form too)
+        const float pv = (r & 3) + 8 * (r >> 2) > last ? 0.f : exp2f((s[r] - mx) * scale_log2e);
+        sum += pv;
+        pf[r >> 3][r & 7] = (half_t)pv;
+    }
+    sum += __shfl_xor(sum, 32, 64);
+    const float inv = 1.0f / sum;
+
+    // O^T[d][q] = V^T[d][key] . P^T[key][q]: the transposed read of a 16-lane group (lane i = 4 tq + tp) delivers to lane i the column
+    // d = 32 dt + 16 tcol16 + i of the 4 keys 16 ss + 4 fh + (0 .. 3); the second read is 8 keys further
+    const int tq = (lane & 15) >> 2, tp = lane & 3, tcol16 = (lane >> 4) & 1;
+    f32x16 o[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+#pragma unroll
+        for (int ss = 0; ss < 2; ++ss) {
+            const int ra = ss * 16 + 4 * fh + tq, rb = ra + 8;
+            const int dcol = dt * 32 + tcol16 * 16 + 4 * tp;
+            const int ch = dcol >> 3, within = (dcol & 7) * 2;
+            const half4v lo = tr_read(sv + ra * ROWB + ((ch ^ (((ra >> 1) & 1) << 2)) << 4) + within);
+            const half4v hi = tr_read(sv + rb * ROWB + ((ch ^ (((rb >> 1) & 1) << 2)) << 4) + within);
+            const half8v vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[ss], o[dt], 0, 0, 0);
+        }
+    }
+    // lane holds O^T[d = 32 dt + 8 g + 4 fh + j][q = fr]: 8-byte stores
+    if (active && fr < T) {
+        half_t* ob = out + (row0 + (int64_t)fr * HW) * ldo + head * D;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                half4v h4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) h4[j] = (half_t)(o[dt][g * 4 + j] * inv);
+                *reinterpret_cast<half4v*>(ob + dt * 32 + 8 * g + 4 * fh) = h4;
+            }
+    }
+}
+
 // Entry checks follow the widest access a kernel makes on an operand: 16-byte loads / LDS-DMA on q, k, v everywhere; 16-byte row
-// stores of `out` in the short and long-key kernels, 8-byte stores in attention_kernel and the temporal kernel.
+// stores of `out` in the short and long-key kernels, 8-byte stores in attention_kernel and the temporal kernels.
 inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
 template <bool IP>
@@ -923,4 +1040,24 @@ extern "C" int moca_temporal_attention_causal_f16(const void* q, const void* k, 
                                                   int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
     if (!(scale > 0.f)) return MOCA_E_BADARG;          // (the mask is applied before the scale: -inf must stay -inf)
     return launch_temporal_attention(true, q, k, v, out, B, T, HW, heads, ld_qkv, ldo, scale, stream);
+}
+
+// 17 <= T <= 32 (T <= 16 stays with the two entries above: one kernel per frame count, and their bits do not move)
+extern "C" int moca_temporal_attention_long_f16(const void* q, const void* k, const void* v, void* out,
+                                                int32_t B, int32_t T, int32_t HW, int32_t heads,
+                                                int32_t ld_qkv, int32_t ldo, float scale, int32_t causal, void* stream) {
+    if (!q || !k || !v || !out) return MOCA_E_BADARG;
+    if (B <= 0 || T <= 16 || T > TL_T || HW <= 0 || heads <= 0 || (causal != 0 && causal != 1)) return MOCA_E_BADARG;
+    if (causal && !(scale > 0.f)) return MOCA_E_BADARG;          // (the mask is applied before the scale: -inf must stay -inf)
+    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(out, 8)) return MOCA_E_BADARG;   // 16-byte loads, 8-byte stores
+    if (ld_qkv % 8 || ldo % 4 || ld_qkv < heads * D || ldo < heads * D) return MOCA_E_BADARG;
+    const int64_t total = (int64_t)B * HW * heads;
+    if ((total + 3) / 4 > INT32_MAX) return MOCA_E_BADARG;
+    const dim3 grid((unsigned)((total + 3) / 4)), block(256);
+    hipLaunchKernelGGL(causal ? tattn_long_kernel<true> : tattn_long_kernel<false>, grid, block, 0, moca_stream(stream),
+                       reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
+                       reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
+                       B, T, HW, heads, ld_qkv, ldo, scale * 1.4426950408889634f);
+    MOCA_CHECK_LAUNCH();
+    return MOCA_OK;
 }

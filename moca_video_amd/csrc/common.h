@@ -119,21 +119,51 @@ __device__ __forceinline__ f32x4g moca_geglu4(f32x4g v, f32x4g g) {
 // GroupNorm statistics accumulated across blocks (MOCA_EP_GSTAT, concat with statistics): 64-bit FIXED-POINT atomics -- integer
 // addition is associative, so the finished statistics do not depend on the order in which the producer's blocks arrive and a
 // replayed graph reproduces its output bit for bit by construction (f64 atomicAdd did so only "in practice").
-// Units (round 6; 2^-30 / 2^-16 before): sum 2^-20, sum of squares 2^-12.  What they must hold: one PARTIAL (a row tile x a
-// channel group, <= 320 x 40 = 12 800 values) is accepted up to 2^53 units, a group's TOTAL up to 2^61 units:
-//     sum:            |partial| < 8.6e9 (a mean of 6.7e5 over 12 800 values), |total| < 2.2e12      -- beyond fp16 (max 65 504)
-//     sum of squares:  partial  < 2.2e12 (rms 1.3e4 over 12 800 values),      total  < 5.6e14 (rms 3.7e4 over the largest group,
-//                      409 600 values): a tensor at that rms already holds fp16 infinities.
+// Units (round 6; 2^-30 / 2^-16 before): sum 2^-20, sum of squares 2^-12.  What they must hold: one PARTIAL (tiled GEMM: a row tile
+// x a channel group, <= 320 x 40 = 12 800 values, whatever the frame count; the weight-stationary kernel's partial is larger, see
+// below) is accepted up to 2^53 units; a group's TOTAL is READ up to 2^61 units of the sum of squares:
+//     sum:            |partial| < 8.6e9 (a mean of 6.7e5 over 12 800 values)                         -- beyond fp16 (max 65 504)
+//     sum of squares:  partial  < 2.2e12 (rms 1.3e4 over 12 800 values),      total  < 2^49 = 5.6e14.
+//   The total is what grows with the frames of a statistics group (the 5-D GroupNorms of the temporal convs and of the temporal
+//   transformers: T x HW rows x C / 32 channels, largest at the 320-channel level).  5.6e14 is an rms of
+//       3.7e4 over   409 600 values (16 frames, 40 x 64 latents): such a tensor already holds fp16 infinities;
+//       2.6e4 over   819 200 values (32 frames, 40 x 64);
+//       2.1e4 over 1 310 720 values (32 frames, 64 x 64): 5 x the largest rms the tests or bench.py's synthetic video reach (~4e3).
+//   A finite fp16 tensor above those rms values is possible (every |x| near 3e4); its statistics then read back as NaN (below), not
+//   as a wrong number.
+//   The WEIGHT-STATIONARY kernel (gemm_ws.hip, the 320 -> 320 linears: 10 channels per group) adds ONE partial per block and
+//   statistics group over ALL the block's rows of that group: rows of the group / bpg, bpg = 256 CUs / statistics groups of the launch.
+//   That partial does grow with the frames and with the videos of a launch, and it is poisoned (NaN, never a wrong number) at
+//   2^41 = 2.2e12, i.e. at an rms of sqrt(2.2e12 / values) -- BELOW the group range above once several videos share the launch:
+//       32 frames x 2560 pixels, B = 1:   320 rows =  3 200 values: rms 2.6e4 (the group range itself);
+//                                B = 8:  2560 rows = 25 600 values: rms 9.3e3  (16 frames: B = 16);
+//                                B = 16: 5120 rows = 51 200 values: rms 6.6e3  (16 frames: B = 32)
+//   -- still above the ~4e3 of the tests and of bench.py's synthetic video, but the figure to know for such a launch.
+//   The sum cannot wrap while the sum of squares is readable: |sum| <= sqrt(values x sum of squares)
+//   < sqrt(2^21 x 2^49) = 2^35 = 2^55 units.
 //   The old units stopped at a partial rms of 3.3e3 -- reached by the latents of bench.py's synthetic video (~4e3), whose statistics
 //   were then CLAMPED, i.e. silently wrong.  Precision: rounding a partial to the units changes a group's mean by
 //   < 2^-21 * partials / values and its mean of squares by < 2^-13 * partials / values <= 2^-13 / 400 = 3e-7 at worst (a 5 x 8 x
-//   10-value partial), below the 1e-6 / 1e-5 eps added to the variance.
+//   10-value partial), below the 1e-6 / 1e-5 eps added to the variance -- a ratio per partial, independent of the frame count.
 // A NON-FINITE partial (NaN / Inf activations) or one beyond +-2^53 units must not turn into finite statistics: it sets bit 62 of
 // the group's sum-of-squares accumulator (acc layout [group][2] = {sum, sum of squares}) and adds nothing; OR is idempotent, so the
-// bit survives however many partials are poisoned.  moca_gstat_get returns NaN when the sum-of-squares accumulator is >= 2^61 -- the
-// poison bit, or accepted adds that came within a factor 2 of it (a group of the UNet receives <= 2^10 partials: rows of a statistics
-// group / 160-row tiles x 2 column tiles, so accepted adds stay below 2^63 and cannot wrap): statistics outside the fixed-point
-// range read back as NaN, never as a wrong finite number, and finite adds can not alias the poison bit unnoticed.
+// bit survives however many partials are poisoned.  moca_gstat_get returns NaN when the sum-of-squares accumulator, read as unsigned,
+// is >= 2^61 -- the poison bit, or accepted adds that came within a factor 2 of it.  That reading is sound while the accepted adds
+// cannot wrap the 64-bit word: every one is <= 2^53 units and non-negative, so FEWER THAN 2^11 PARTIALS per (statistics group, channel
+// group) keep the total below 2^64, and everything in [2^61, 2^64) reads NaN.  Partials per accumulator:
+//     tiled GEMM epilogue (MOCA_EP_GSTAT): row tiles of >= 160 rows; a channel group (<= 80 columns) lies in <= 2 column tiles
+//         (>= 128 columns): <= 2 x ceil(rows of the statistics group / 160).  16 frames x 2560 pixels: 512; 32 x 2560: 1024 = 2^10;
+//         32 x 4096 (64 x 64 latents): 1640 by this bound, which counts 160-row tiles whatever the route (131 072 rows are no
+//         multiple of 160, so the launch itself takes 256-row tiles: 1024).  The bound 2047 is reached past 1023 x 160 = 163 680
+//         rows = 32 frames x 5115 pixels, and the plan refuses a group of MORE THAN 16 FRAMES beyond that (plan.py,
+//         _check_gstat_range) instead of running it.  Groups of up to 16 frames are not checked, so that every forward that ran
+//         before still runs: 16 frames x more than 10 230 pixels (e.g. 128 x 80 latents) lie outside this bound likewise.  PER-FRAME groups have HW rows whatever the frame count and are not checked: the largest one in
+//         use, the VAE decoder's 320 x 512 frame (163 840 rows), receives at most 2^11 partials, where a wrap would need EVERY
+//         partial to be exactly 2^53 units -- outside the strict argument by that one case, as before this derivation;
+//     weight-stationary kernel: one per block and 80-column wave that touches the group, <= 2 x the blocks of the launch;
+//     concat / statistics passes (norm.hip): per-frame statistics only, gn_nchunk(F, HW) <= 2048 / F partials per frame.
+// So statistics outside the fixed-point range read back as NaN, never as a wrong finite number, and finite adds can not alias the
+// poison bit unnoticed.
 #define MOCA_GSTAT_SUM_SCALE 1048576.0        /* 2^20 */
 #define MOCA_GSTAT_SQ_SCALE 4096.0            /* 2^12 */
 #define MOCA_GSTAT_POISON (1ull << 62)

@@ -87,6 +87,14 @@ def refuse_image_attention(model):
                                   "its 154-token two-prompt context would be read as 77 text + 77 image tokens")
 
 
+def refuse_long_window(args):
+    """FIFO / MoCA windows are at most 16 frames: the one-graph loop (ring queue, per-window timestep tables, batched windows) is
+    built and measured for the 16-frame tile of the temporal attention; the UNet alone takes up to 32 frames (UNetModel.forward)"""
+    if args.video_length > 16:
+        raise ValueError(f"video_length = {args.video_length}: FIFO sampling takes windows of video_length <= 16 frames "
+                         f"(base_ddim_sampling / v2v_ddim_sampling take up to 32)")
+
+
 def refuse_concat(model, cond=None):
     """FIFO / MoCA sampling has no channel-concatenated conditioning: the reference's loop hands every window the whole `cond`
     and never slices `c_concat` along the queue, so there is no behaviour to reproduce.  Raise instead of computing something."""
@@ -208,6 +216,7 @@ def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg
     conditional context, a tensor [1,L,D] replaces it from this iteration on (same L; on the graph path `FifoEngine.set_context`)."""
     context_at = kwargs.pop("context_at", None)
     kwargs.update({"clean_cond": True})
+    refuse_long_window(args)
     refuse_image_attention(model)
     refuse_concat(model, conditioning)
     cond = conditioning
@@ -381,6 +390,7 @@ def fifo_ddim_sampling_multiprompts(args, model, conditioning, noise_shape, ddim
     for k in ("davis_data", "davis_masks"):
         if kwargs.pop(k, None) is not None:
             raise NotImplementedError(f"fifo_ddim_sampling_multiprompts has no DAVIS-video mode: {k} is not supported")
+    refuse_long_window(args)
     refuse_image_attention(model)
     refuse_concat(model, conditioning)
     if save_frames and (not decode or output_dir is None):

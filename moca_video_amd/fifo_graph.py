@@ -67,7 +67,8 @@ class FifoEngine:
         """sam_capacity > 0 (and no `masks`): prompt mode with precomputed Grounded-SAM-2 candidates -- `ddim_step`'s segmentation
         branch (ddim.py:592-606 -> `_apply_segmentation` :739-903) runs inside the iteration graph on at most `sam_capacity`
         candidate masks per iteration, handed to `step(sam_masks=...)`."""
-        from .fifo import refuse_concat, refuse_image_attention
+        from .fifo import refuse_concat, refuse_image_attention, refuse_long_window
+        refuse_long_window(args)
         refuse_image_attention(model)
         refuse_concat(model, cond)
         self.unet = unet = model.model.diffusion_model

@@ -403,6 +403,13 @@ def temporal_attention_causal(q, k, v, out, *, B, T, HW, heads, ld_qkv, ldo, sca
     return out
 
 
+def temporal_attention_long(q, k, v, out, *, B, T, HW, heads, ld_qkv, ldo, scale, causal=False):
+    """temporal_attention over 17 <= T <= 32 frames (one 32 x 32 score tile per wavefront); causal: frame t attends to frames <= t"""
+    _l.check(_l.load().moca_temporal_attention_long_f16(_l.ptr(q), _l.ptr(k), _l.ptr(v), _l.ptr(out), B, T, HW, heads,
+                                                        ld_qkv, ldo, scale, int(bool(causal)), _st()), "moca_temporal_attention_long_f16")
+    return out
+
+
 def ncthw_to_nhwc(x, y, *, B, Cin, T, HW, Cpad):
     _l.check(_l.load().moca_ncthw_to_nhwc_f16(_l.ptr(x), 1 if x.dtype == torch.float32 else 0, _l.ptr(y), B, Cin, T, HW,
                                               Cpad, _st()), "moca_ncthw_to_nhwc_f16")

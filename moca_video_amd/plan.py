@@ -67,6 +67,20 @@ SPLITK_GN = os.environ.get("MOCA_SKGN", "1") != "0"
 # moca_gemm_params.wgroup_rows): the normalised tensor is never written.  MOCA_GNFOLD=0: A/B
 GN_FOLD = os.environ.get("MOCA_GNFOLD", "1") != "0"
 SPLITK_GN_ALL = os.environ.get("MOCA_SKGN", "1") == "2"     # (A/B: also the 16-frame GroupNorms of the temporal convs)
+# frames of one temporal-attention problem: T <= 16 one 16 x 16 MFMA tile (moca_temporal_attention_f16 / _causal_f16 and the fused
+# MOCA_EP_TATTN launch), 17 .. 32 one 32 x 32 tile (moca_temporal_attention_long_f16)
+MAX_FRAMES = 32
+# MOCA_EP_GSTAT: a (statistics group, channel group) accumulator takes fewer than 2^11 partials of <= 2^53 units each, so it cannot
+# wrap past 2^64 (csrc/common.h).  Its producer is a tiled GEMM with row tiles of >= 160 rows, and a channel group (<= 80 columns)
+# lies in at most two of its column tiles (>= 128 columns): 2 * ceil(rows / 160) partials.  Checked for the statistics groups of MORE THAN 16
+# FRAMES (the 5-D GroupNorms of a T > 16 forward: the shapes that were refused before); every plan of up to 16 frames is built as before
+GSTAT_MAX_PARTIALS = (1 << 11) - 1
+
+
+def _check_gstat_range(rows):
+    if 2 * -(-rows // 160) > GSTAT_MAX_PARTIALS:
+        raise ValueError(f"GroupNorm statistics over {rows} rows (frames x pixels of one group) are outside the range of the fixed-point "
+                         f"accumulators: at most {GSTAT_MAX_PARTIALS // 2 * 160} rows, e.g. 32 frames of 5115 latent pixels")
 
 
 class _LNRef:
@@ -290,6 +304,8 @@ class _PlanBase:
         elif cs is not None and (fps * HW) % cs[1] == 0 and fm.src is not None:
             # the producer is re-targeted: instead of per-tile column sums it accumulates the FINISHED statistics of this
             # GroupNorm (fixed-point atomics per (statistics group, channel group), MOCA_EP_GSTAT) -- no finalize launch
+            if fps > 16:                                  # (groups of up to 16 frames, per-frame ones included: as before)
+                _check_gstat_range(fps * HW)
             prod = self.steps[fm.src]
             slot = self._gstat_slot((fm.F // fps) * 64)
             kw = dict(prod.keywords)
@@ -406,6 +422,8 @@ class _Plan(_PlanBase):
                 if Ls > IMAGE_CONTEXT_MAX:
                     raise ValueError(f"image-attention UNet: a context of {Ls} tokens is longer than {IMAGE_CONTEXT_MAX} ({TEXT_CONTEXT_LEN} "
                                      f"text + {IMAGE_CONTEXT_MAX - TEXT_CONTEXT_LEN} image tokens, the fused attention's key tile)")
+        if T > MAX_FRAMES:
+            raise ValueError(f"x has T = {T} frames: the temporal attention kernels take at most {MAX_FRAMES}")
         super().__init__(model, device)
         self.B, self.T, self.H, self.W, self.L = B, T, H, W, L
         self.BT = B * T
@@ -578,6 +596,9 @@ class _Plan(_PlanBase):
         if spatial:
             self._emit(ops.attention, q, k, v, o, Bq=F, heads=heads, Nq=HW, Nk=HW, ldq=3 * Cn, ldk=3 * Cn, ldv=3 * Cn,
                        ldo=Cn, kv_div=1, scale=scale)
+        elif self.T > 16:                    # one 32 x 32 score tile per (video, pixel, head)
+            self._emit(ops.temporal_attention_long, q, k, v, o, B=M // (self.T * HW), T=self.T, HW=HW, heads=heads, ld_qkv=3 * Cn,
+                       ldo=Cn, scale=scale, causal=causal)
         else:
             self._emit(ops.temporal_attention_causal if causal else ops.temporal_attention, q, k, v, o, B=M // (self.T * HW), T=self.T,
                        HW=HW, heads=heads, ld_qkv=3 * Cn, ldo=Cn, scale=scale)
@@ -722,6 +743,8 @@ class _Plan(_PlanBase):
         if have:
             slot = fm.gstat[0]
         else:                                        # re-target the producer: finished statistics instead of per-tile column sums (as gn())
+            if fps > 16:
+                _check_gstat_range(rows)
             prod = self.steps[fm.src]
             slot = self._gstat_slot(n_sg * 64)
             kw = dict(prod.keywords)

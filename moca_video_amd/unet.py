@@ -516,8 +516,8 @@ class UNetModel(nn.Module):
             self._pack()
         B, Cin, T, H, W = x.shape
         assert Cin + concat_channels == self.in_channels
-        if T > 16:
-            raise ValueError("temporal attention kernel supports T <= 16 (temporal_length of the YAML)")
+        if T > 32:
+            raise ValueError(f"x has T = {T} frames: the temporal attention kernels take T <= 32 (16 x 16 tile up to 16, 32 x 32 up to 32)")
         timesteps = torch.as_tensor(timesteps, device=x.device).reshape(-1).to(torch.int64)
         n_t = timesteps.shape[0]
         if n_t == B:                       # not is_fifo: emb.repeat_interleave(T) (:548-549)
