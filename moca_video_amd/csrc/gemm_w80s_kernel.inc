@@ -1,4 +1,4 @@
-// Text of the staggered "w80s" GEMM kernel (see gemm.hip, which includes this file twice).  Set by the including file:
+// Text of the staggered "w80s" GEMM kernel (see gemm_tiled.hip, which includes this file twice).  Set by the including file:
 //   MOCA_W80S_NAME    name of the __global__ template <int AMODE, int SHAPE> defined here
 //   MOCA_W80S_CAUSAL  true: the MOCA_EP_TATTN epilogue (SHAPE 3) masks key frame > query frame (moca_gemm_params.tattn_causal)
 template <int AMODE, int SHAPE>

@@ -11,7 +11,7 @@ from moca_video_amd import lib as L
 TOL16 = 3e-3                    # tests/test_kernels_gpu.py: one fp16-output kernel against torch on the same fp16 operands
 TOL32 = 1e-3                    # tests/test_kernels_gpu.py::test_gemm_rowadd_f32out
 NAN = float("nan")
-BK = 64                         # k-tile depth of every kernel (csrc/gemm.hip)
+BK = 64                         # k-tile depth of every kernel (csrc/gemm_device.h)
 
 
 def gen(seed):

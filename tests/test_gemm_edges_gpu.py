@@ -1,4 +1,4 @@
-"""GPU: moca_gemm_f16 (csrc/gemm.hip, gemm_w80s_kernel.inc, gemm_ws.hip) on every dispatch route at its gather, stride, tail and epilogue
+"""GPU: moca_gemm_f16 (csrc/gemm.hip, gemm_tiled.hip, gemm_w80s_kernel.inc, gemm_persistent.hip, gemm_ws.hip) on every dispatch route at its gather, stride, tail and epilogue
 edges, against float64 torch on the same fp16 operands (tests/gemm_edges_ref.py).  The error is taken per block of 64 output rows --
 max|got - ref| over the block / max|ref| of that block -- and every block must meet TOL16 = 3e-3 (fp32 output: 1e-3).  Bias, row add
 and residual are drawn at scale 1, so dropping or misplacing one of them is an O(1) error.

@@ -101,6 +101,18 @@ def test_every_gemm_kernel_of_the_dispatch_is_present(isa):
         assert len(have) == n, f"{stem}: {len(have)} instantiations, expected {n}: {have}"
 
 
+def test_every_kernel_is_defined_in_exactly_one_code_object(isa):
+    """The GEMM kernel families are spread over several translation units that share their device helpers through a header.  A kernel
+    template instantiated from two of them would be compiled twice, and analyse() -- which keys by name -- would show only one copy to
+    every check above."""
+    import isa_report
+    from moca_video_amd import lib
+    owners = isa_report.kernel_owners(lib.LIB_PATH)
+    assert len(owners) >= len(isa), f"{len(owners)} kernel symbols for {len(isa)} kernels"
+    twice = {name: n for name, n in owners.items() if n != 1}
+    assert not twice, f"kernels defined in more than one code object: {twice}"
+
+
 def test_weight_stationary_strip_loop_issues_exactly_the_counted_stores(isa):
     """gemm_ws_kernel waits for strip k + 1 with a HAND-COUNTED `s_waitcnt vmcnt(BASE + k * ST_PER_STRIP)` (gemm_ws.hip): vmcnt retires
     loads, LDS-DMA and stores together in issue order, so the count only holds while the strip loop issues exactly ST_PER_STRIP vector

@@ -8,14 +8,14 @@ stream inside the MFMA segment: what hipcc inserts when it cannot prove an LDS a
 register that is a known load destination is rewritten).
 
     python tools/isa_report.py [libmoca_hip.so] [name filter ...]
-    python tools/isa_report.py --diff OLD NEW      (two builds of the library or of one object file, e.g. csrc/gemm.o)
+    python tools/isa_report.py --diff OLD NEW      (two builds of the library or of one object file, e.g. csrc/gemm_tiled.o)
 
 `--diff` is the check of a host-only change: the same kernel symbols, per kernel the same instruction encodings and the same register /
 LDS / scratch figures.  Moving host code moves the kernels inside the code object, so two things may differ and are counted, not
 failed: the 32-bit literal of an `s_add_u32` (a pc-relative offset to another symbol) and the padding behind a kernel's last
 instruction.  Exit status 1 on any other difference.
 
-`analyse(lib_path)` is what tests/test_isa_cpu.py calls."""
+`analyse(lib_path)` and `kernel_owners(lib_path)` are what tests/test_isa_cpu.py calls."""
 import os
 import re
 import shutil
@@ -258,6 +258,18 @@ def analyse(lib_path=None):
                 short = re.sub(r"\(.*\)$", "", short)
                 res[short] = d
     return res
+
+
+def kernel_owners(lib_path=None):
+    """{mangled kernel name: number of gfx950 code objects (= translation units) of the library that define it}.  analyse() and
+    encodings() key by name, so a kernel instantiated in two units would silently merge there."""
+    lib_path = lib_path or os.path.join(ROOT, "moca_video_amd", "libmoca_hip.so")
+    owners = {}
+    with tempfile.TemporaryDirectory() as wd:
+        for co in code_objects(lib_path, wd):
+            for name in metadata(co):
+                owners[name] = owners.get(name, 0) + 1
+    return owners
 
 
 _ENC = re.compile(r"^\s+(\S+)\s*(.*?)\s*//\s*[0-9A-Fa-f]+:((?:\s+[0-9A-Fa-f]{8})+)\s*$")

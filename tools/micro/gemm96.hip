@@ -1,7 +1,7 @@
 // Prototype / micro-benchmark for DESIGN section 9 "(1)": is a 256 x 256 block of FOUR waves with 128 x 128 wave tiles (one wave per SIMD,
 // 256 accumulator registers in the AGPR half of the register file) faster at the power cap than the library's 8-wave kernels (80 x 80 /
 // 64 x 128 wave tiles, two waves per SIMD)?  0.25 fragment reads per MFMA instead of 0.375-0.40, the same LDS-DMA ring and swizzles as
-// gemm_sqp_kernel (moca_video_amd/csrc/gemm.hip).  Plain linear only: out[M][N] = A[M][K] . W[N][K]^T, fp16 in / out, fp32 accumulate;
+// gemm_sqp_kernel (moca_video_amd/csrc/gemm_persistent.hip).  Plain linear only: out[M][N] = A[M][K] . W[N][K]^T, fp16 in / out, fp32 accumulate;
 // M % 256 == 0, N % 192 == 0, K % 64 == 0.  Not part of the product.
 //
 //   hipcc -O3 --offload-arch=gfx950 tools/micro/gemm128.hip -o tools/micro/gemm128 && tools/micro/gemm128 [M N K]
