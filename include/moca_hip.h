@@ -539,6 +539,31 @@ int moca_fifo_prepare_queue_f32(const float* z, const float* noise, float* queue
 int moca_base_set_timestep(const moca_fifo_state* state, const int64_t* table, int32_t S, int64_t* rows, int32_t n, void* stream);
 int moca_base_ddim_step_f32(moca_fifo_state* state, float* x, const float* eps_c, const float* eps_u, const float* noise,
                             float* pred_x0, const float* coef, int32_t S, float cfg_scale, int32_t use_scale, int64_t n, void* stream);
+/* ---- one reverse step of the DDPM sampler: `LatentDiffusion.p_sample` (ddpm3d.py:591-610) over `p_mean_variance` (:565-588),
+ * `predict_start_from_noise` (:212-216) and `q_posterior` (:218-225), with the masked-inpainting blend of `p_sample_loop` (:646-648)
+ * over `q_sample` (:412-420).  x, out, eps_*, noise, x_recon, mean, x0, noise_q are [B][per] f32; per element of sample b at
+ * t_b = t[b * t_stride] (int64, DEVICE memory: the UNet plan's timestep rows with t_stride = frames), in the reference's order of
+ * fp32 operations (mul / add / sub, no contraction):
+ *   eps = eps_u + cfg_scale (eps_c - eps_u)                    ddim.py:304; eps_u NULL: eps = eps_c
+ *   x_recon = srac x - srm1 eps   (MOCA_DDPM_X0: x_recon = eps), MOCA_DDPM_CLIP: clamped to [-1, 1]
+ *   mean = c1 x_recon + c2 x
+ *   out = mean + (nonzero(t_b) std) (noise temperature)        nonzero = 0 at t_b == 0
+ *   mask, x0, noise_q non-NULL (all or none):  orig = sac x0 [scale, MOCA_DDPM_SCALE] + s1mac noise_q;  out = orig mask + (1 - mask) out
+ * coef[n_tab][8] = {srac, srm1, c1, c2, std, sac, s1mac, scale}: sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod,
+ * posterior_mean_coef1/2, exp(0.5 posterior_log_variance_clipped), sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, scale_arr,
+ * built by the host in fp32 as the reference's buffers are (:136-153,:376).  mask is [B][per], or with MOCA_DDPM_MASK_C0
+ * [B][mask_inner] read with channel stride 0 (per % mask_inner == 0).  out may alias x; out, x_recon, mean are optional (one at
+ * least; out needs noise).  eps_c NULL: no reverse step, out = orig (`q_sample`; x0, noise_q, out only).  per need not be a multiple
+ * of 4.  t_b outside [0, n_tab) reads no table entry: every output of sample b is NaN.  state non-NULL: then iter += 1,
+ * ext_noise = 0 (the captured step of fifo_graph.DdpmEngine); NULL: the state is not touched (host-issued calls). */
+#define MOCA_DDPM_X0 1
+#define MOCA_DDPM_CLIP 2
+#define MOCA_DDPM_SCALE 4
+#define MOCA_DDPM_MASK_C0 8
+int moca_ddpm_step_f32(moca_fifo_state* state, const float* x, float* out, const float* eps_c, const float* eps_u,
+                       const float* noise, float* x_recon, float* mean, const float* mask, const float* x0,
+                       const float* noise_q, const float* coef, const int64_t* t, int64_t t_stride, int32_t B, int32_t n_tab,
+                       int64_t per, int64_t mask_inner, float cfg_scale, float temperature, int32_t flags, void* stream);
 /* sums[fr] = sum of mask frame fr, mask [frames][HW] (ddim.py:585) */
 int moca_mask_frame_sums_f32(const float* mask, float* sums, int32_t frames, int32_t HW, void* stream);
 

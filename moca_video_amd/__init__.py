@@ -3,7 +3,9 @@
 Public surface mirrors the reference interfaces for this path only:
   UNetModel            lvdm/modules/networks/openaimodel3d.py:279-578
   DiffusionWrapper     lvdm/models/ddpm3d.py:696-763
-  DenoiseModel         the slice of LatentDiffusion the samplers use (apply_model + schedule buffers)
+  DenoiseModel         the slice of LatentDiffusion the samplers use (apply_model + schedule buffers) and its own DDPM sampler:
+                       q_sample, predict_start_from_noise, q_posterior, p_mean_variance, p_sample, p_sample_loop with masked
+                       inpainting (ddpm3d.py:136-153,212-225,412-420,565-657; moca_video_amd.ddpm)
   DDIMSampler          lvdm/models/samplers/ddim.py (make_schedule, p_sample_ddim, unet, ddim_step, fifo_onestep,
                        stochastic_encode, decode, ddim_inversion)
   freq_mix_3d, get_freq_filter   utils/freeinit_utils.py

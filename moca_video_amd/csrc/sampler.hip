@@ -173,6 +173,138 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* x0, const fl
     }
 }
 
+// One reverse step of the DDPM sampler, `LatentDiffusion.p_sample` (ddpm3d.py:591-610) with the mask blend of `p_sample_loop`
+// (:646-648), per element of sample b at that sample's timestep t_b = t[b * t_stride], in the reference's order of fp32 operations:
+//   eps = e_u + s (e_c - e_u)                               ddim.py:304 (eps_u NULL: eps = e_c)
+//   x_recon = srac x - srm1 eps  |  eps                     :212-216, :573-576     [clamp to -1 .. 1, :580-581]
+//   mean = c1 x_recon + c2 x                                :219-222
+//   out = mean + (nonzero(t) std) (noise temperature)       :601-610, std = exp(0.5 posterior_log_variance_clipped) from the host
+//   orig = sac x0 [scale] + s1mac noise_q                   :415-420
+//   out = orig mask + (1 - mask) out                        :648
+// mul / add / sub only and no contraction: bit-equal to the torch expression over the same tables.  coef[t] = {srac, srm1, c1, c2,
+// std, sac, s1mac, scale}.  eps_c NULL: no reverse step, out = orig (`q_sample`).  Groups of four consecutive elements of the flat
+// [B * per] range as in q_sample_kernel: float4 where the group lies inside one sample and every pointer is 16-byte aligned, element
+// by element otherwise; out may alias x (each thread reads all it needs before it writes).  t_b outside [0, n_tab): nothing is read
+// from the table and every output of sample b is NaN.
+struct ddpm_args {
+    const float* x; float* out; const float* eps_c; const float* eps_u; const float* noise; float* x_recon; float* mean;
+    const float* mask; const float* x0; const float* noise_q; const float* coef; const int64_t* t;
+    int64_t t_stride, per, mask_inner;
+    float cfg_scale, temperature;
+    int B, n_tab, flags, vec_ok, mask_vec;
+};
+
+struct ddpm_coef {
+    float srac, srm1, c1, c2, sd, sac, s1mac, scale;
+    bool bad;
+};
+
+__device__ __forceinline__ ddpm_coef ddpm_load_coef(const ddpm_args& a, int64_t b) {
+    const int64_t tb = a.t[b * a.t_stride];
+    ddpm_coef k;
+    k.bad = tb < 0 || tb >= (int64_t)a.n_tab;
+    k.srac = k.srm1 = k.c1 = k.c2 = k.sd = k.sac = k.s1mac = k.scale = 0.f;
+    if (k.bad) return k;
+    const float* c = a.coef + tb * 8;
+    k.srac = c[0]; k.srm1 = c[1]; k.c1 = c[2]; k.c2 = c[3];
+    k.sd = (tb == 0 ? 0.f : 1.f) * c[4];                        // nonzero_mask * (0.5 * model_log_variance).exp(), :605-610
+    k.sac = c[5]; k.s1mac = c[6]; k.scale = c[7];
+    return k;
+}
+
+__device__ __forceinline__ void ddpm_ld(const float* p, int64_t e0, bool vec, int cnt, float (&v)[4]) {
+    if (!p) return;
+    if (vec) {
+        const float4 q = *reinterpret_cast<const float4*>(p + e0);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+        for (int j = 0; j < cnt; ++j) v[j] = p[e0 + j];
+    }
+}
+
+__device__ __forceinline__ void ddpm_st(float* p, int64_t e0, bool vec, int cnt, const float (&v)[4]) {
+    if (!p) return;
+    if (vec) {
+        *reinterpret_cast<float4*>(p + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int j = 0; j < cnt; ++j) p[e0 + j] = v[j];
+    }
+}
+
+__global__ __launch_bounds__(256) void ddpm_step_kernel(const ddpm_args a) {
+    const int64_t per = a.per, total = (int64_t)a.B * per;
+    const int64_t n4 = (total + 3) / 4;
+    const float qnan = __builtin_nanf("");
+    const bool x0_param = a.flags & MOCA_DDPM_X0, clip = a.flags & MOCA_DDPM_CLIP, use_scale = a.flags & MOCA_DDPM_SCALE;
+    const bool blend = a.eps_c && a.mask;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
+        const int64_t e0 = q * 4;
+        const int64_t b0 = e0 / per;
+        const int cnt = total - e0 < 4 ? (int)(total - e0) : 4;
+        const bool vec = a.vec_ok && cnt == 4 && (e0 + 3) / per == b0;
+        float x[4] = {}, ec[4] = {}, eu[4] = {}, nz[4] = {}, mk[4] = {}, x0[4] = {}, nq[4] = {}, o[4], rc[4], mn[4];
+        ddpm_ld(a.x, e0, vec, cnt, x);
+        ddpm_ld(a.eps_c, e0, vec, cnt, ec);
+        ddpm_ld(a.eps_u, e0, vec, cnt, eu);
+        if (a.out) ddpm_ld(a.noise, e0, vec, cnt, nz);
+        ddpm_ld(a.x0, e0, vec, cnt, x0);
+        ddpm_ld(a.noise_q, e0, vec, cnt, nq);
+        if (blend) {
+            if (!(a.flags & MOCA_DDPM_MASK_C0)) {
+                ddpm_ld(a.mask, e0, vec, cnt, mk);
+            } else if (vec && a.mask_vec) {                     // per % 4 == 0 and inner % 4 == 0: the group stays inside one channel
+                ddpm_ld(a.mask, b0 * a.mask_inner + (e0 - b0 * per) % a.mask_inner, true, 4, mk);
+            } else {
+                for (int j = 0; j < cnt; ++j) {
+                    const int64_t b = (e0 + j) / per;
+                    mk[j] = a.mask[b * a.mask_inner + (e0 + j - b * per) % a.mask_inner];
+                }
+            }
+        }
+        ddpm_coef k = ddpm_load_coef(a, b0);
+        int64_t b_cur = b0;
+        for (int j = 0; j < cnt; ++j) {
+            if (!vec) {
+                const int64_t b = (e0 + j) / per;
+                if (b != b_cur) {
+                    k = ddpm_load_coef(a, b);
+                    b_cur = b;
+                }
+            }
+            float orig = 0.f;
+            if (a.x0) {
+                float s = k.sac * x0[j];
+                if (use_scale) s = s * k.scale;
+                orig = s + k.s1mac * nq[j];                     // :415-420
+            }
+            float v = orig;
+            rc[j] = mn[j] = qnan;
+            if (a.eps_c) {
+                float e = ec[j];
+                if (a.eps_u) e = eu[j] + a.cfg_scale * (e - eu[j]);            // ddim.py:304
+                float r = x0_param ? e : k.srac * x[j] - k.srm1 * e;          // :573-576
+                if (clip) r = r < -1.f ? -1.f : (r > 1.f ? 1.f : r);          // :581 (NaN stays NaN, as clamp_)
+                const float m = k.c1 * r + k.c2 * x[j];                       // :219-222
+                v = m + k.sd * (nz[j] * a.temperature);                       // :601,608
+                if (blend) v = orig * mk[j] + (1.f - mk[j]) * v;              // :648
+                if (!k.bad) {
+                    rc[j] = r;
+                    mn[j] = m;
+                }
+            }
+            o[j] = k.bad ? qnan : v;
+        }
+        ddpm_st(a.out, e0, vec, cnt, o);
+        ddpm_st(a.x_recon, e0, vec, cnt, rc);
+        ddpm_st(a.mean, e0, vec, cnt, mn);
+    }
+}
+
+__global__ void ddpm_state_bump_kernel(moca_fifo_state* st) {
+    st->iter = st->iter + 1;
+    st->ext_noise = 0;
+}
+
 }  // namespace
 
 extern "C" int moca_cfg_combine_f32(const float* e_c, const float* e_u, float* out, float scale,
@@ -238,5 +370,42 @@ extern "C" int moca_q_sample_f32(const float* x0, const float* noise, float* out
     hipLaunchKernelGGL(q_sample_kernel, dim3(grid_for(n4)), dim3(256), 0, moca_stream(stream), x0, noise, out, coef_x, coef_n, t, B, n_tab,
                        per, vec_ok);
     MOCA_CHECK_LAUNCH();
+    return MOCA_OK;
+}
+
+extern "C" int moca_ddpm_step_f32(moca_fifo_state* state, const float* x, float* out, const float* eps_c, const float* eps_u,
+                                  const float* noise, float* x_recon, float* mean, const float* mask, const float* x0,
+                                  const float* noise_q, const float* coef, const int64_t* t, int64_t t_stride, int32_t B, int32_t n_tab,
+                                  int64_t per, int64_t mask_inner, float cfg_scale, float temperature, int32_t flags, void* stream) {
+    if (!coef || !t || B <= 0 || n_tab <= 0 || per <= 0 || t_stride < 0) return MOCA_E_BADARG;
+    if (flags & ~(MOCA_DDPM_X0 | MOCA_DDPM_CLIP | MOCA_DDPM_SCALE | MOCA_DDPM_MASK_C0)) return MOCA_E_BADARG;
+    if (!x0 != !noise_q) return MOCA_E_BADARG;
+    if (eps_c) {                                                 // a reverse step: at least one output; the blend wants all three
+        if (!x || !(out || x_recon || mean) || (out && !noise)) return MOCA_E_BADARG;
+        if (!mask != !x0 || (mask && !out)) return MOCA_E_BADARG;
+    } else if (!x0 || !out || mask || eps_u || x_recon || mean) { // q_sample only
+        return MOCA_E_BADARG;
+    }
+    const bool c0 = mask && (flags & MOCA_DDPM_MASK_C0);
+    if (c0 && (mask_inner <= 0 || per % mask_inner != 0)) return MOCA_E_BADARG;
+    const uintptr_t all = (uintptr_t)x | (uintptr_t)out | (uintptr_t)eps_c | (uintptr_t)eps_u | (uintptr_t)noise | (uintptr_t)x_recon |
+                          (uintptr_t)mean | (uintptr_t)x0 | (uintptr_t)noise_q;
+    if (((all | (uintptr_t)mask | (uintptr_t)coef) & 3) || ((uintptr_t)t & 7) || ((uintptr_t)state & 3)) return MOCA_E_BADARG;
+    ddpm_args a;
+    a.x = x; a.out = out; a.eps_c = eps_c; a.eps_u = eps_u; a.noise = noise; a.x_recon = x_recon; a.mean = mean;
+    a.mask = mask; a.x0 = x0; a.noise_q = noise_q; a.coef = coef; a.t = t;
+    a.t_stride = t_stride; a.per = per; a.mask_inner = c0 ? mask_inner : per;
+    a.cfg_scale = cfg_scale; a.temperature = temperature;
+    a.B = B; a.n_tab = n_tab; a.flags = flags;
+    a.vec_ok = ((all | (c0 ? 0 : (uintptr_t)mask)) & 15) == 0;
+    a.mask_vec = c0 && ((uintptr_t)mask & 15) == 0 && per % 4 == 0 && mask_inner % 4 == 0;
+    hipStream_t st = moca_stream(stream);
+    const int64_t n4 = ((int64_t)B * per + 3) / 4;
+    hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for(n4)), dim3(256), 0, st, a);
+    MOCA_CHECK_LAUNCH();
+    if (state) {
+        hipLaunchKernelGGL(ddpm_state_bump_kernel, dim3(1), dim3(1), 0, st, state);
+        MOCA_CHECK_LAUNCH();
+    }
     return MOCA_OK;
 }

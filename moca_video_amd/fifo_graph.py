@@ -543,3 +543,165 @@ class BaseEngine:
 
     def close(self):
         self.plan.close()
+
+
+class DdpmEngine:
+    """One step of `LatentDiffusion.p_sample_loop` (ddpm3d.py:638-648: p_sample at t = i for all samples, then with a mask
+    `img = q_sample(x0, ts) * mask + (1 - mask) * img`) as ONE hipGraph: [timestep rows of step k from the state counter
+    (`moca_base_set_timestep` over the table arange(timesteps), so step k runs at t = timesteps - 1 - k) + the Philox draws: the step's
+    noise and, with a mask, q_sample's, one launch over both] + the UNet forward + [`moca_ddpm_step_f32`, in place, k += 1].  Without
+    guidance the plan holds the B latents and one context segment; with it (an extension: the reference's DDPM loop has none) 2 B rows
+    with the shared prefix, as `BaseEngine`.  The latents live in the plan's input buffer; `mask` and `x0` are written once per
+    trajectory by `reset`.  The step kernel reads its per-sample t from the plan's timestep rows (row stride = frames)."""
+
+    @staticmethod
+    def supported(model, x, cond, uc=None):
+        """'crossattn' models with `c_crossattn` / `fps` conditioning only (a tensor or a list is `c_crossattn`, as apply_model takes
+        them); a guidance branch must have the same keys and fps (the shared prefix adds ONE fps embedding)"""
+        unet = getattr(getattr(model, "model", None), "diffusion_model", None)
+        if not isinstance(unet, UNetModel) or getattr(model.model, "conditioning_key", None) != "crossattn" or not x.is_cuda:
+            return False
+        as_dict = lambda c: c if isinstance(c, dict) else {"c_crossattn": c if isinstance(c, list) else [c]}
+        if cond is None:
+            return False
+        cond = as_dict(cond)
+        if "c_crossattn" not in cond or not set(cond.keys()) <= {"c_crossattn", "fps"}:
+            return False
+        reps = 1
+        if uc is not None:
+            uc = as_dict(uc)
+            if set(uc.keys()) != set(cond.keys()) or not same_fps([cond.get("fps", 16), uc.get("fps", 16)]):
+                return False
+            reps = 2
+        return reps * x.shape[0] <= 64
+
+    def __init__(self, model, x, cond, uc, cfg_scale, timesteps, mask=None, x0=None, seed=0, keep_x_recon=False):
+        from .ddpm import mask_operand
+        self.model = model
+        self.unet = unet = model.model.diffusion_model
+        dev = x.device
+        self.device = dev
+        if unet._packed is None:
+            unet._pack()
+        B, Cc, T, H, W = x.shape
+        self.shape = (B, Cc, T, H, W)
+        self.S = S = int(timesteps)
+        if not 1 <= S <= model.num_timesteps:
+            raise ValueError(f"timesteps = {timesteps}: the schedule has {model.num_timesteps} rows")
+        self.guided = uc is not None
+        cc = torch.cat(cond["c_crossattn"], 1)
+        if self.guided:
+            cu = torch.cat(uc["c_crossattn"], 1)
+            self.plan = plan = _Plan(unet, 2 * B, T, H, W, ((B, int(cc.shape[1])), (B, int(cu.shape[1]))), torch.float32, dev, shared_x=True)
+        else:
+            self.plan = plan = _Plan(unet, B, T, H, W, int(cc.shape[1]), torch.float32, dev)
+        self.coef = model._ddpm_dev(dev)["coef"]
+        self.t_table = torch.arange(S, dtype=torch.int64, device=dev)           # `for i in reversed(range(0, timesteps))`, :632,639
+        self.state = torch.zeros(8, dtype=torch.int32, device=dev)
+        n = x.numel()
+        self.n = n
+        self.n_pad = (n + 3) // 4 * 4                                            # q_sample's draw starts 16-byte aligned
+        self.masked = mask is not None
+        self.noise = torch.zeros(self.n_pad + n if self.masked else n, dtype=torch.float32, device=dev)
+        self.mask = self.x0 = None
+        self.mask_inner = 0
+        self.flags = model._ddpm_flags(clip=model.clip_denoised)
+        if self.masked:
+            m, mflag, self.mask_inner = mask_operand(mask, x.shape, dev)
+            self.flags |= mflag
+            self.mask = torch.empty_like(m)
+            self.x0 = torch.empty(n, dtype=torch.float32, device=dev)
+        self.x_recon = torch.empty(n, dtype=torch.float32, device=dev) if keep_x_recon else None
+        self.reset(x, cond, uc, seed, mask=mask, x0=x0)
+        lib = _l.load()
+        eps = plan.out.reshape(plan.B, -1)
+        st_ = _l.ptr(self.state)
+        S_ = lambda: C.c_void_p(ops.current_stream())
+        nq = self.noise[self.n_pad:] if self.masked else None
+
+        def pre():
+            _l.check(lib.moca_base_set_timestep(st_, _l.ptr(self.t_table), S, _l.ptr(plan.t_rows), plan.t_rows.numel(), S_()), "moca_base_set_timestep")
+            _l.check(lib.moca_fifo_randn_f32(st_, _l.ptr(self.noise), self.noise.numel(), S_()), "moca_fifo_randn_f32")
+
+        def post():
+            _l.check(lib.moca_ddpm_step_f32(st_, _l.ptr(plan.x_in), _l.ptr(plan.x_in), _l.ptr(eps[:B]), _l.ptr(eps[B:]) if self.guided else None,
+                                            _l.ptr(self.noise), _l.ptr(self.x_recon), None, _l.ptr(self.mask), _l.ptr(self.x0), _l.ptr(nq),
+                                            _l.ptr(self.coef), _l.ptr(plan.t_rows), T, B, int(self.coef.shape[0]), n // B, self.mask_inner,
+                                            float(cfg_scale), 1.0, self.flags, S_()), "moca_ddpm_step_f32")
+        plan.steps = [pre] + plan.steps + [post]
+
+    def reset(self, x, cond, uc=None, seed=0, mask=None, x0=None):
+        """start a new trajectory on the same plan: latents x_T, contexts, fps, mask and x0, step 0, a new noise stream"""
+        from .ddpm import mask_operand
+        plan, dev = self.plan, self.device
+        B, T = self.shape[0], self.shape[2]
+        if (uc is not None) != self.guided or (mask is not None) != self.masked:
+            raise ValueError("guidance and mask go with an engine built for them")
+        if tuple(x.shape) != self.shape:
+            raise ValueError(f"x {tuple(x.shape)} does not match the engine's latents {self.shape}")
+
+        def fps_rows(fp):
+            if isinstance(fp, int):
+                return torch.full((B * T,), fp, dtype=torch.int64, device=dev)
+            fp = torch.as_tensor(fp, device=dev).reshape(-1).to(torch.int64)
+            return (fp if fp.shape[0] == B else fp[:1].expand(B)).repeat_interleave(T)
+        branches = [cond] + ([uc] if self.guided else [])
+        if not same_fps([c.get("fps", 16) for c in branches]):
+            raise ValueError("DdpmEngine shares the UNet prefix between the two guidance branches: their fps must be equal")
+        st = _l.FifoState(0, 0, seed & 0xffffffff, (seed >> 32) & 0xffffffff, 0)
+        cur = torch.cuda.current_stream(dev)
+        plan.stream.wait_stream(cur)
+        with torch.cuda.stream(plan.stream):
+            self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
+            plan.x_in.copy_(x.to(torch.float32))
+            plan.fps_rows.copy_(torch.cat([fps_rows(c.get("fps", 16)) for c in branches]))
+            plan.set_context([torch.cat(c["c_crossattn"], 1).expand(B, -1, -1) for c in branches])
+            if self.masked:
+                m, mflag, inner = mask_operand(mask, self.shape, dev)
+                if m.shape != self.mask.shape or inner != self.mask_inner:
+                    raise ValueError(f"mask {tuple(mask.shape)} is read another way than the mask the engine was built with")
+                if tuple(x0.shape) != self.shape:
+                    raise ValueError(f"x0 {tuple(x0.shape)} does not match the engine's latents {self.shape}")
+                self.mask.copy_(m)
+                self.x0.copy_(x0.reshape(-1).to(dev, torch.float32))
+        cur.wait_stream(plan.stream)
+        self.n_iter = 0
+
+    def step(self, noise=None, mask_noise=None):
+        """one DDPM step (enqueued, not synchronised); `noise` [B,C,T,H,W] fixes p_sample's draw and, on a masked engine, `mask_noise`
+        q_sample's (both or neither: one flag tells the Philox launch that the host filled the buffer)"""
+        if self.masked and (noise is None) != (mask_noise is None):
+            raise ValueError("a masked engine takes the step's two draws together: noise and mask_noise, or neither")
+        plan = self.plan
+        cur = torch.cuda.current_stream(self.device)
+        plan.stream.wait_stream(cur)
+        with torch.cuda.stream(plan.stream):
+            if noise is not None:
+                self.noise[:self.n].copy_(noise.reshape(-1).to(self.device, torch.float32))
+                if self.masked:
+                    self.noise[self.n_pad:].copy_(mask_noise.reshape(-1).to(self.device, torch.float32))
+                self.state[4:5].fill_(1)
+            handle = plan.stream.cuda_stream
+            ops.set_stream(handle)
+            try:
+                plan._launch(handle)
+            finally:
+                ops.set_stream(None)
+        plan.n_runs += 1
+        self.n_iter += 1
+
+    def latents(self):
+        torch.cuda.current_stream(self.device).wait_stream(self.plan.stream)
+        return self.plan.x_in.clone()
+
+    def t_rows(self):
+        """the timestep rows the UNet of the last step was given (a copy)"""
+        torch.cuda.current_stream(self.device).wait_stream(self.plan.stream)
+        return self.plan.t_rows.clone()
+
+    def last_x_recon(self):
+        torch.cuda.current_stream(self.device).wait_stream(self.plan.stream)
+        return None if self.x_recon is None else self.x_recon.view(self.shape).clone()
+
+    def close(self):
+        self.plan.close()

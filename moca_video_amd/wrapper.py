@@ -11,6 +11,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .ddpm import DdpmMixin
 from .unet import UNetModel
 
 # `target:` strings of the reference YAML resolve to our classes, so an unmodified
@@ -134,20 +135,26 @@ def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2)
     return betas.numpy()
 
 
-class DenoiseModel(nn.Module):
+class DenoiseModel(DdpmMixin, nn.Module):
     """What `DDIMSampler` needs from `LatentDiffusion`: `apply_model`, `num_timesteps`, `betas`,
-    `alphas_cumprod(_prev)`, `use_scale`/`scale_arr`, `device` (ddpm3d.py:83-165,362-376,512-527)."""
+    `alphas_cumprod(_prev)`, `use_scale`/`scale_arr`, `device` (ddpm3d.py:83-165,362-376,512-527); and the model's own DDPM
+    sampler -- posterior tables, `q_sample`, `p_sample`, `p_sample_loop` with masked inpainting -- from `ddpm.DdpmMixin`."""
 
     def __init__(self, unet_config, timesteps=1000, linear_start=0.00085, linear_end=0.012, conditioning_key="crossattn",
                  use_scale=True, scale_a=1, scale_b=0.7, mid_step=400, fix_scale_bug=False, parameterization="eps",
-                 uncond_type="empty_seq", first_stage_config=None, scale_factor=1.0, cond_stage_config=None, **ignored):
+                 uncond_type="empty_seq", first_stage_config=None, scale_factor=1.0, cond_stage_config=None, v_posterior=0.,
+                 log_every_t=100, **ignored):
         super().__init__()
         self.parameterization = parameterization
+        self.v_posterior = v_posterior                   # ddpm3d.py:93: weight of the posterior variance, sigma = (1-v) beta_tilde + v beta
+        self.log_every_t = log_every_t                   # :75
+        self.clip_denoised = False                       # :390 (LatentDiffusion: what p_sample_loop hands to p_sample)
         self.uncond_type = uncond_type
         self.model = DiffusionWrapper(unet_config, conditioning_key)
         self.num_timesteps = int(timesteps)
         # register_schedule, ddpm3d.py:113-165
         betas = make_beta_schedule("linear", timesteps, linear_start=linear_start, linear_end=linear_end)
+        self._betas64 = betas                            # float64: the posterior tables (ddpm.ddpm_tables) are derived from these
         alphas = 1. - betas
         alphas_cumprod = np.cumprod(alphas, axis=0)
         alphas_cumprod_prev = np.append(1., alphas_cumprod[:-1])
