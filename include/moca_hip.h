@@ -273,7 +273,8 @@ int moca_gstat_accum_f16(const void* x, int32_t F, int32_t HW, int32_t C, int32_
 /* zero `bytes` bytes at the 16-byte aligned `ptr` on the stream (the MOCA_EP_GSTAT accumulators of a forward are zeroed by one call) */
 int moca_memset_zero(void* ptr, int64_t bytes, void* stream);
 
-/* LayerNorm over the last dim of fp16 x[M][C] (eps 1e-5): attention.py:199-201 */
+/* LayerNorm over the last dim of fp16 x[M][C] (eps 1e-5): attention.py:199-201.  C % 8 == 0, C <= 2560; x, y, gamma and beta
+ * 16-byte aligned (all four move as 16-byte vectors), else MOCA_E_BADARG. */
 int moca_layernorm_f16(const void* x, void* y, const float* gamma, const float* beta,
                        int32_t M, int32_t C, float eps, void* stream);
 
@@ -367,7 +368,8 @@ int moca_nchw_add_rows_f16(void* rows, const void* src, int32_t src_is_f32, int3
  * (openaimodel3d.py:573-577) */
 int moca_nhwc_to_ncthw(const void* y, int32_t ld, void* x, int32_t x_is_f32, int32_t B,
                        int32_t Cout, int32_t T, int32_t HW, void* stream);
-/* out[r][0:C1] = a[r], out[r][C1:C1+C2] = b[r]  (torch.cat(dim=1), openaimodel3d.py:571) */
+/* out[r][0:C1] = a[r], out[r][C1:C1+C2] = b[r]  (torch.cat(dim=1), openaimodel3d.py:571).  C1 % 8 == 0, C2 % 8 == 0; a, b and out
+ * 16-byte aligned (8-channel chunks), else MOCA_E_BADARG. */
 int moca_concat_channels_f16(const void* a, const void* b, void* out, int64_t rows,
                              int32_t C1, int32_t C2, void* stream);
 /* dst = `reps` back-to-back copies of src[0:bytes] (bytes % 16 == 0).  The batch of a classifier-free-guidance forward repeats the
@@ -375,10 +377,12 @@ int moca_concat_channels_f16(const void* a, const void* b, void* out, int64_t ro
  * first cross-attention is computed once, this copy is where the branches start to differ. */
 int moca_repeat_f16(const void* src, void* dst, int64_t bytes, int32_t reps, void* stream);
 /* sinusoidal embedding [n][dim] fp16 = [cos(t f_k), sin(t f_k)] (utils_diffusion.py:8-28);
- * t is int64 on device */
+ * t is int64 on device; a trailing zero column when dim is odd.  n * dim <= INT32_MAX (the kernel indexes with int), else
+ * MOCA_E_BADARG. */
 int moca_timestep_embedding_f16(const int64_t* t, void* out, int32_t n, int32_t dim,
                                 float max_period, void* stream);
-/* y = silu(x) (+ broadcasting helper for the embedding MLPs): out[i][:] = silu(a[i/div_a] + b[i/div_b]) */
+/* y = silu(x) (+ broadcasting helper for the embedding MLPs): out[i][:] = silu(a[i/div_a] + b[i/div_b]); b NULL = no second term,
+ * apply_silu 0 = the sum alone.  rows * C <= INT32_MAX (the kernel indexes with int), else MOCA_E_BADARG. */
 int moca_silu_add_rows_f16(const void* a, int32_t div_a, const void* b, int32_t div_b, void* out,
                            int32_t rows, int32_t C, int32_t apply_silu, void* stream);
 
@@ -422,7 +426,9 @@ int moca_channel_mix_f16(const void* z, int32_t z_is_f32, const float* w, const 
  * `scale_factor *` of get_first_stage_encoding (ddpm3d.py:458-465). */
 int moca_gaussian_sample_f32(const float* moments, const float* noise, float* out, int32_t n, int32_t z, int32_t hw,
                              float scale, void* stream);
-/* p[r][0:N] = softmax(scale * s[r][0:N]) for R rows, fp32 logits in, fp16 probabilities out; N, lds, ldp % 4 == 0.
+/* p[r][0:N] = softmax(scale * s[r][0:N]) for R rows, fp32 logits in, fp16 probabilities out; N, lds, ldp % 4 == 0, s 16-byte and p
+ * 8-byte aligned (four logits per load, four halves per store), scale > 0 (the pivot is the row max of the unscaled logits), else
+ * MOCA_E_BADARG.
  * Replaces `w_ = w_ * c**-0.5; softmax(w_, dim=2)` of AttnBlock.forward (ae_modules.py:66-68). */
 int moca_softmax_rows_f16(const float* s, void* p, int64_t R, int32_t N, int64_t lds, int64_t ldp, float scale,
                           void* stream);

@@ -297,6 +297,7 @@ extern "C" int moca_nhwc_to_ncthw(const void* y, int32_t ld, void* x, int32_t x_
 extern "C" int moca_concat_channels_f16(const void* a, const void* b, void* out, int64_t rows,
                                         int32_t C1, int32_t C2, void* stream) {
     if (!a || !b || !out || rows <= 0 || C1 <= 0 || C2 <= 0 || C1 % 8 || C2 % 8) return MOCA_E_BADARG;
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) return MOCA_E_BADARG;   // (16-byte chunks on all three)
     const int g = grid_for(rows * ((C1 + C2) / 8));
     hipLaunchKernelGGL(concat_kernel, dim3(g), dim3(256), 0, moca_stream(stream), reinterpret_cast<const half_t*>(a),
                        reinterpret_cast<const half_t*>(b), reinterpret_cast<half_t*>(out), rows, C1, C2);
@@ -315,6 +316,7 @@ extern "C" int moca_repeat_f16(const void* src, void* dst, int64_t bytes, int32_
 extern "C" int moca_timestep_embedding_f16(const int64_t* t, void* out, int32_t n, int32_t dim,
                                            float max_period, void* stream) {
     if (!t || !out || n <= 0 || dim <= 1 || max_period <= 0.f) return MOCA_E_BADARG;
+    if ((int64_t)n * dim > 0x7fffffff) return MOCA_E_BADARG;    // (the kernel indexes with int)
     const int g = grid_for((int64_t)n * dim);
     hipLaunchKernelGGL(timestep_embedding_kernel, dim3(g), dim3(256), 0, moca_stream(stream), t,
                        reinterpret_cast<half_t*>(out), n, dim, -logf(max_period));
@@ -325,6 +327,7 @@ extern "C" int moca_timestep_embedding_f16(const int64_t* t, void* out, int32_t 
 extern "C" int moca_silu_add_rows_f16(const void* a, int32_t div_a, const void* b, int32_t div_b, void* out,
                                       int32_t rows, int32_t C, int32_t apply_silu, void* stream) {
     if (!a || !out || rows <= 0 || C <= 0 || div_a <= 0 || (b && div_b <= 0)) return MOCA_E_BADARG;
+    if ((int64_t)rows * C > 0x7fffffff) return MOCA_E_BADARG;   // (the kernel indexes with int)
     const int g = grid_for((int64_t)rows * C);
     hipLaunchKernelGGL(silu_add_rows_kernel, dim3(g), dim3(256), 0, moca_stream(stream), reinterpret_cast<const half_t*>(a),
                        div_a, reinterpret_cast<const half_t*>(b), div_b > 0 ? div_b : 1, reinterpret_cast<half_t*>(out),
@@ -351,6 +354,8 @@ extern "C" int moca_channel_mix_f16(const void* z, int32_t z_is_f32, const float
 extern "C" int moca_softmax_rows_f16(const float* s, void* p, int64_t R, int32_t N, int64_t lds, int64_t ldp, float scale,
                                      void* stream) {
     if (!s || !p || R <= 0 || N <= 0 || N % 4 || lds % 4 || ldp % 4 || lds < N || ldp < N) return MOCA_E_BADARG;
+    if (((uintptr_t)s & 15) || ((uintptr_t)p & 7)) return MOCA_E_BADARG;   // (16-byte loads of four logits, 8-byte stores of four halves)
+    if (!(scale > 0.f)) return MOCA_E_BADARG;                  // (the pivot is the max of the UNSCALED logits: right for scale > 0 only)
     const int64_t blocks = (R + 3) / 4;
     if (blocks > 0x7fffffff) return MOCA_E_BADARG;
     hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, moca_stream(stream), s,

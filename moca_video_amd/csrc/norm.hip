@@ -926,6 +926,7 @@ extern "C" int moca_gstat_accum_f16(const void* x, int32_t F, int32_t HW, int32_
 extern "C" int moca_layernorm_f16(const void* x, void* y, const float* gamma, const float* beta,
                                   int32_t M, int32_t C, float eps, void* stream) {
     if (!x || !y || !gamma || !beta || M <= 0 || C <= 0 || C % 8) return MOCA_E_BADARG;
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) return MOCA_E_BADARG;   // (all four move as 16-byte vectors)
     const int nch = C / 8;
     hipStream_t st = moca_stream(stream);
     const half_t* xi = reinterpret_cast<const half_t*>(x);

@@ -131,6 +131,46 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert d80(out=P(4)) == -1 and d80(ldo=162) == -1 and d80(B=32768) == -1
 
 
+def test_small_kernel_entry_contracts():
+    """moca_layernorm_f16, moca_softmax_rows_f16 and moca_concat_channels_f16 make 16-byte (softmax stores: 8-byte) accesses and refuse
+    pointers that are not aligned for them; moca_softmax_rows_f16 refuses scale <= 0 (its pivot is the max of the unscaled logits);
+    moca_timestep_embedding_f16 and moca_silu_add_rows_f16 refuse more elements than their int index holds (include/moca_hip.h).  Every
+    call differs from an acceptable one (fake 4 KiB-aligned pointers) in exactly the named argument and returns before any launch."""
+    from moca_video_amd import lib
+    l = lib.load()
+    P = lambda off=0: C.c_void_p(0x10000 + off)
+
+    def ln(x=P(), y=P(), gamma=P(), beta=P(), M=4, Cn=64):
+        return l.moca_layernorm_f16(x, y, gamma, beta, M, Cn, 1e-5, None)
+
+    def sm(s=P(), p=P(), R=5, N=8, lds=12, ldp=16, scale=0.5):
+        return l.moca_softmax_rows_f16(s, p, R, N, lds, ldp, scale, None)
+
+    def cat(a=P(), b=P(), out=P(), rows=3, C1=8, C2=16):
+        return l.moca_concat_channels_f16(a, b, out, rows, C1, C2, None)
+
+    for name in ("x", "y", "gamma", "beta"):
+        for off in (2, 4, 8):
+            assert ln(**{name: P(off)}) == -1, (name, off)
+    assert ln(Cn=60) == -1 and ln(M=0) == -1 and ln(Cn=2568) == -1
+    for off in (4, 8):
+        assert sm(s=P(off)) == -1, off
+    for off in (2, 4):
+        assert sm(p=P(off)) == -1, off
+    for scale in (0.0, -0.5, -512 ** -0.5, float("nan")):
+        assert sm(scale=scale) == -1, scale
+    assert sm(N=6) == -1 and sm(lds=4) == -1 and sm(ldp=4) == -1 and sm(lds=10) == -1
+    for name in ("a", "b", "out"):
+        for off in (2, 8):
+            assert cat(**{name: P(off)}) == -1, (name, off)
+    assert cat(C1=4) == -1 and cat(rows=0) == -1
+    big = (1 << 31) // 320 + 1                                   # big * 320 = INT32_MAX + 193 elements
+    assert l.moca_timestep_embedding_f16(P(), P(), big, 320, 10000.0, None) == -1
+    assert l.moca_timestep_embedding_f16(P(), P(), 1 << 16, 1 << 15, 10000.0, None) == -1
+    assert l.moca_silu_add_rows_f16(P(), 1, P(), 1, P(), big, 320, 1, None) == -1
+    assert l.moca_silu_add_rows_f16(P(), 1, None, 1, P(), 1 << 16, 1 << 15, 0, None) == -1
+
+
 def test_unet_state_dict_surface_matches_reference_counts():
     """1484 tensors / 1 413 284 420 parameters, typo'd `temopral_conv` key included."""
     from moca_video_amd import UNetModel

@@ -1,5 +1,6 @@
-"""Kernel-level parity: every C-ABI kernel of libmoca_hip.so against a plain PyTorch fp32
-restatement of the same op, computed on the same (fp16-rounded) inputs.  These run on the
+"""Kernel-level parity: C-ABI kernels of libmoca_hip.so against a plain PyTorch fp32
+restatement of the same op, computed on the same (fp16-rounded) inputs.  Which GPU tests launch which entry point is kept, and
+checked, in the ledger of tests/small_kernels_ref.py (tests/test_small_kernels_cpu.py::test_ledger).  These run on the
 GPU box only (`-m gpu`).  Tolerances: fp16 outputs -> max|err| <= 3e-3 * max|ref| (one fp16
 rounding is 4.9e-4 relative; K up to ~3000 fp32-accumulated products); fp32 sampler /
 FreeInit kernels -> 1e-5 relative."""
