@@ -85,20 +85,14 @@ class BlockRunner:
         later calls replay it."""
         pl = self.plan
         cur = torch.cuda.current_stream(x.device)
-        pl.stream.wait_stream(cur)
-        with torch.cuda.stream(pl.stream):
+        with pl._enqueue(cur):
             self.x_in.copy_(x.permute(0, 2, 3, 1).reshape(-1, self.cin))
             if self.emb_in is not None:
                 self.emb_in.copy_(emb)
             if self.ctx_in is not None:
                 self.ctx_in.copy_(context.reshape(self.B * self.L, -1))
-            ops.set_stream(pl.stream.cuda_stream)
-            try:
-                pl._launch(pl.stream.cuda_stream)
-            finally:
-                ops.set_stream(None)
+            pl._replay()
             o = self.out
             y = o.buf.view(o.F, o.H, o.W, o.C).permute(0, 3, 1, 2).float()
-        pl.n_runs += 1
         cur.wait_stream(pl.stream)
         return y

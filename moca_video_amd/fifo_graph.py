@@ -19,8 +19,8 @@ The recorded sequence (gather + ~640 UNet launches + tail) is run eagerly once, 
 as one `hipGraphLaunch` from then on; the host never synchronises inside the loop."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-import functools
 
 import numpy as np
 import torch
@@ -46,7 +46,63 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-class FifoEngine:
+def state_block(seed, it=0):
+    """a `moca_fifo_state` (head 0, iteration `it`, the 64-bit seed, ext_noise 0) as the host int32 tensor the device block is written from"""
+    st = _l.FifoState(0, it, seed & 0xffffffff, (seed >> 32) & 0xffffffff, 0)
+    return torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32)
+
+
+def fps_rows(fp, B, T, dev):
+    """the fps of B videos of T frames as the [B*T] int64 rows of the plan: an int, one value for all videos, or one per video"""
+    if isinstance(fp, int):
+        return torch.full((B * T,), fp, dtype=torch.int64, device=dev)
+    fp = torch.as_tensor(fp, device=dev).reshape(-1).to(torch.int64)
+    return (fp if fp.shape[0] == B else fp[:1].expand(B)).repeat_interleave(T)
+
+
+class _StepEngine:
+    """what the three one-graph engines share: a `_Plan` whose recorded UNet forward is wrapped into the engine's own launches, one
+    enqueue per step on the plan's stream, accessors that wait for that stream before they copy"""
+
+    def _wrap_plan(self, pre, post):
+        """a step = pre() + the UNet forward + post(), recorded and captured as one sequence"""
+        self.plan.steps = [pre] + self.plan.steps + [post]
+
+    @contextlib.contextmanager
+    def _step(self):
+        """`with self._step():` -- the body (host-given noise, uploads) is enqueued on the plan's stream, ordered after the current one;
+        then one replay of the wrapped sequence.  Nothing is synchronised."""
+        with self.plan._enqueue():
+            yield
+            self.plan._replay()
+        self.n_iter += 1
+
+    def _fix_noise(self, *pairs):
+        """host-given draws: copy every (destination slice, tensor) and tell the Philox launch to leave the buffer alone (ext_noise)"""
+        for dst, src in pairs:
+            dst.copy_(src.reshape(-1).to(self.device, torch.float32))
+        self.state[4:5].fill_(1)
+
+    def _refuse_unequal_fps(self, fps):
+        if not same_fps(fps):
+            raise ValueError(f"{type(self).__name__} shares the UNet prefix between the two guidance branches: their fps must be equal")
+
+    def sync_to(self, stream=None):
+        (stream or torch.cuda.current_stream(self.device)).wait_stream(self.plan.stream)
+
+    def _copy(self, t, shape=None):
+        """a copy of an engine buffer as of the last enqueued step (None stays None)"""
+        self.sync_to()
+        return None if t is None else (t if shape is None else t.view(shape)).clone()
+
+    def latents(self):
+        return self._copy(self.plan.x_in)
+
+    def close(self):
+        self.plan.close()
+
+
+class FifoEngine(_StepEngine):
     """Device-resident MoCA-FIFO loop, prompt mode and DAVIS-video mode.  `supported(...)` says whether a call can run here;
     `fifo.fifo_ddim_sampling` falls back to its host-driven loop otherwise (a mask-producer callback, per-call mask lists, a model
     that is not ours).
@@ -120,11 +176,9 @@ class FifoEngine:
         self.gather_reps = 1 if shared or not guided else 2
         self.plan = plan = _Plan(unet, B, f, H, W, segs, torch.float32, dev, shared_x=shared)
 
-        def fps_rows(fp):
-            if isinstance(fp, int):
-                return torch.full((nW * f,), fp, dtype=torch.int64, device=dev)
-            return torch.as_tensor(fp, device=dev).reshape(-1)[:1].to(torch.int64).expand(nW * f)
-        fr = [fps_rows(fps_c)] + ([fps_rows(uc.get("fps", fps_c))] if guided else [])
+        # (one fps per branch: of a tensor the first value serves all windows)
+        one = lambda fp: fp if isinstance(fp, int) else torch.as_tensor(fp).reshape(-1)[:1]
+        fr = [fps_rows(one(fp), nW, f, dev) for fp in [fps_c] + ([uc.get("fps", fps_c)] if guided else [])]
         with torch.cuda.stream(plan.stream):
             plan.t_rows.copy_(to_dev(t_rows).reshape(-1).repeat(self.reps))
             plan.fps_rows.copy_(torch.cat(fr))
@@ -136,8 +190,7 @@ class FifoEngine:
         # ---- device state
         f32 = dict(dtype=torch.float32, device=dev)
         self.queue = latents[0].to(torch.float32).reshape(Cc, Q, HW).clone()
-        st = _l.FifoState(0, 0, seed & 0xffffffff, (seed >> 32) & 0xffffffff, 0)
-        self.state = torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32).to(dev)
+        self.state = state_block(seed).to(dev)
         n_win = nW * Cc * f * HW
         self.noise = torch.zeros(n_win + 2 * Cc * HW, **f32)         # [nW][C][f][HW] window noise | [C][HW] enqueued noise | [C][HW] anchor draw
         self.moments = None
@@ -220,7 +273,7 @@ class FifoEngine:
             _l.check(lib.moca_fifo_advance_f32(st_, q_, _l.ptr(self.newframe), _l.ptr(self.emitted), self.n_slots, self.emit_frame,
                                                _l.ptr(self.mask), _l.ptr(self.mask_sums), Cc, Q, HW, S()), "moca_fifo_advance_f32")
         self.n_unet_launches = len(plan.steps)
-        plan.steps = [pre] + plan.steps + [post]
+        self._wrap_plan(pre, post)
         self.n_iter = 0
         sampler.momentum = self.momentum[nW - 1].view(1, Cc, f, H, W)      # what the reference's last call (rank 0) leaves behind
 
@@ -283,10 +336,8 @@ class FifoEngine:
         if c.dim() != 3 or c.shape[0] != 1 or c.shape[1] != L:
             raise ValueError(f"set_context: the plan's conditional segment holds [1, {L}, D] contexts, got {tuple(c.shape)}")
         plan = self.plan
-        cur = torch.cuda.current_stream(self.device)
         src = c.to(self.device)
-        plan.stream.wait_stream(cur)
-        with torch.cuda.stream(plan.stream):
+        with plan._enqueue():
             plan.set_context([src.expand(self.nW, -1, -1)])       # (only the first segment: zip over the plan's segments)
         src.record_stream(plan.stream)
 
@@ -295,33 +346,16 @@ class FifoEngine:
         """one outer iteration (enqueued, not synchronised).  `noise` = list over windows (reference order: rank 2n-1 .. 0) of
         [1,C,f,H,W] tensors, `shift_noise` [1,C,H,W] and (DAVIS mode) `anchor_noise` [1,C,1,H,W] fix the draws (all or none);
         `sam_masks` (engines built with sam_capacity): this iteration's candidate masks, see `_upload_sam`."""
-        plan = self.plan
-        cur = torch.cuda.current_stream(self.device)
-        plan.stream.wait_stream(cur)
-        with torch.cuda.stream(plan.stream):
+        with self._step():
             if self.sam_capacity > 0:
                 self._upload_sam(sam_masks)
             elif sam_masks is not None:
                 raise ValueError("this engine was built without sam_capacity")
             if noise is not None:
-                n_win = self.nW * self.C * self.f * self.HW
-                self.noise[:n_win].view(self.nW, -1).copy_(torch.stack([n.reshape(-1) for n in noise]).to(self.device, torch.float32))
-                chw = self.C * self.HW
-                self.noise[n_win:n_win + chw].copy_(shift_noise.reshape(-1).to(self.device, torch.float32))
-                if anchor_noise is not None:
-                    self.noise[n_win + chw:].copy_(anchor_noise.reshape(-1).to(self.device, torch.float32))
-                self.state[4:5].fill_(1)                                 # ext_noise (the advance clears it)
-            handle = plan.stream.cuda_stream
-            ops.set_stream(handle)
-            try:
-                plan._launch(handle)
-            finally:
-                ops.set_stream(None)
-        plan.n_runs += 1
-        self.n_iter += 1
-
-    def sync_to(self, stream=None):
-        (stream or torch.cuda.current_stream(self.device)).wait_stream(self.plan.stream)
+                n_win, chw = self.nW * self.C * self.f * self.HW, self.C * self.HW
+                self._fix_noise((self.noise[:n_win], torch.stack([n.reshape(-1) for n in noise])),
+                                (self.noise[n_win:n_win + chw], shift_noise),
+                                *([(self.noise[n_win + chw:], anchor_noise)] if anchor_noise is not None else []))   # (the advance clears ext_noise)
 
     def latents(self):
         """the queue in frame order [1,C,Q,H,W] (a copy; the ring itself never moves)"""
@@ -347,11 +381,8 @@ class FifoEngine:
         v = lambda t: [t[w].view(1, self.C, self.f, self.H, self.W) for w in range(self.nW)]
         return v(self.x_prev), v(self.pred_x0)
 
-    def close(self):
-        self.plan.close()
 
-
-class BaseEngine:
+class BaseEngine(_StepEngine):
     """One step of base sampling -- `DDIMSampler.ddim_sampling`'s loop body (ddim.py:226-252: two UNet calls on the same latents, guidance,
     the DDIM update with `use_scale`, fresh noise) -- as ONE hipGraph: [timestep rows of step i] + the shared-prefix UNet forward of
     the B latents x (conditional, unconditional) + [noise, guidance + update in place, i += 1].  The latents live in the plan's input
@@ -412,12 +443,6 @@ class BaseEngine:
         unet._check_adapter(features_adapter)
         self.plan = plan = _Plan(unet, 2 * B, T, H, W, segs, torch.float32, dev, shared_x=True, pieces=pieces,
                                  adapter=None if features_adapter is None else unet.adapter_sites)
-
-        def fps_rows(fp):
-            if isinstance(fp, int):
-                return torch.full((B * T,), fp, dtype=torch.int64, device=dev)
-            fp = torch.as_tensor(fp, device=dev).reshape(-1).to(torch.int64)
-            return (fp if fp.shape[0] == B else fp[:1].expand(B)).repeat_interleave(T)
         f32 = np.float32
         coef = np.zeros((S, 8), np.float32)
         use_scale = bool(sampler.use_scale)
@@ -434,7 +459,6 @@ class BaseEngine:
         n = x.numel()
         self.noise = torch.zeros(n, dtype=torch.float32, device=dev)
         self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev) if keep_pred_x0 else None
-        self._fps_rows = fps_rows
         self.reset(x, cond, uc, seed, features_adapter=features_adapter)
         lib = _l.load()
         eps = plan.out.reshape(2 * B, -1)
@@ -448,37 +472,29 @@ class BaseEngine:
         def post():
             _l.check(lib.moca_base_ddim_step_f32(st_, _l.ptr(plan.x_in), _l.ptr(eps[:B]), _l.ptr(eps[B:]), _l.ptr(self.noise), _l.ptr(self.pred_x0),
                                                  _l.ptr(self.coef), S, float(cfg_scale), 1 if use_scale else 0, n, S_()), "moca_base_ddim_step_f32")
-        plan.steps = [pre] + plan.steps + [post]
+        self._wrap_plan(pre, post)
 
     def reset(self, x, cond, uc, seed=0, features_adapter=None):
         """start a new trajectory on the same plan: latents x_T, contexts, fps, adapter maps, iteration 0, a new noise stream"""
         plan, dev = self.plan, self.device
         if (features_adapter is None) != (plan.adapter_in is None):
             raise ValueError("features_adapter goes with an engine built for it")
-        B = self.shape[0]
-        fps_c, fps_u = (16, 16) if self.hybrid else (cond.get("fps", 16), uc.get("fps", 16))
-        if not same_fps([fps_c, fps_u]):
-            raise ValueError("BaseEngine shares the UNet prefix between the two guidance branches: their fps must be equal")
+        B, T = self.shape[0], self.shape[2]
+        fps = (16, 16) if self.hybrid else (cond.get("fps", 16), uc.get("fps", 16))
+        self._refuse_unequal_fps(fps)
         cc, cu = (torch.cat(c["c_crossattn"], 1).expand(B, -1, -1) for c in (cond, uc))
-        st = _l.FifoState(0, 0, seed & 0xffffffff, (seed >> 32) & 0xffffffff, 0)
-        cur = torch.cuda.current_stream(dev)
-        plan.stream.wait_stream(cur)
-        with torch.cuda.stream(plan.stream):
-            self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
-            st.iter = -1                                         # (no step ever draws at this iteration: steps count up from 0)
-            self.enc_state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
+        with plan._enqueue():
+            self.state.copy_(state_block(seed))
+            self.enc_state.copy_(state_block(seed, -1))          # (no step ever draws at this iteration: steps count up from 0)
             plan.x_in.copy_(x.to(torch.float32))
-            plan.fps_rows.copy_(torch.cat([self._fps_rows(fps_c), self._fps_rows(fps_u)]))
+            plan.fps_rows.copy_(torch.cat([fps_rows(fp, B, T, dev) for fp in fps]))
             plan.set_context([cc, cu])
             if features_adapter is not None:
                 plan.set_adapter(list(features_adapter))
             if plan.pieces is not None:
-                ops.set_stream(plan.stream.cuda_stream)
-                try:
+                with plan._ops_stream():
                     plan.set_concat(cond["c_concat"])
-                finally:
-                    ops.set_stream(None)
-        cur.wait_stream(plan.stream)
+        self.sync_to()
         self.n_iter = 0
 
     def encode(self, x0, t_index, noise=None):
@@ -500,9 +516,7 @@ class BaseEngine:
             raise IndexError(f"index {t.tolist()} is out of bounds for the {n_tab}-entry schedule table")
         lib = _l.load()
         n = self.noise.numel()
-        cur = torch.cuda.current_stream(dev)
-        plan.stream.wait_stream(cur)
-        with torch.cuda.stream(plan.stream):
+        with plan._enqueue():
             h = C.c_void_p(plan.stream.cuda_stream)
             src = x0.to(dev, torch.float32).contiguous()
             t_d = t.to(dev, torch.int64).contiguous()
@@ -517,35 +531,15 @@ class BaseEngine:
 
     def step(self, noise=None):
         """one DDIM step (enqueued, not synchronised); `noise` [B,C,T,H,W] fixes the draw"""
-        plan = self.plan
-        cur = torch.cuda.current_stream(self.device)
-        plan.stream.wait_stream(cur)
-        with torch.cuda.stream(plan.stream):
+        with self._step():
             if noise is not None:
-                self.noise.copy_(noise.reshape(-1).to(self.device, torch.float32))
-                self.state[4:5].fill_(1)
-            handle = plan.stream.cuda_stream
-            ops.set_stream(handle)
-            try:
-                plan._launch(handle)
-            finally:
-                ops.set_stream(None)
-        plan.n_runs += 1
-        self.n_iter += 1
-
-    def latents(self):
-        torch.cuda.current_stream(self.device).wait_stream(self.plan.stream)
-        return self.plan.x_in.clone()
+                self._fix_noise((self.noise, noise))
 
     def last_pred_x0(self):
-        torch.cuda.current_stream(self.device).wait_stream(self.plan.stream)
-        return None if self.pred_x0 is None else self.pred_x0.view(self.shape).clone()
-
-    def close(self):
-        self.plan.close()
+        return self._copy(self.pred_x0, self.shape)
 
 
-class DdpmEngine:
+class DdpmEngine(_StepEngine):
     """One step of `LatentDiffusion.p_sample_loop` (ddpm3d.py:638-648: p_sample at t = i for all samples, then with a mask
     `img = q_sample(x0, ts) * mask + (1 - mask) * img`) as ONE hipGraph: [timestep rows of step k from the state counter
     (`moca_base_set_timestep` over the table arange(timesteps), so step k runs at t = timesteps - 1 - k) + the Philox draws: the step's
@@ -628,7 +622,7 @@ class DdpmEngine:
                                             _l.ptr(self.noise), _l.ptr(self.x_recon), None, _l.ptr(self.mask), _l.ptr(self.x0), _l.ptr(nq),
                                             _l.ptr(self.coef), _l.ptr(plan.t_rows), T, B, int(self.coef.shape[0]), n // B, self.mask_inner,
                                             float(cfg_scale), 1.0, self.flags, S_()), "moca_ddpm_step_f32")
-        plan.steps = [pre] + plan.steps + [post]
+        self._wrap_plan(pre, post)
 
     def reset(self, x, cond, uc=None, seed=0, mask=None, x0=None):
         """start a new trajectory on the same plan: latents x_T, contexts, fps, mask and x0, step 0, a new noise stream"""
@@ -639,22 +633,12 @@ class DdpmEngine:
             raise ValueError("guidance and mask go with an engine built for them")
         if tuple(x.shape) != self.shape:
             raise ValueError(f"x {tuple(x.shape)} does not match the engine's latents {self.shape}")
-
-        def fps_rows(fp):
-            if isinstance(fp, int):
-                return torch.full((B * T,), fp, dtype=torch.int64, device=dev)
-            fp = torch.as_tensor(fp, device=dev).reshape(-1).to(torch.int64)
-            return (fp if fp.shape[0] == B else fp[:1].expand(B)).repeat_interleave(T)
         branches = [cond] + ([uc] if self.guided else [])
-        if not same_fps([c.get("fps", 16) for c in branches]):
-            raise ValueError("DdpmEngine shares the UNet prefix between the two guidance branches: their fps must be equal")
-        st = _l.FifoState(0, 0, seed & 0xffffffff, (seed >> 32) & 0xffffffff, 0)
-        cur = torch.cuda.current_stream(dev)
-        plan.stream.wait_stream(cur)
-        with torch.cuda.stream(plan.stream):
-            self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
+        self._refuse_unequal_fps([c.get("fps", 16) for c in branches])
+        with plan._enqueue():
+            self.state.copy_(state_block(seed))
             plan.x_in.copy_(x.to(torch.float32))
-            plan.fps_rows.copy_(torch.cat([fps_rows(c.get("fps", 16)) for c in branches]))
+            plan.fps_rows.copy_(torch.cat([fps_rows(c.get("fps", 16), B, T, dev) for c in branches]))
             plan.set_context([torch.cat(c["c_crossattn"], 1).expand(B, -1, -1) for c in branches])
             if self.masked:
                 m, mflag, inner = mask_operand(mask, self.shape, dev)
@@ -664,7 +648,7 @@ class DdpmEngine:
                     raise ValueError(f"x0 {tuple(x0.shape)} does not match the engine's latents {self.shape}")
                 self.mask.copy_(m)
                 self.x0.copy_(x0.reshape(-1).to(dev, torch.float32))
-        cur.wait_stream(plan.stream)
+        self.sync_to()
         self.n_iter = 0
 
     def step(self, noise=None, mask_noise=None):
@@ -672,36 +656,13 @@ class DdpmEngine:
         q_sample's (both or neither: one flag tells the Philox launch that the host filled the buffer)"""
         if self.masked and (noise is None) != (mask_noise is None):
             raise ValueError("a masked engine takes the step's two draws together: noise and mask_noise, or neither")
-        plan = self.plan
-        cur = torch.cuda.current_stream(self.device)
-        plan.stream.wait_stream(cur)
-        with torch.cuda.stream(plan.stream):
+        with self._step():
             if noise is not None:
-                self.noise[:self.n].copy_(noise.reshape(-1).to(self.device, torch.float32))
-                if self.masked:
-                    self.noise[self.n_pad:].copy_(mask_noise.reshape(-1).to(self.device, torch.float32))
-                self.state[4:5].fill_(1)
-            handle = plan.stream.cuda_stream
-            ops.set_stream(handle)
-            try:
-                plan._launch(handle)
-            finally:
-                ops.set_stream(None)
-        plan.n_runs += 1
-        self.n_iter += 1
-
-    def latents(self):
-        torch.cuda.current_stream(self.device).wait_stream(self.plan.stream)
-        return self.plan.x_in.clone()
+                self._fix_noise((self.noise[:self.n], noise), *([(self.noise[self.n_pad:], mask_noise)] if self.masked else []))
 
     def t_rows(self):
         """the timestep rows the UNet of the last step was given (a copy)"""
-        torch.cuda.current_stream(self.device).wait_stream(self.plan.stream)
-        return self.plan.t_rows.clone()
+        return self._copy(self.plan.t_rows)
 
     def last_x_recon(self):
-        torch.cuda.current_stream(self.device).wait_stream(self.plan.stream)
-        return None if self.x_recon is None else self.x_recon.view(self.shape).clone()
-
-    def close(self):
-        self.plan.close()
+        return self._copy(self.x_recon, self.shape)

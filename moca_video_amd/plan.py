@@ -11,6 +11,7 @@ not exist here.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -94,7 +95,7 @@ class _LNRef:
 
 class _PlanBase:
     """pool + recorded launch list + hipGraph capture/replay, shared by the UNet plan and the VAE-decoder plan"""
-    _defer_slabs = False     # (UNet plan only: every feature map it creates reaches gn() or _drop_colsum(), which release the deferred workspace)
+    _defer_slabs = False     # (UNet plan only: every feature map it creates reaches gn() or _retire(), which release the deferred workspace)
 
     def __init__(self, model, device):
         self.model = model
@@ -109,7 +110,6 @@ class _PlanBase:
         self.graph_failed = False
         self.n_runs = 0
         self._gstat_buf, self._gstat_used, self._last_gemm_step = None, 0, None
-        self._last_slabs = None
         self._held = {}          # data_ptr -> [pending deferred reduces that read it, buffer released meanwhile]
         self._gstat_full = []
         self.reps = 1            # > 1: the batch is `reps` context variants of the same Bx latents (_Plan: shared prefix)
@@ -129,13 +129,10 @@ class _PlanBase:
         launch: the largest of the weights that asked for it)"""
         if self.prefetch_on:
             for j, ws in self._prefetch_at.items():
-                prod = self.steps[j]
-                kw = dict(prod.keywords)
+                host = self.steps[j]
                 # the spare blocks must be done before the host's tiles are, or they prolong it: only hosts with enough work
-                if 2.0 * kw["M"] * prod.args[1].N * prod.args[1].K < PREFETCH_HOST_FLOP:
-                    continue
-                kw["prefetch"] = max(ws, key=lambda w: w.numel())
-                self.steps[j] = functools.partial(prod.func, *prod.args, **kw)
+                if 2.0 * host.keywords["M"] * host.args[1].N * host.args[1].K >= PREFETCH_HOST_FLOP:
+                    self._retarget(j, prefetch=max(ws, key=lambda w: w.numel()))
         self._prefetch_at = {}
 
     def close(self):
@@ -157,6 +154,13 @@ class _PlanBase:
     # ------------------------------------------------------------------ emit helpers
     def _emit(self, fn, *args, **kw):
         self.steps.append(functools.partial(fn, *args, **kw))
+
+    def _retarget(self, i, **changes):
+        """re-record launch `i` with some keywords replaced: the ONE place a recorded step is rewritten (a producer that takes on,
+        or is relieved of, what it leaves behind for its consumer; the prefetch operand).  Returns the step as it was."""
+        prod = self.steps[i]
+        self.steps[i] = functools.partial(prod.func, *prod.args, **{**prod.keywords, **changes})
+        return prod
 
     def _release(self, *bufs):
         for b in bufs:
@@ -187,8 +191,9 @@ class _PlanBase:
         return gemm_splits(M, pw)
 
     def _gemm(self, a, pw, M, *, out_cols=None, want_colsum=False, **kw):
-        """returns `out`, or `(out, colsum)` with want_colsum: colsum = (f32 [row tiles][N][2], rows per tile) when this launch
-        can leave the GroupNorm statistics of its output behind (moca_gemm_colsum_rows), else None"""
+        """returns `out`, or `(out, colsum, slabs)` with want_colsum (the two promises of _FMap, see _gemm_map):
+        colsum = (f32 [row tiles][N][2], rows per tile) when this launch can leave the GroupNorm statistics of its output behind
+        (moca_gemm_colsum_rows), else None; slabs = the split-K workspace whose reduce may still move into the consumer, else None"""
         n_out = pw.n_out if pw.geglu else pw.N
         out = self.pool.get(M, n_out)
         splits = self._splits(M, pw)
@@ -202,7 +207,7 @@ class _PlanBase:
                 cs = (self.pool.get((M + rows - 1) // rows, 2 * pw.N, torch.float32), rows)
         self._note_gemm(pw)
         self._emit(ops.gemm, a, pw, out, M=M, splits=splits, splitk_ws=ws, colsum=None if cs is None else cs[0], **kw)
-        self._last_slabs = None
+        slabs = None
         if ws is not None:
             if want_colsum and SPLITK_GN and self._defer_slabs:   # the workspace stays reserved until the consumer is known
                 ptrs = []                                       # ... and so do the operands a fused reduce re-reads there
@@ -210,13 +215,21 @@ class _PlanBase:
                     if t is not None and t.data_ptr() not in self._pinned:
                         self._held.setdefault(t.data_ptr(), [0, None])[0] += 1
                         ptrs.append(t.data_ptr())
-                self._last_slabs = (ws, self._last_gemm_step, tuple(ptrs))   # (_FMap.slabs; released by gn() / _drop_colsum())
+                slabs = (ws, self._last_gemm_step, tuple(ptrs))   # (_FMap.slabs; released by gn() / _drop_colsum())
             else:
                 self.pool.put(ws)
-        return (out, cs) if want_colsum else out
+        return (out, cs, slabs) if want_colsum else out
 
-    def linear(self, a, M, pw, residual=None, lda=None, want_colsum=False):
-        return self._gemm(a, pw, M, lda=lda if lda is not None else a.stride(-2), residual=residual, want_colsum=want_colsum)
+    def _gemm_map(self, F, H, W, a, pw, **kw):
+        """a GEMM whose output is a feature map [F*H*W][pw.N]: the map is made HERE with everything its producer promised -- per-tile
+        column sums (with the index of the launch, so that a consumer can re-target it) and / or the deferred split-K workspace"""
+        out, cs, slabs = self._gemm(a, pw, F * H * W, want_colsum=True, **kw)
+        o = _FMap(out, F, H, W, pw.N, cs, src=self._last_gemm_step if cs is not None else None)
+        o.slabs = slabs
+        return o
+
+    def linear(self, a, M, pw, residual=None, lda=None):
+        return self._gemm(a, pw, M, lda=lda if lda is not None else a.stride(-2), residual=residual)
 
     def conv(self, fm, pw, *, stride=1, up=0, rowadd=None, rowadd_div=1, residual=None):
         """3x3 conv; the output carries its GroupNorm statistics when the launch can produce them"""
@@ -226,12 +239,8 @@ class _PlanBase:
             oH, oW = (fm.H - 1) // 2 + 1, (fm.W - 1) // 2 + 1
         else:
             oH, oW = fm.H, fm.W
-        M = fm.F * oH * oW
-        out, cs = self._gemm(fm.buf, pw, M, mode=_l.MOCA_A_CONV3X3, conv=(fm.C, fm.H, fm.W, oH, oW, stride, up),
-                             rowadd=rowadd, rowadd_div=rowadd_div, residual=residual, want_colsum=True)
-        o = _FMap(out, fm.F, oH, oW, pw.N, cs, src=self._last_gemm_step if cs is not None else None)
-        o.slabs = self._last_slabs
-        return o
+        return self._gemm_map(fm.F, oH, oW, fm.buf, pw, mode=_l.MOCA_A_CONV3X3, conv=(fm.C, fm.H, fm.W, oH, oW, stride, up),
+                              rowadd=rowadd, rowadd_div=rowadd_div, residual=residual)
 
     def upconv(self, fm, conv):
         """`Upsample` (openaimodel3d.py:96-106: nearest x2, then conv3x3).  With enough low-resolution rows to fill the chip per
@@ -258,74 +267,69 @@ class _PlanBase:
         return up
 
     def tconv(self, fm, pw, residual=None):
-        out, cs = self._gemm(fm.buf, pw, fm.M, mode=_l.MOCA_A_TCONV3, tconv=(fm.C, self.T, fm.H * fm.W), residual=residual,
-                             want_colsum=True)
-        o = _FMap(out, fm.F, fm.H, fm.W, pw.N, cs, src=self._last_gemm_step if cs is not None else None)
-        o.slabs = self._last_slabs
-        return o
+        return self._gemm_map(fm.F, fm.H, fm.W, fm.buf, pw, mode=_l.MOCA_A_TCONV3, tconv=(fm.C, self.T, fm.H * fm.W), residual=residual)
 
     def gn(self, fm, gb, *, fps, eps, silu, x_dead=False):
-        """GroupNorm(32) (+SiLU).  With `fm.colsum` (left by the producing GEMM) and row tiles that do not straddle frames the
-        statistics pass over x disappears: finalize-from-column-sums + apply; otherwise the three-launch / slab path."""
+        """GroupNorm(32) (+SiLU), cashing in whatever the producer of `fm` promised (_FMap): a deferred split-K reduce moves into this
+        launch; finished statistics (accumulated by a concat, or by the producing GEMM once it is re-targeted) leave only the apply
+        pass; otherwise the plain statistics + apply launch."""
         if isinstance(fm, _CatMap):                            # the virtual concat: both sources read in place, statistics finished
             y = self.pool.get(fm.M, fm.C)
             self._emit(ops.groupnorm_gstat_cat, fm.h.buf, fm.skip.buf, y, gb[0], gb[1], fm.gcat, fm.gb, F=fm.F, HW=fm.H * fm.W,
                        C1=fm.h.C, C2=fm.skip.C, frames_per_stat=fps, eps=eps, silu=silu, Fb=fm.Fb)
             assert fps == 1
             return y
-        if getattr(fm, "slabs", None) is not None:
+        HW = fm.H * fm.W
+        if fm.slabs is not None:
             # the producer ran split-K: its reduce launch moves into this GroupNorm (x_dead: nobody else reads fm.buf -- it is not written)
-            slabs = fm.slabs
-            wsk, src = slabs[0], slabs[1]
-            prod = self.steps[src]
-            kw = dict(prod.keywords)
-            fm.slabs = None
+            slabs, fm.slabs = fm.slabs, None
+            prod = self.steps[slabs[1]]
+            kw, y = prod.keywords, None
             # (only per-frame statistics: 1024 slabs fill the chip and the launch beats reduce + GroupNorm by 2.3 us; the 64 slabs of the
             #  16-frame GroupNorms are slower fused, 18.6 against 7.9 + 7.9 us -- profiles/r05_ab_splitk_groupnorm.txt)
-            if (fps == 1 or SPLITK_GN_ALL) and \
-                    ops.gemm_splitk_groupnorm_ok(prod.args[0], prod.args[1], HW=fm.H * fm.W, frames_per_stat=fps, **kw):
+            if (fps == 1 or SPLITK_GN_ALL) and ops.gemm_splitk_groupnorm_ok(prod.args[0], prod.args[1], HW=HW, frames_per_stat=fps, **kw):
                 y = self.pool.get(fm.M, fm.C)
-                kw["slabs"] = True
-                self.steps[src] = functools.partial(prod.func, *prod.args, **kw)
-                self._emit(ops.gemm_splitk_groupnorm, prod.args[0], prod.args[1], prod.args[2], y, gb[0], gb[1], HW=fm.H * fm.W,
-                           frames_per_stat=fps, eps=eps, silu=silu, write_x=not x_dead, **kw)
-                self.pool.put(wsk)
-                self._unhold(slabs)
-                return y
-            self.pool.put(wsk)
+                self._retarget(slabs[1], slabs=True)
+                self._emit(ops.gemm_splitk_groupnorm, prod.args[0], prod.args[1], prod.args[2], y, gb[0], gb[1], HW=HW,
+                           frames_per_stat=fps, eps=eps, silu=silu, write_x=not x_dead, **kw, slabs=True)
+            self.pool.put(slabs[0])
             self._unhold(slabs)
+            if y is not None:
+                return y
         y = self.pool.get(fm.M, fm.C)
-        HW = fm.H * fm.W
         ws = self.pool.get(1, ops.groupnorm_ws_floats(fm.F, HW, fm.C), torch.float32)
-        cs = fm.colsum
-        if fm.gstat is not None and fm.gstat[1] == fps:       # (the concat that produced fm accumulated the statistics)
-            self._emit(ops.groupnorm_gstat, fm.buf, y, gb[0], gb[1], fm.gstat[0], F=fm.F, HW=HW, Cn=fm.C, frames_per_stat=fps,
-                       eps=eps, silu=silu)
-        elif cs is not None and (fps * HW) % cs[1] == 0 and fm.src is not None:
-            # the producer is re-targeted: instead of per-tile column sums it accumulates the FINISHED statistics of this
-            # GroupNorm (fixed-point atomics per (statistics group, channel group), MOCA_EP_GSTAT) -- no finalize launch
-            if fps > 16:                                  # (groups of up to 16 frames, per-frame ones included: as before)
-                _check_gstat_range(fps * HW)
-            prod = self.steps[fm.src]
-            slot = self._gstat_slot((fm.F // fps) * 64)
-            kw = dict(prod.keywords)
-            kw["colsum"] = None
-            kw["gstat"] = (slot, fps * HW)
-            self.steps[fm.src] = functools.partial(prod.func, *prod.args, **kw)
-            self.pool.put(cs[0])
-            fm.colsum = None
-            fm.gstat_own = (slot, fps)
-            self._emit(ops.groupnorm_gstat, fm.buf, y, gb[0], gb[1], slot, F=fm.F, HW=HW, Cn=fm.C, frames_per_stat=fps,
-                       eps=eps, silu=silu)
-        elif cs is not None and (fps * HW) % cs[1] == 0:      # no row tile straddles two statistics groups
-            fm.cs_used = True
-            self._emit(ops.groupnorm_colsum, fm.buf, y, gb[0], gb[1], cs[0], tile_rows=cs[1], F=fm.F, HW=HW, Cn=fm.C,
-                       frames_per_stat=fps, eps=eps, silu=silu, ws=ws)
-        else:
+        if self._stats_ready(fm, fps):
+            self._emit(ops.groupnorm_gstat, fm.buf, y, gb[0], gb[1], self._finished_stats(fm, fps), F=fm.F, HW=HW, Cn=fm.C,
+                       frames_per_stat=fps, eps=eps, silu=silu)
+        else:                                                 # (nothing promised, or row tiles that straddle two statistics groups)
             self._emit(ops.groupnorm, fm.buf, y, gb[0], gb[1], F=fm.F, HW=HW, Cn=fm.C, frames_per_stat=fps,
                        eps=eps, silu=silu, ws=ws)
         self.pool.put(ws)
         return y
+
+    def _stats_ready(self, fm, fps):
+        """can `_finished_stats(fm, fps)` deliver?  Either the concat that produced fm accumulated these statistics, or fm's producer left
+        per-tile column sums whose row tiles lie inside one statistics group (fps frames): then it can be re-targeted"""
+        if fm.gstat is not None and fm.gstat[1] == fps:
+            return True
+        return fm.colsum is not None and (fps * fm.H * fm.W) % fm.colsum[1] == 0
+
+    def _finished_stats(self, fm, fps):
+        """the FINISHED GroupNorm statistics of fm over groups of `fps` frames (call only where _stats_ready): returns the accumulators.
+        Where fm still holds per-tile column sums its producer is re-targeted: it accumulates the finished statistics instead
+        (fixed-point atomics per (statistics group, channel group), MOCA_EP_GSTAT) -- no finalize launch; the column-sum buffer goes back
+        to the pool and the map moves to `gstat_own`"""
+        if fm.gstat is not None and fm.gstat[1] == fps:
+            return fm.gstat[0]
+        rows = fps * fm.H * fm.W
+        if fps > 16:                                          # (groups of up to 16 frames, per-frame ones included: as before)
+            _check_gstat_range(rows)
+        slot = self._gstat_slot((fm.F // fps) * 64)
+        self._retarget(fm.src, colsum=None, gstat=(slot, rows))
+        self.pool.put(fm.colsum[0])
+        fm.colsum = None
+        fm.gstat_own = (slot, fps)
+        return slot
 
     def _gstat_slot(self, n_doubles):
         """64-bit fixed-point accumulators of one GEMM -> GroupNorm pair, carved from ONE buffer that a single memset zeroes at the start of
@@ -340,19 +344,25 @@ class _PlanBase:
         return s
 
     def _drop_colsum(self, fm):
-        """the statistics buffer of a feature map goes back to the pool once its GroupNorm consumer has been recorded"""
-        if getattr(fm, "slabs", None) is not None:             # a split-K producer whose consumer was no GroupNorm: its own reduce stays
+        """settle what fm's producer still promises once no consumer can take it up any more (the statistics half of _retire; alone only
+        where fm's rows are still read: in front of the launch that reuses the freed workspace, or when the rows are about to change)"""
+        if fm.slabs is not None:                               # a split-K producer whose consumer was no GroupNorm: its own reduce stays
             self.pool.put(fm.slabs[0])
             self._unhold(fm.slabs)
             fm.slabs = None
-        if fm.colsum is not None:
-            if not fm.cs_used and fm.src is not None:          # nobody read the column sums (the consumer was a conv / a concat /
-                prod = self.steps[fm.src]                      # a GroupNorm whose statistics groups the row tiles straddle):
-                kw = dict(prod.keywords)                       # the producer goes back to the plain store loop
-                kw["colsum"] = None
-                self.steps[fm.src] = functools.partial(prod.func, *prod.args, **kw)
-            self.pool.put(fm.colsum[0])
+        if fm.colsum is not None:                              # nobody read the column sums (the consumer was a conv / a concat / a
+            self._retarget(fm.src, colsum=None)                # GroupNorm whose statistics groups the row tiles straddle): the
+            self.pool.put(fm.colsum[0])                        # producer goes back to the plain store loop
             fm.colsum = None
+
+    def _retire(self, fm):
+        """`fm` is consumed -- every launch that reads it has been recorded: its buffer goes back to the pool (unless pinned, or held
+        for a deferred reduce) and whatever its producer still promised is settled.  A virtual concat retires both of its sources.
+        (Settle first: operands held for the reduce re-enter the pool in front of fm's own buffer.  The pool hands out the buffer put
+        back last, so the order decides which one the next launch gets; tests/golden/plan_full_launches.npz pins it.)"""
+        for m in ((fm.h, fm.skip) if isinstance(fm, _CatMap) else (fm,)):
+            self._drop_colsum(m)
+            self._release(m.buf)
 
     def ln(self, x, M, Cn, gb):
         y = self.pool.get(M, Cn)
@@ -368,6 +378,30 @@ class _PlanBase:
             ops.memset_zero(self._gstat_buf[:self._gstat_used])
         for s in self.steps:
             s()
+
+    @contextlib.contextmanager
+    def _enqueue(self, cur=None):
+        """`with plan._enqueue(cur):` -- the plan's stream is ordered after `cur` (default: the current stream) and entered: whatever the
+        body enqueues (input copies, then `_replay()`) runs on it; the caller joins (`cur.wait_stream(plan.stream)`) when it wants"""
+        self.stream.wait_stream(cur if cur is not None else torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            yield
+
+    @contextlib.contextmanager
+    def _ops_stream(self):
+        """the C-ABI launches of `ops` go to the plan's stream inside, to torch's current stream again afterwards"""
+        ops.set_stream(self.stream.cuda_stream)
+        try:
+            yield
+        finally:
+            ops.set_stream(None)
+
+    def _replay(self):
+        """one run of the recorded sequence on the plan's stream (inside `_enqueue`): the ONE caller of `_launch`, which decides
+        eager / capture / replay from the runs counted so far"""
+        with self._ops_stream():
+            self._launch(self.stream.cuda_stream)
+        self.n_runs += 1
 
     def _launch(self, handle):
         lib = _l.load()
@@ -472,8 +506,7 @@ class _Plan(_PlanBase):
         h1 = self.conv(_FMap(g1, x.F, x.H, x.W, x.C), P[id(mod.in_layers[2])], rowadd=emb_out, rowadd_div=HW)
         self._release(g1)
         g2 = self.gn(h1, P[id(mod.out_layers[0])], fps=1, eps=1e-5, silu=True, x_dead=True)
-        self._release(h1.buf)
-        self._drop_colsum(h1)
+        self._retire(h1)
         if isinstance(mod.skip_connection, torch.nn.Identity):
             sk = x.buf
         elif isinstance(x, _CatMap):                             # 1x1 conv over the virtual concat: two A sources, split at h's channels
@@ -495,13 +528,13 @@ class _Plan(_PlanBase):
         for i, (name, idx) in enumerate((("conv1", 2), ("conv2", 3), ("conv3", 3), ("conv4", 3))):
             sq = getattr(tc, name)
             g = self.gn(cur, P[id(sq[0])], fps=self.T, eps=1e-5, silu=True, x_dead=cur is not h2)
-            self._drop_colsum(cur)
+            self._drop_colsum(cur)      # (now: the tconv below reuses the freed workspace; h2's rows are read until conv4's residual)
             nxt = self.tconv(_FMap(g, cur.F, cur.H, cur.W, cur.C), P[id(sq[idx])], residual=h2.buf if i == 3 else None)
             self._release(g)
             if cur is not h2:
-                self._release(cur.buf)
+                self._retire(cur)
             cur = nxt
-        self._release(h2.buf)
+        self._retire(h2)
         return cur
 
     # ---- LayerNorm folded into the linear that consumes it ------------------------------------------------------------
@@ -725,35 +758,19 @@ class _Plan(_PlanBase):
         FINISHED statistics behind (the condition of gn()'s single-launch path: a GEMM whose row tiles lie inside one statistics group, or
         a concat that accumulated them) and (b) the linear runs on a staggered kernel whose row tiles lie inside one group
         (moca_gemm_wgroup_ok).  Returns (per-group PackedWeight, (rows per group, stride)) or None (the caller runs gn() + the linear)."""
-        if not GN_FOLD or isinstance(fm, _CatMap) or getattr(fm, "slabs", None) is not None or fm.C % 32 or pw.geglu:
+        if not GN_FOLD or isinstance(fm, _CatMap) or fm.slabs is not None or fm.C % 32 or pw.geglu:
             return None
-        HW, rows = fm.H * fm.W, fps * fm.H * fm.W
-        cs = fm.colsum
-        have = fm.gstat is not None and fm.gstat[1] == fps
-        can = cs is not None and rows % cs[1] == 0 and fm.src is not None and not isinstance(fm.src, tuple)
+        rows = fps * fm.H * fm.W
         # worth it only while the derived weights (written once, read by the group's row tiles) are small against the tensor the GroupNorm
         # pass would read and write: rows per group >= 4 N.  (640-channel level, per-frame statistics: 640 rows per group -- 256 frames x
         # 819 KB of weights at B = 16, as many bytes as the pass itself: measured no gain; that norm stays a launch)
-        if not (have or can) or fm.F % fps or rows < 4 * pw.N:
+        if not self._stats_ready(fm, fps) or fm.F % fps or rows < 4 * pw.N:
             return None
         stride = pw.N * pw.w.stride(0)
         if not ops.gemm_wgroup_ok(fm.buf, pw, M=fm.M, lda=fm.buf.stride(-2), splits=self._splits(fm.M, pw), wgroup=(rows, stride)):
             return None
         n_sg = fm.F // fps
-        if have:
-            slot = fm.gstat[0]
-        else:                                        # re-target the producer: finished statistics instead of per-tile column sums (as gn())
-            if fps > 16:
-                _check_gstat_range(rows)
-            prod = self.steps[fm.src]
-            slot = self._gstat_slot(n_sg * 64)
-            kw = dict(prod.keywords)
-            kw["colsum"] = None
-            kw["gstat"] = (slot, rows)
-            self.steps[fm.src] = functools.partial(prod.func, *prod.args, **kw)
-            self.pool.put(cs[0])
-            fm.colsum = None
-            fm.gstat_own = (slot, fps)
+        slot = self._finished_stats(fm, fps)
         wg = self.pool.get(n_sg * pw.N, pw.w.stride(0))
         bg = self.pool.get(1, n_sg * pw.N, torch.float32)
         self._emit(ops.groupnorm_fold_weights, pw, gb[0], gb[1], slot, wg, bg, n_sg=n_sg, count=rows * (fm.C // 32), eps=eps)
@@ -800,12 +817,12 @@ class _Plan(_PlanBase):
                                       causal=causal)
         if Fr != x.F:                                            # the shared prefix ended inside: the outer residual too
             xres = self._expand(x.buf, x.M, x.C)
-        out, cs = self.linear(h, M, P[id(mod.proj_out)], residual=xres, want_colsum=True)
+        # (a split-K proj_out, e.g. M = 640 at B = 1, defers its reduce like the convs: gn() or _retire() of the map settles it)
+        o = self._gemm_map(Fr, x.H, x.W, h, P[id(mod.proj_out)], lda=h.stride(-2), residual=xres)
+        assert o.C == x.C and o.M == M
         self._release(h)
         if xres is not x.buf:
             self._release(xres)
-        o = _FMap(out, Fr, x.H, x.W, x.C, cs, src=self._last_gemm_step if cs is not None else None)
-        o.slabs = self._last_slabs          # (split-K proj_out, e.g. M = 640 at B = 1: released by gn() / _drop_colsum())
         return o
 
     def run_seq(self, seq, h):
@@ -823,13 +840,7 @@ class _Plan(_PlanBase):
                 nh = self.upconv(h, layer.conv)
             else:
                 raise TypeError(type(layer))
-            if isinstance(h, _CatMap):
-                self._drop_colsum(h.h)          # (whatever _virtual_cat did not re-target: column sums nobody read, a deferred workspace)
-                self._drop_colsum(h.skip)
-                self._release(h.h.buf, h.skip.buf)
-            else:
-                self._release(h.buf)
-                self._drop_colsum(h)
+            self._retire(h)     # (of a virtual concat: whatever _virtual_cat did not re-target -- column sums nobody read, a deferred workspace)
             h = nh
         return h
 
@@ -885,8 +896,7 @@ class _Plan(_PlanBase):
             if i == 0:
                 if m.addition_attention:
                     nh = self.transformer(m.init_attn[0], h, False)
-                    self._release(h.buf)
-                    self._drop_colsum(h)
+                    self._retire(h)
                     h = nh
             else:
                 h = self.run_seq(module, h)
@@ -902,8 +912,7 @@ class _Plan(_PlanBase):
             if skip.F != h.F:                                    # a skip connection from the shared prefix
                 self._pinned.discard(skip.buf.data_ptr())
                 wide = self._expand(skip.buf, skip.M, skip.C)
-                self._drop_colsum(skip)
-                self._release(skip.buf)
+                self._retire(skip)
                 own, own_F = skip.gstat_own, skip.F
                 skip = _FMap(wide, h.F, skip.H, skip.W, skip.C)
                 skip.gstat_own, skip.own_F = own, own_F          # (the copies share the statistics of the frames they repeat)
@@ -924,17 +933,15 @@ class _Plan(_PlanBase):
             else:
                 self._emit(ops.concat_channels, h.buf, skip.buf, cat, rows=h.M, C1=h.C, C2=skip.C)   # torch.cat(dim=1), :571
             self._pinned.discard(skip.buf.data_ptr())
-            self._drop_colsum(h)          # (a concat consumed h: its producer goes back to the plain store loop)
-            self._drop_colsum(skip)
-            self._release(h.buf, skip.buf)
+            self._retire(h)               # (a concat consumed h: its producer goes back to the plain store loop)
+            self._retire(skip)
             h = self.run_seq(module, _FMap(cat, h.F, h.H, h.W, Cc, gstat=gst))
         g = self.gn(h, P[id(m.out[0])], fps=1, eps=1e-5, silu=True)
-        self._release(h.buf)
-        self._drop_colsum(h)
+        self._retire(h)
         o = self.conv(_FMap(g, h.F, h.H, h.W, h.C), P[id(m.out[2])])
         self._release(g)
         self._emit(ops.nhwc_to_ncthw, o.buf, o.C, self.out, B=B, Cout=m.out_channels, T=T, HW=H * W)
-        self._release(o.buf)
+        self._retire(o)
         self._finish_prefetch()
 
     def _adapter_add(self, h, FT):
@@ -944,7 +951,7 @@ class _Plan(_PlanBase):
         producer goes back to its plain store loop and its own reduce -- and every consumer of the sum (the next block's GroupNorm or
         transformer norm, the output block that reads it as skip) runs its own statistics pass."""
         self._drop_colsum(h)
-        assert h.gstat is None and h.gstat_own is None and not h.cs_used      # (set by consumers only: h has none yet)
+        assert h.gstat is None and h.gstat_own is None      # (set by consumers only: h has none yet)
         h.src, h.cs_rows = None, 0
         src = torch.empty(FT, h.C, h.H, h.W, dtype=torch.float32, device=self.device)
         self.adapter_in.append(src)
@@ -974,16 +981,13 @@ class _Plan(_PlanBase):
             rows = fm.colsum[1] if fm.colsum is not None else fm.cs_rows
             phases = isinstance(fm.src, tuple)                   # an `Upsample` as four 2 x 2 convs on the low-resolution grid
             grp = HW // 4 if phases else HW                     # GEMM rows per frame
-            if fm.src is None or rows <= 0 or grp % rows or fm.gstat_own is not None or fm.cs_used:
+            if fm.src is None or rows <= 0 or grp % rows or fm.gstat_own is not None:
                 return False
             for i in (fm.src if phases else (fm.src,)):
-                prod = self.steps[i]
-                kw = dict(prod.keywords)
+                kw = self.steps[i].keywords
                 if kw.get("gstat") is not None or kw.get("rowsum") is not None:
                     return False
-                kw["colsum"] = None
-                kw["gstat"] = (slot, grp, gw, coff)
-                self.steps[i] = functools.partial(prod.func, *prod.args, **kw)
+                self._retarget(i, colsum=None, gstat=(slot, grp, gw, coff))
             if fm.colsum is not None:
                 self.pool.put(fm.colsum[0])
                 fm.colsum = None
@@ -1053,25 +1057,18 @@ class _Plan(_PlanBase):
             raise ValueError("c_concat goes with a plan built for it (UNetModel.forward_concat)")
         if (features_adapter is None) != (self.adapter_in is None):
             raise ValueError("features_adapter goes with a plan built for it (UNetModel.forward(features_adapter=...))")
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
+        with self._enqueue(cur):
             self.x_in.copy_(x, non_blocking=True)
             self.t_rows.copy_(t_rows, non_blocking=True)
             self.fps_rows.copy_(fps_rows, non_blocking=True)
             self.set_context(context)
             if features_adapter is not None:
                 self.set_adapter(features_adapter)
-            handle = self.stream.cuda_stream
-            ops.set_stream(handle)
-            try:
-                if c_concat is not None:
+            if c_concat is not None:
+                with self._ops_stream():
                     self.set_concat(c_concat)
-                self._launch(handle)
-            finally:
-                ops.set_stream(None)
-            out = self.out.clone()
-        self.n_runs += 1
-        return out
+            self._replay()
+            return self.out.clone()
 
     def run(self, x, t_rows, fps_rows, context, c_concat=None, features_adapter=None):
         cur = torch.cuda.current_stream(self.device)

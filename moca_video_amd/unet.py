@@ -203,15 +203,30 @@ class _Pool:
 
 
 class _FMap:
-    """channels-last feature map: buf [F*H*W][C] fp16; `colsum` = (f32 [row tiles][C][2] buffer, rows per tile) when the
-    GEMM that produced it also left per-(row tile, channel) sums and sums of squares behind (GroupNorm statistics)"""
-    __slots__ = ("buf", "F", "H", "W", "C", "colsum", "src", "gstat", "cs_used", "cs_rows", "gstat_own", "own_F", "slabs")
+    """channels-last feature map: buf [F*H*W][C] fp16, plus what its producer PROMISED a GroupNorm consumer.  The states, and who moves a
+    map between them (all in plan.py; a consumer only ever calls gn() / _gn_fold() / _virtual_cat() and, when done, _retire()):
+
+      nothing promised      colsum, gstat, gstat_own, slabs all None: the consumer runs its own statistics pass.  Maps made by hand,
+                            and every map after _drop_colsum() / _adapter_add().
+      per-tile column sums  `colsum` = (f32 [row tiles][C][2], rows per tile) with `src` = index of the recorded GEMM that writes them
+                            (_gemm_map; an `Upsample` of four phase launches has src = their indices and `cs_rows` but no buffer yet).
+                            Nobody reads the sums as they are: _finished_stats() / _virtual_cat() re-target the producer to finished
+                            statistics, _drop_colsum() re-targets it back to the plain store loop; either way the buffer returns to
+                            the pool and colsum becomes None.
+      finished statistics   `gstat` = (accumulators, frames per group): the concat that wrote buf accumulated them (made with the map);
+                            `gstat_own` = the same, left by the re-targeted producer (_finished_stats), kept so that a later virtual
+                            concat can merge them; `own_F` > 0: inherited -- they cover own_F frames and buf is F / own_F copies of
+                            those (the repeat that ends the shared prefix).  Accumulators are slots of the plan's zeroed chunk: nothing
+                            to release.
+      deferred slabs        `slabs` = (split-K workspace, index of the producer, held operand addresses): the producer ran split-K and
+                            its reduce has not been placed (_gemm_map).  gn() moves it into the GroupNorm launch or lets the producer
+                            reduce; _drop_colsum() does the latter; both free the workspace and the operands held for the reduce."""
+    __slots__ = ("buf", "F", "H", "W", "C", "colsum", "src", "gstat", "cs_rows", "gstat_own", "own_F", "slabs")
 
     def __init__(self, buf, F, H, W, C, colsum=None, src=None, gstat=None):
         self.buf, self.F, self.H, self.W, self.C, self.colsum = buf, F, H, W, C, colsum
-        self.src = src          # index of the recorded GEMM launch that produced buf (with colsum): plan.gn() may re-target it
+        self.src = src          # index of the recorded GEMM launch that produced buf (with colsum): plan._retarget() rewrites it
         self.gstat = gstat      # (f64 accumulators, frames_per_stat) when the producer already accumulated finished statistics
-        self.cs_used = False    # a GroupNorm consumed the column sums (else the producer is re-recorded without them)
         self.cs_rows = colsum[1] if colsum is not None else 0   # rows per tile of the producer's statistics epilogue (kept when colsum is dropped)
         self.gstat_own = None   # (accumulators, frames_per_stat): the producer was re-targeted to FINISHED statistics of this map (32 groups of C / 32)
         self.own_F = 0          # > 0: gstat_own covers own_F frames and buf is F / own_F copies of them (the repeat that ends the shared prefix)

@@ -211,22 +211,19 @@ class _VaePlan(_PlanBase):
         self._emit(ops.nhwc_to_ncthw, o.buf, o.C, self.out, B=n, Cout=d.out_ch, T=1, HW=o.H * o.W)
         self._release(o.buf)
 
-    def run(self, z):
+    def _run_on(self, dst, src):
+        """copy the input into the plan's buffer, replay, hand back a copy of the output that the caller's stream may use"""
         cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.z_in.copy_(z, non_blocking=True)
-            handle = self.stream.cuda_stream
-            ops.set_stream(handle)
-            try:
-                self._launch(handle)
-            finally:
-                ops.set_stream(None)
+        with self._enqueue(cur):
+            dst.copy_(src, non_blocking=True)
+            self._replay()
             out = self.out.clone()
-        self.n_runs += 1
         out.record_stream(cur)
         cur.wait_stream(self.stream)
         return out
+
+    def run(self, z):
+        return self._run_on(self.z_in, z)
 
 
 class _EncPlan(_PlanBase):
@@ -243,6 +240,7 @@ class _EncPlan(_PlanBase):
 
     resnet = _VaePlan.resnet
     attn = _VaePlan.attn
+    _run_on = _VaePlan._run_on
 
     def _build(self):
         m, e, P = self.model, self.model.encoder, self.P
@@ -285,21 +283,7 @@ class _EncPlan(_PlanBase):
         return _FMap(out, x.F, x.H // 2, x.W // 2, pw.N)
 
     def run(self, x):
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            self.x_in.copy_(x, non_blocking=True)
-            handle = self.stream.cuda_stream
-            ops.set_stream(handle)
-            try:
-                self._launch(handle)
-            finally:
-                ops.set_stream(None)
-            out = self.out.clone()
-        self.n_runs += 1
-        out.record_stream(cur)
-        cur.wait_stream(self.stream)
-        return out
+        return self._run_on(self.x_in, x)
 
 
 class DiagonalGaussianDistribution:

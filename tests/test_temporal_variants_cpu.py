@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from helpers import FULL, REDUCED, golden
-from plan_cpu import cpu_plan, signature
+from plan_cpu import aliases, cpu_plan, fixture_plans, signature
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -195,18 +195,19 @@ def test_shared_prefix_ends_at_the_first_cross_attention_of_either_kind():
 
 def test_full_configuration_records_the_parent_commits_launch_list():
     """no behaviour change for existing models: the launch list of the FULL (t2v) configuration at the headline shape -- names, operand
-    shapes, every scalar argument -- equals the list recorded at the parent commit (tests/golden/plan_full_launches.npz: the plain
-    B = 1 forward and the shared-prefix CFG pair; tools/record_parent_fixtures.py --plans re-records it when a plan change is meant).
-    The heaviest test of the CPU set (~15 s: the full-width tree is packed ONCE on the host and serves both plans); the reduced model
-    would not do -- the kernel choices under test (fused temporal attention, GroupNorm folds, split-K) depend on the full widths."""
-    from moca_video_amd import UNetModel
-    from moca_video_amd.plan import _Plan
+    shapes, every scalar argument (plan_cpu.signature) -- AND the buffer every operand of a launch is bound to (plan_cpu.aliases:
+    which pool buffer a launch was handed, when it went back) equal the lists recorded at the parent commit
+    (tests/golden/plan_full_launches.npz; tools/record_parent_fixtures.py --plans re-records it when a plan change is meant), for
+    every plan of plan_cpu.fixture_plans: seven signatures of the FULL configuration and the hybrid `pieces` plan of the reduced one.
+    The heaviest test of the CPU set (~15 s: the full-width tree is packed ONCE on the host and serves its seven plans); the reduced
+    model would not do -- the kernel choices under test (fused temporal attention, GroupNorm folds, split-K) depend on the full widths."""
     g = golden("plan_full_launches")
-    m = UNetModel(**FULL)
-    m._pack(torch.device("cpu"))
-    for tag, args, kw in (("b1_77", (1, 16, 40, 64, 77), {}), ("cfg_shared", (2, 16, 40, 64, ((1, 77), (1, 77))), dict(shared_x=True))):
-        sig = signature(_Plan(m, *args, torch.float32, torch.device("cpu"), **kw))
-        want = [str(s) for s in g[tag]]
-        assert len(sig) == len(want), tag
-        diff = [(i, a, b) for i, (a, b) in enumerate(zip(sig, want)) if a != b]
-        assert not diff, f"{tag}: {len(diff)} launches differ from the parent commit's, first: {diff[0]}"
+    tags = []
+    for tag, plan in fixture_plans(FULL, REDUCED):
+        tags.append(tag)
+        for key, got in ((tag, signature(plan)), (tag + ".aliases", aliases(plan))):
+            want = [str(s) for s in g[key]]
+            assert len(got) == len(want), key
+            diff = [(i, a, b) for i, (a, b) in enumerate(zip(got, want)) if a != b]
+            assert not diff, f"{key}: {len(diff)} launches differ from the parent commit's, first: {diff[0]}"
+    assert sorted(g.files) == sorted(tags + [t + ".aliases" for t in tags]) and len(tags) == 8

@@ -3,9 +3,10 @@
 with its own built libmoca_hip.so), so that they can be audited and re-recorded when a plan optimisation or a compiler bump
 legitimately changes them:
 
-  tests/golden/plan_full_launches.npz            (--plans, no GPU)  the launch list of the FULL configuration at [.,4,16,40,64]: the plain
-                                                 B = 1 forward and the shared-prefix CFG pair, one line per launch
-                                                 (tests/plan_cpu.py::signature)
+  tests/golden/plan_full_launches.npz            (--plans, no GPU)  the launch lists of tests/plan_cpu.py::fixture_plans (seven plans of
+                                                 the FULL configuration, the hybrid `pieces` plan of the reduced one), one line per
+                                                 launch: `<tag>` = what is launched (plan_cpu.signature), `<tag>.aliases` = which
+                                                 buffer every operand is (plan_cpu.aliases)
   tests/golden/temporal_attention_parent_sha.npz (--sha, on the GPU)  sha256 of the outputs of moca_temporal_attention_f16 and of the
                                                  non-causal MOCA_EP_TATTN launch on the host-generated operands of
                                                  tests/temporal_variants_ref.py
@@ -19,6 +20,7 @@ checkout's.  A tree older than the host-recordable plan (no `UNetModel._pack(dev
 through two stand-ins defined here; nothing of it is modified."""
 import argparse
 import os
+import re
 import sys
 
 import numpy as np
@@ -50,16 +52,13 @@ def record_plans():
             P[id(self.out[2])] = ops.pack_conv3x3(self.out[2].weight.detach(), self.out[2].bias.detach(), device=dev)
             self._packed = P
         UNetModel._pack = _pack
-    from helpers import FULL
-    from moca_video_amd.plan import _Plan
+    from helpers import FULL, REDUCED
     import plan_cpu
-    m = UNetModel(**FULL)
-    m._pack(torch.device("cpu"))
     out = {}
-    for tag, args, kw in (("b1_77", (1, 16, 40, 64, 77), {}), ("cfg_shared", (2, 16, 40, 64, ((1, 77), (1, 77))), dict(shared_x=True))):
-        sig = plan_cpu.signature(_Plan(m, *args, torch.float32, torch.device("cpu"), **kw))
-        print(f"{tag}: {len(sig)} launches")
-        out[tag] = np.asarray(sig)
+    for tag, plan in plan_cpu.fixture_plans(FULL, REDUCED):
+        sig, ali = plan_cpu.signature(plan), plan_cpu.aliases(plan)
+        print(f"{tag}: {len(sig)} launches, {1 + max(int(n) for l in ali for n in re.findall(r'#([0-9]+)', l))} buffers")
+        out[tag], out[tag + ".aliases"] = np.asarray(sig), np.asarray(ali)
     np.savez_compressed(os.path.join(GOLD, "plan_full_launches.npz"), **out)
 
 
