@@ -22,6 +22,8 @@ import torch
 
 from . import lib as _l
 from . import ops
+from .conditioning import _f32c, as_cond_dict, check_schedule_index, conditioning_key, guidance_eps
+from .fifo_graph import DdpmEngine, EngineCache, mask_kind, mask_operand  # noqa: F401  (mask_kind, mask_operand: re-exported)
 
 TABLE_NAMES = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "log_one_minus_alphas_cumprod", "posterior_variance",
                "posterior_log_variance_clipped", "posterior_mean_coef1", "posterior_mean_coef2")
@@ -65,28 +67,6 @@ def ddpm_coef(tables, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, scale_
     return coef
 
 
-def _f32c(t):
-    return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
-
-
-def mask_kind(mask, shape):
-    """how the kernel reads `mask` against latents of `shape`: "c0" (one channel, channel stride 0) or "full" (`img_orig * mask`,
-    :648, broadcasts: everything else is expanded to the latents' shape)"""
-    ms = (1,) * (len(shape) - mask.dim()) + tuple(mask.shape)
-    return "c0" if ms[1] == 1 and shape[1] > 1 else "full"
-
-
-def mask_operand(mask, shape, device):
-    """-> (contiguous fp32 mask as the kernel reads it, kernel flag, elements per mask channel)"""
-    B, Cc = int(shape[0]), int(shape[1])
-    inner = int(np.prod(shape[2:]))
-    m = mask.to(device, torch.float32)
-    m = m.reshape((1,) * (len(shape) - m.dim()) + tuple(m.shape))
-    if mask_kind(mask, shape) == "c0":
-        return m.expand(B, 1, *shape[2:]).contiguous(), _l.MOCA_DDPM_MASK_C0, inner
-    return m.expand(*shape).contiguous(), 0, inner * Cc
-
-
 def launch_ddpm_step(coef, t, *, B, per, x=None, out=None, eps_c=None, eps_u=None, noise=None, x_recon=None, mean=None, mask=None,
                      x0=None, noise_q=None, mask_inner=0, cfg_scale=1.0, temperature=1.0, flags=0, state=None, t_stride=1, stream=None):
     """`moca_ddpm_step_f32` on tensors (None = NULL); raises on a refused call"""
@@ -106,16 +86,6 @@ def engine_key(shape, cond, uc, timesteps, scale, mask, clip_denoised, parameter
             str(parameterization), str(device))
 
 
-def _as_cond_dict(model, cond):
-    """apply_model's normalisation of `cond` (:513-520)"""
-    if isinstance(cond, dict):
-        return cond
-    if not isinstance(cond, list):
-        cond = [cond]
-    key = 'c_concat' if model.model.conditioning_key == 'concat' else 'c_crossattn'
-    return {key: cond}
-
-
 def _table_property(name):
     def get(self):
         return self._ddpm_dev(self.betas.device)[name]
@@ -130,7 +100,13 @@ class DdpmMixin:
 
     _ddpm_host_tables = None
     _ddpm_dev_tables = None
-    _ddpm_engine = None
+
+    @property
+    def _ddpm_engines(self):
+        """the cached step graph of `p_sample_loop` (made on first use: the mixin has no constructor)"""
+        return self.__dict__.setdefault("_ddpm_engine_cache", EngineCache())
+
+    _ddpm_engine = property(lambda self: self._ddpm_engines.entry, doc="None, or the (key, engine) of the cached step graph")
 
     def _ddpm_host(self):
         tabs = self._ddpm_host_tables
@@ -164,13 +140,7 @@ class DdpmMixin:
         `extract_into_tensor`'s gather); a device tensor is gathered by the kernel (a t out of range gives that sample NaN)."""
         if not x.is_cuda:
             raise ValueError("the DDPM sampler runs on the GPU: the latents must be cuda tensors")
-        t = torch.as_tensor(t)
-        B = x.shape[0]
-        if t.dim() != 1 or t.shape[0] != B:
-            raise ValueError(f"t must hold one timestep per sample, shape [{B}], got {tuple(t.shape)}")
-        if not t.is_cuda and (int(t.min()) < 0 or int(t.max()) >= self.num_timesteps):
-            raise IndexError(f"timestep {t.tolist()} is out of bounds for the {self.num_timesteps}-entry schedule tables")
-        return t.to(x.device, torch.int64).contiguous()
+        return check_schedule_index(t, x.shape[0], self.num_timesteps, "timestep").to(x.device, torch.int64).contiguous()
 
     def _extract(self, name, t, x):
         return self._ddpm_dev(x.device)[name][t].reshape(x.shape[0], *((1,) * (x.dim() - 1)))    # extract_into_tensor, utils_diffusion.py
@@ -221,21 +191,13 @@ class DdpmMixin:
         x = _f32c(x)
         t = self._ddpm_t(t, x)
         B = x.shape[0]
-        eps_u = None
         scale = 1.0 if unconditional_guidance_scale is None else float(unconditional_guidance_scale)
         uc = unconditional_conditioning if scale != 1. else None
-        from .fifo_graph import DdpmEngine
-        if uc is not None and not kwargs and DdpmEngine.supported(self, x, c, uc):
-            # both branches in ONE forward that shares everything before the first cross-attention (same x, same t), as
-            # DDIMSampler._cfg_eps and the engine run them
-            cd, ud = _as_cond_dict(self, c), _as_cond_dict(self, uc)
-            e = self.model.diffusion_model.forward_segments(x, t, [torch.cat(d["c_crossattn"], 1) for d in (cd, ud)],
-                                                            fps=[d.get("fps", 16) for d in (cd, ud)], shared_x=True)
-            eps_c, eps_u = _f32c(e[:B]), _f32c(e[B:])
-        else:
-            eps_c = _f32c(self.apply_model(x, t, c, **kwargs))                               # :567
-            if uc is not None:
-                eps_u = _f32c(self.apply_model(x, t, uc, **kwargs))
+        # the guidance branches share the UNet prefix exactly where the one-graph step does (and only without further UNet kwargs);
+        # otherwise one apply_model per branch (:567).  The kernel combines them
+        e = guidance_eps(self, x, t, c, uc, scale, share_prefix=uc is not None and not kwargs and DdpmEngine.supported(self, x, c, uc),
+                         share_any=True, batch=False, **kwargs)
+        eps_c, eps_u = (_f32c(e), None) if torch.is_tensor(e) else (_f32c(e[0]), _f32c(e[1]))
         out = recon = mean = None
         if want_out:
             out = torch.empty_like(x)
@@ -282,25 +244,13 @@ class DdpmMixin:
 
     # ---- the loop --------------------------------------------------------------------------------------------------------------
     def _ddpm_engine_for(self, img, cond, uc, scale, timesteps, mask, x0, seed):
-        from .fifo_graph import DdpmEngine
         key = engine_key(img.shape, cond, uc, timesteps, scale, mask, self.clip_denoised, self.parameterization, img.device)
-        cached = self._ddpm_engine
-        if cached is not None and cached[0] != key:
-            cached[1].close()
-            cached = self._ddpm_engine = None
-        if cached is None:
-            eng = DdpmEngine(self, img, cond, uc, scale, timesteps, mask=mask, x0=x0, seed=seed)
-            self._ddpm_engine = (key, eng)
-        else:
-            eng = cached[1]
-            eng.reset(img, cond, uc, seed, mask=mask, x0=x0)
-        return eng
+        return self._ddpm_engines.get(key, lambda: DdpmEngine(self, img, cond, uc, scale, timesteps, mask=mask, x0=x0, seed=seed),
+                                      lambda eng: eng.reset(img, cond, uc, seed, mask=mask, x0=x0))
 
     def release(self):
         """free the cached step graph of `p_sample_loop` (plan buffers + hipGraph)"""
-        if self._ddpm_engine is not None:
-            self._ddpm_engine[1].close()
-            self._ddpm_engine = None
+        self._ddpm_engines.release()
 
     @torch.no_grad()
     def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None, mask=None,
@@ -329,10 +279,10 @@ class DdpmMixin:
             raise NotImplementedError("noise_dropout is outside the DDPM sampler's scope")
         scale = 1.0 if unconditional_guidance_scale is None else float(unconditional_guidance_scale)
         uc = unconditional_conditioning if scale != 1. else None
-        from .fifo_graph import DdpmEngine
         if use_graph is not False and timesteps > 0 and not kwargs and DdpmEngine.supported(self, img, cond, uc):
-            cd = _as_cond_dict(self, cond)
-            ud = None if uc is None else _as_cond_dict(self, uc)
+            key = conditioning_key(self)
+            cd = as_cond_dict(cond, key)
+            ud = None if uc is None else as_cond_dict(uc, key)
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())                  # the host generator seeds the device stream
             eng = self._ddpm_engine_for(img, cd, ud, scale, timesteps, mask, x0, seed)
             for k, i in enumerate(reversed(range(0, timesteps))):

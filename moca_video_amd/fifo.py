@@ -5,16 +5,13 @@
 Noise is an optional explicit argument wherever the reference calls torch.randn*."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import lib as _l
-from . import ops
-from .fifo_graph import FifoEngine, fifo_windows
+from .conditioning import refuse_concat, refuse_image_attention, refuse_long_window
+from .fifo_graph import FifoEngine, fifo_windows, lookahead_schedule
 from .freeinit import freq_mix_3d, get_freq_filter
-from .sampler import DDIMSampler, sqrt_f32
+from .sampler import DDIMSampler, noise_queue
 
 
 def prepare_latents(args, input_path, sampler, model=None, data=None, initial_latents=None, noises=None):
@@ -30,25 +27,12 @@ def prepare_latents(args, input_path, sampler, model=None, data=None, initial_la
     elif initial_latents is None:
         initial_latents = torch.load(input_path + f"/{args.num_inference_steps}.pt")
     z = initial_latents.to("cuda", torch.float32).contiguous()
-    b, c, tz, h, w = z.shape
+    tz = z.shape[2]
     n_look = args.video_length // 2 if args.lookahead_denoising else 0
     N = args.num_inference_steps
-    Q = n_look + N
-    # per queue frame: which base frame it starts from and its noise level (:55-77) -- O(Q) host scalars, evaluated like the
-    # reference's 0-dim fp32 tensors (alpha ** 0.5, (1 - alpha) ** 0.5); the arithmetic over the latents is one kernel
+    # per queue frame: which base frame it starts from and its noise level (:55-77); the arithmetic over the latents is one kernel
     alphas = torch.as_tensor(np.asarray(sampler.ddim_alphas), dtype=torch.float32)
-    j_alpha = torch.cat([alphas[:1].expand(n_look), alphas[:N]])
-    coef_z, coef_n = sqrt_f32(j_alpha), sqrt_f32(1 - j_alpha)        # (correctly rounded: torch's host sqrt differs between CPU vendors)
-    fidx = torch.tensor([0] * n_look + [max(0, i - (N - tz)) for i in range(N)], dtype=torch.int32)
-    if noises is None:
-        noise = torch.randn(b, c, Q, h, w, device=z.device)          # the Q torch.randn_like draws of :62,72, one tensor
-    else:
-        noise = torch.cat([n.to(z.device, torch.float32).reshape(b, c, 1, h, w) for n in noises[:Q]], dim=2).contiguous()
-    out = torch.empty(b, c, Q, h, w, dtype=torch.float32, device=z.device)
-    cz, cn, fi = coef_z.to(z.device), coef_n.to(z.device), fidx.to(z.device)      # (named: a temporary's block would be reused by the next)
-    _l.check(_l.load().moca_fifo_prepare_queue_f32(_l.ptr(z), _l.ptr(noise), _l.ptr(out), _l.ptr(cz), _l.ptr(cn), _l.ptr(fi), b * c, tz, Q, h * w,
-                                                   C.c_void_p(ops.current_stream())), "moca_fifo_prepare_queue_f32")
-    return out
+    return noise_queue(z, torch.cat([alphas[:1].expand(n_look), alphas[:N]]), [0] * n_look + [max(0, i - (N - tz)) for i in range(N)], noises)
 
 
 def shift_latents(latents, davis_data=None, model=None, noise=None, anchor_noise=None):
@@ -78,34 +62,6 @@ def shift_latents(latents, davis_data=None, model=None, noise=None, anchor_noise
     return latents, (frames, masks)
 
 
-def refuse_image_attention(model):
-    """The MoCA loop's two-prompt context is 154 tokens; an image-attention UNet would split it 77 / 77 into "text" and "image"
-    tokens by the reference's rule (attention.py:82-84).  That mode is not supported: raise instead of computing it."""
-    unet = getattr(getattr(model, "model", None), "diffusion_model", None)
-    if getattr(unet, "use_image_attention", False):
-        raise NotImplementedError("FIFO / MoCA sampling with an image-attention UNet (use_image_attention=True) is not supported: "
-                                  "its 154-token two-prompt context would be read as 77 text + 77 image tokens")
-
-
-def refuse_long_window(args):
-    """FIFO / MoCA windows are at most 16 frames: the one-graph loop (ring queue, per-window timestep tables, batched windows) is
-    built and measured for the 16-frame tile of the temporal attention; the UNet alone takes up to 32 frames (UNetModel.forward)"""
-    if args.video_length > 16:
-        raise ValueError(f"video_length = {args.video_length}: FIFO sampling takes windows of video_length <= 16 frames "
-                         f"(base_ddim_sampling / v2v_ddim_sampling take up to 32)")
-
-
-def refuse_concat(model, cond=None):
-    """FIFO / MoCA sampling has no channel-concatenated conditioning: the reference's loop hands every window the whole `cond`
-    and never slices `c_concat` along the queue, so there is no behaviour to reproduce.  Raise instead of computing something."""
-    from .wrapper import HYBRID_KEYS
-    key = getattr(getattr(model, "model", None), "conditioning_key", None)
-    if key in HYBRID_KEYS or (isinstance(cond, dict) and cond.get("c_concat") is not None):
-        raise NotImplementedError(f"FIFO / MoCA sampling with channel-concatenated conditioning (conditioning_key={key!r}, c_concat) is "
-                                  "not supported: the queue's windows would each need their own slice of c_concat; use "
-                                  "base_ddim_sampling")
-
-
 def uncond_embedding(model, c_emb, uc_emb):
     """The unconditional context of funcs.py:199-208 / :268-270: `model.uncond_type == "empty_seq"` (the YAML's value) is
     the text encoding of the EMPTY PROMPT -- it needs the text encoder, so the caller must pass it (`uc_emb`, e.g.
@@ -127,18 +83,21 @@ def uncond_embedding(model, c_emb, uc_emb):
 def base_uncond(model, cond, batch, cfg_scale, uc_emb=None):
     """the unconditional branch of funcs.py:197-216 (None without guidance): `model.uncond_type`'s context -- for an image-conditioned
     model followed by the image tokens of a zero image (:207-210) -- in a copy of `cond` that replaces `c_crossattn` only (:211-214)"""
+    return uncond_like(model, cond, cfg_scale, uc_emb, image_tokens_for=batch)
+
+
+def uncond_like(model, cond, cfg_scale, uc_emb=None, image_tokens_for=None):
+    """None without guidance, else `cond` with `model.uncond_type`'s context (funcs.py:199-206, :268-270) in place of `c_crossattn`
+    (a copy of the dict that replaces that key only, :211-214; the bare context for a bare `cond`).  `image_tokens_for` = batch: an
+    image-conditioned model appends the image tokens of a zero image (:207-210), which `base_ddim_sampling` does and the FIFO loop
+    does not."""
     if cfg_scale == 1.0:
         return None
-    c_emb = cond["c_crossattn"][0] if isinstance(cond, dict) else cond
-    uc_emb = uncond_embedding(model, c_emb, uc_emb)       # model.uncond_type (:199-206)
-    if hasattr(model, "embedder"):                        # image-conditioned model (:207-210): + the embedding of a zero image
-        uc_img = model.get_image_embeds(torch.zeros(batch, 3, 224, 224, device=model.device))
+    uc_emb = uncond_embedding(model, cond["c_crossattn"][0] if isinstance(cond, dict) else cond, uc_emb)
+    if image_tokens_for is not None and hasattr(model, "embedder"):
+        uc_img = model.get_image_embeds(torch.zeros(image_tokens_for, 3, 224, 224, device=model.device))
         uc_emb = torch.cat([uc_emb, uc_img], dim=1)
-    if isinstance(cond, dict):
-        uc = {key: cond[key] for key in cond.keys()}
-        uc.update({'c_crossattn': [uc_emb]})
-        return uc
-    return uc_emb
+    return dict(cond, c_crossattn=[uc_emb]) if isinstance(cond, dict) else uc_emb
 
 
 def base_ddim_sampling(model, cond, noise_shape, ddim_steps=50, ddim_eta=1.0, cfg_scale=1.0, uc_emb=None,
@@ -220,22 +179,14 @@ def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg
     refuse_image_attention(model)
     refuse_concat(model, conditioning)
     cond = conditioning
-    uc = None
-    if cfg_scale != 1.0:
-        uc_emb = uncond_embedding(model, cond["c_crossattn"][0], uc_emb)       # :268-270
-        uc = {key: cond[key] for key in cond.keys()}
-        uc.update({'c_crossattn': [uc_emb]})
+    uc = uncond_like(model, cond, cfg_scale, uc_emb)       # :268-270
     if davis_data is not None:
         davis_data = (davis_data[0].to(model.device), davis_data[1].to(model.device))     # :296-300
         masks = davis_data[1]
     if latents is None:
         latents = prepare_latents(args, latents_dir, ddim_sampler, model=model, data=davis_data)
     f = args.video_length
-    timesteps = ddim_sampler.ddim_timesteps
-    indices = np.arange(args.num_inference_steps)
-    if args.lookahead_denoising:
-        timesteps = np.concatenate([np.full((f // 2,), timesteps[0]), timesteps])
-        indices = np.concatenate([np.full((f // 2,), 0), indices])
+    timesteps, indices = lookahead_schedule(ddim_sampler, args)
     total = args.new_video_length + args.num_inference_steps - f if n_iterations is None else n_iterations
     frames, pending = [], []
 

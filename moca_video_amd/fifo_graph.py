@@ -27,9 +27,11 @@ import torch
 
 from . import lib as _l
 from . import ops
+from .conditioning import (check_schedule_index, cond_image_rows, conditioning_key, as_cond_dict, context, fps_rows, one_fps,
+                           refuse_concat, refuse_image_attention, refuse_long_window, same_fps, unet_of)
 from .freeinit import get_freq_filter
 from .plan import _Plan
-from .unet import UNetModel, same_fps
+from .unet import UNetModel
 
 
 def fifo_windows(args):
@@ -42,6 +44,66 @@ def fifo_windows(args):
         yield start, start + f // 2, start + f
 
 
+def lookahead_schedule(sampler, args):
+    """(timesteps, indices) per queue frame (funcs.py:290-294): the schedule's, behind video_length // 2 copies of its first entry
+    when the loop denoises with lookahead"""
+    timesteps, indices = np.asarray(sampler.ddim_timesteps), np.arange(args.num_inference_steps)
+    if args.lookahead_denoising:
+        n_look = args.video_length // 2
+        timesteps = np.concatenate([np.full((n_look,), timesteps[0]), timesteps])
+        indices = np.concatenate([np.full((n_look,), 0), indices])
+    return timesteps, indices
+
+
+def ddim_coef(sampler, index):
+    """the five coefficients of schedule index `index` that every DDIM step kernel reads -- sqrt(a_t), sqrt(a_prev), sigma_t,
+    sqrt(1 - a_t), sqrt(1 - a_prev - sigma_t^2) -- evaluated in fp32 exactly as the reference's 0-dim tensors are
+    (ddim.py:331-343,409-418)"""
+    f32 = np.float32
+    a_t, a_prev, sig = f32(sampler.ddim_alphas[index]), f32(sampler.ddim_alphas_prev[index]), f32(sampler.ddim_sigmas[index])
+    return np.sqrt(a_t), np.sqrt(a_prev), sig, f32(sampler.ddim_sqrt_one_minus_alphas[index]), np.sqrt(f32(1.) - a_prev - sig * sig)
+
+
+def mask_kind(mask, shape):
+    """how the DDPM step kernel reads `mask` against latents of `shape`: "c0" (one channel, channel stride 0) or "full"
+    (`img_orig * mask`, ddpm3d.py:648, broadcasts: everything else is expanded to the latents' shape)"""
+    ms = (1,) * (len(shape) - mask.dim()) + tuple(mask.shape)
+    return "c0" if ms[1] == 1 and shape[1] > 1 else "full"
+
+
+def mask_operand(mask, shape, device):
+    """-> (contiguous fp32 mask as the kernel reads it, kernel flag, elements per mask channel)"""
+    B, Cc = int(shape[0]), int(shape[1])
+    inner = int(np.prod(shape[2:]))
+    m = mask.to(device, torch.float32)
+    m = m.reshape((1,) * (len(shape) - m.dim()) + tuple(m.shape))
+    if mask_kind(mask, shape) == "c0":
+        return m.expand(B, 1, *shape[2:]).contiguous(), _l.MOCA_DDPM_MASK_C0, inner
+    return m.expand(*shape).contiguous(), 0, inner * Cc
+
+
+class EngineCache:
+    """one cached step engine and what it was built for: `entry` is None or (key, engine)"""
+    entry = None
+
+    def get(self, key, build, reset):
+        """the engine for `key` at the start of a new trajectory: the cached one after `reset(engine)`, or -- the cached one closed if
+        its key is another -- `build()`"""
+        if self.entry is not None and self.entry[0] != key:
+            self.release()
+        if self.entry is None:
+            self.entry = (key, build())
+        else:
+            reset(self.entry[1])
+        return self.entry[1]
+
+    def release(self):
+        """close the cached engine (plan buffers + hipGraph)"""
+        if self.entry is not None:
+            self.entry[1].close()
+            self.entry = None
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -50,14 +112,6 @@ def state_block(seed, it=0):
     """a `moca_fifo_state` (head 0, iteration `it`, the 64-bit seed, ext_noise 0) as the host int32 tensor the device block is written from"""
     st = _l.FifoState(0, it, seed & 0xffffffff, (seed >> 32) & 0xffffffff, 0)
     return torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32)
-
-
-def fps_rows(fp, B, T, dev):
-    """the fps of B videos of T frames as the [B*T] int64 rows of the plan: an int, one value for all videos, or one per video"""
-    if isinstance(fp, int):
-        return torch.full((B * T,), fp, dtype=torch.int64, device=dev)
-    fp = torch.as_tensor(fp, device=dev).reshape(-1).to(torch.int64)
-    return (fp if fp.shape[0] == B else fp[:1].expand(B)).repeat_interleave(T)
 
 
 class _StepEngine:
@@ -113,8 +167,7 @@ class FifoEngine(_StepEngine):
 
     @staticmethod
     def supported(model, cond, latents, davis_data=None, sam_masks_fn=None):
-        unet = getattr(getattr(model, "model", None), "diffusion_model", None)
-        return (isinstance(unet, UNetModel) and isinstance(cond, dict) and "c_crossattn" in cond
+        return (isinstance(unet_of(model), UNetModel) and isinstance(cond, dict) and "c_crossattn" in cond
                 and (davis_data is None or getattr(model, "first_stage_model", None) is not None)
                 and sam_masks_fn is None and latents is not None and latents.is_cuda and latents.shape[0] == 1)
 
@@ -123,7 +176,6 @@ class FifoEngine(_StepEngine):
         """sam_capacity > 0 (and no `masks`): prompt mode with precomputed Grounded-SAM-2 candidates -- `ddim_step`'s segmentation
         branch (ddim.py:592-606 -> `_apply_segmentation` :739-903) runs inside the iteration graph on at most `sam_capacity`
         candidate masks per iteration, handed to `step(sam_masks=...)`."""
-        from .fifo import refuse_concat, refuse_image_attention, refuse_long_window
         refuse_long_window(args)
         refuse_image_attention(model)
         refuse_concat(model, cond)
@@ -144,11 +196,7 @@ class FifoEngine(_StepEngine):
         guided = uc is not None and cfg_scale != 1.0
         self.reps = 2 if guided else 1
         # ---- timesteps / coefficient tables per window slot (funcs.py:290-294,311-312; ddim.py:405-430,565-582)
-        timesteps = np.asarray(sampler.ddim_timesteps)
-        indices = np.arange(args.num_inference_steps)
-        if self.lookahead:
-            timesteps = np.concatenate([np.full((f // 2,), timesteps[0]), timesteps])
-            indices = np.concatenate([np.full((f // 2,), 0), indices])
+        timesteps, indices = lookahead_schedule(sampler, args)
         coef = np.zeros((nW, f, 6), np.float32)
         enh = np.ones((nW, f), np.float32)
         mframe = np.full((nW, f), -1, np.int32)
@@ -162,10 +210,7 @@ class FifoEngine(_StepEngine):
         self.coef, self.enh, self.mframe = to_dev(coef), to_dev(enh), to_dev(mframe)
         self.win_start = to_dev(np.asarray([s0 for s0, _, _ in wins], np.int32))
         # ---- the batched UNet plan: [conditional windows | unconditional windows], one context segment each
-        cc = torch.cat(cond["c_crossattn"], 1)
-        ctxs = [cc.expand(nW, -1, -1)]
-        if guided:
-            ctxs.append(torch.cat(uc["c_crossattn"], 1).expand(nW, -1, -1))
+        ctxs = [context(c).expand(nW, -1, -1) for c in [cond] + ([uc] if guided else [])]
         segs = tuple((nW, int(c.shape[1])) for c in ctxs)
         B = self.reps * nW
         # guided: the unconditional windows are the SAME latents with another context: one plan whose prefix (everything before the
@@ -177,8 +222,7 @@ class FifoEngine(_StepEngine):
         self.plan = plan = _Plan(unet, B, f, H, W, segs, torch.float32, dev, shared_x=shared)
 
         # (one fps per branch: of a tensor the first value serves all windows)
-        one = lambda fp: fp if isinstance(fp, int) else torch.as_tensor(fp).reshape(-1)[:1]
-        fr = [fps_rows(one(fp), nW, f, dev) for fp in [fps_c] + ([uc.get("fps", fps_c)] if guided else [])]
+        fr = [fps_rows(one_fps(fp), nW, f, dev) for fp in [fps_c] + ([uc.get("fps", fps_c)] if guided else [])]
         with torch.cuda.stream(plan.stream):
             plan.t_rows.copy_(to_dev(t_rows).reshape(-1).repeat(self.reps))
             plan.fps_rows.copy_(torch.cat(fr))
@@ -217,7 +261,7 @@ class FifoEngine(_StepEngine):
             self._sam_stage = [(torch.empty(self.sam_capacity, HW, dtype=torch.float32).pin_memory(),
                                 torch.zeros(2, nW * f, dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(2)]
             self._sam_turn = 0
-            self.cond = self._cond_image(conditioned_image, Cc, HW, dev)
+            self.cond = cond_image_rows(conditioned_image, Cc, HW, dev)[0].contiguous()
         if masks is not None:
             if masks.shape[2] != Q:
                 raise ValueError("the device-resident loop wants one mask frame per queue frame")
@@ -225,7 +269,7 @@ class FifoEngine(_StepEngine):
             self.mask_sums = torch.empty(Q, **f32)
             _l.check(lib.moca_mask_frame_sums_f32(_l.ptr(self.mask), _l.ptr(self.mask_sums), Q, HW,
                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "moca_mask_frame_sums_f32")
-            self.cond = self._cond_image(conditioned_image, Cc, HW, dev)
+            self.cond = cond_image_rows(conditioned_image, Cc, HW, dev)[0].contiguous()
         torch.cuda.current_stream(dev).synchronize()
         # ---- the launch sequence of one iteration = [noise, gather] + UNet + [guidance + step + write-back, FreeInit mix, advance]
         p = _l.FifoStepParams()
@@ -276,17 +320,6 @@ class FifoEngine(_StepEngine):
         self._wrap_plan(pre, post)
         self.n_iter = 0
         sampler.momentum = self.momentum[nW - 1].view(1, Cc, f, H, W)      # what the reference's last call (rank 0) leaves behind
-
-    @staticmethod
-    def _cond_image(conditioned_image, Cc, HW, dev):
-        if conditioned_image is None:
-            return torch.zeros(Cc, HW, dtype=torch.float32, device=dev)                      # ddim.py:573-574
-        ci = conditioned_image.to(dev)
-        if ci.shape[1] != Cc:
-            if ci.shape[1] != 3:
-                raise ValueError(f"Conditional image must have 3 or 4 channels, got {ci.shape[1]}")
-            ci = torch.cat([ci, torch.ones_like(ci[:, :1])], dim=1)                          # :575-578
-        return ci.to(torch.float32).reshape(-1, Cc, HW)[0].contiguous()
 
     def _upload_sam(self, sam_masks):
         """pack the candidates of this iteration -- `sam_masks[w][i]` = [n,H,W] masks Grounded-SAM-2 returns for frame i of window w
@@ -395,13 +428,12 @@ class BaseEngine(_StepEngine):
 
     @staticmethod
     def supported(model, x, cond, uc, scale, features_adapter=None):
-        unet = getattr(getattr(model, "model", None), "diffusion_model", None)
-        if features_adapter is not None and getattr(getattr(model, "model", None), "conditioning_key", None) != "crossattn":
+        unet, key = unet_of(model), conditioning_key(model)
+        if features_adapter is not None and key != "crossattn":
             return False                                     # (the host-issued path's wrapper names the refusal)
         ok = isinstance(unet, UNetModel) and x.is_cuda and isinstance(cond, dict) and isinstance(uc, dict) and scale != 1.0
         if not ok or set(cond.keys()) != set(uc.keys()) or 2 * x.shape[0] > 64:
             return False
-        key = getattr(model.model, "conditioning_key", None)
         if key in ("hybrid", "hybrid-adm-mask"):
             # (the other hybrid keys need c_adm / s: they stay on the host-issued path, which keeps the reference's asserts.)  Both
             # guidance branches must see the SAME c_concat (funcs.py:211-214 copies cond and replaces c_crossattn only): the shared
@@ -431,11 +463,10 @@ class BaseEngine(_StepEngine):
         if not 1 <= S <= len(sampler.ddim_timesteps):
             raise ValueError(f"n_rows = {n_rows}: the schedule has {len(sampler.ddim_timesteps)} rows")
         self.S = S
-        cc, cu = torch.cat(cond["c_crossattn"], 1), torch.cat(uc["c_crossattn"], 1)
-        segs = ((B, int(cc.shape[1])), (B, int(cu.shape[1])))
+        segs = tuple((B, sum(int(k.shape[1]) for k in c["c_crossattn"])) for c in (cond, uc))
         # hybrid keys: x carries the latent channels only; the c_concat columns of the first conv's input rows are constant over a
         # trajectory (reset() writes them), the recorded step rewrites the latent columns from plan.x_in; fps is dropped (16)
-        self.hybrid = getattr(model.model, "conditioning_key", None) != "crossattn"
+        self.hybrid = conditioning_key(model) != "crossattn"
         concat = cond.get("c_concat") if self.hybrid else None
         pieces = None if concat is None else tuple(int(c.shape[1]) for c in concat)
         # features_adapter: constant over a trajectory like c_concat -- reset() writes the plan's adapter buffers, the recorded step
@@ -443,14 +474,11 @@ class BaseEngine(_StepEngine):
         unet._check_adapter(features_adapter)
         self.plan = plan = _Plan(unet, 2 * B, T, H, W, segs, torch.float32, dev, shared_x=True, pieces=pieces,
                                  adapter=None if features_adapter is None else unet.adapter_sites)
-        f32 = np.float32
-        coef = np.zeros((S, 8), np.float32)
+        coef = np.zeros((S, 8), np.float32)                  # {the five of ddim_coef, scale, scale_prev (1 without use_scale), unused}
         use_scale = bool(sampler.use_scale)
-        for i in range(S):                                   # the 0-dim fp32 tensors of ddim.py:331-343, per schedule index
-            a_t, a_prev, sig = f32(sampler.ddim_alphas[i]), f32(sampler.ddim_alphas_prev[i]), f32(sampler.ddim_sigmas[i])
-            coef[i, :5] = (np.sqrt(a_t), np.sqrt(a_prev), sig, f32(sampler.ddim_sqrt_one_minus_alphas[i]), np.sqrt(f32(1.) - a_prev - sig * sig))
-            coef[i, 5] = f32(sampler.ddim_scale_arr[i]) if use_scale else 1.0
-            coef[i, 6] = f32(sampler.ddim_scale_arr_prev[i]) if use_scale else 1.0
+        for i in range(S):
+            coef[i, :5] = ddim_coef(sampler, i)
+            coef[i, 5:7] = (sampler.ddim_scale_arr[i], sampler.ddim_scale_arr_prev[i]) if use_scale else 1.0
         self.coef = torch.from_numpy(coef).to(dev)
         self.t_table = torch.from_numpy(np.ascontiguousarray(np.asarray(sampler.ddim_timesteps, dtype=np.int64)[:S])).to(dev)
         self.enc_coef = tuple(c.to(dev) for c in sampler.encode_tables())     # `encode`: the whole schedule's q_sample tables
@@ -482,7 +510,7 @@ class BaseEngine(_StepEngine):
         B, T = self.shape[0], self.shape[2]
         fps = (16, 16) if self.hybrid else (cond.get("fps", 16), uc.get("fps", 16))
         self._refuse_unequal_fps(fps)
-        cc, cu = (torch.cat(c["c_crossattn"], 1).expand(B, -1, -1) for c in (cond, uc))
+        cc, cu = (context(c).expand(B, -1, -1) for c in (cond, uc))
         with plan._enqueue():
             self.state.copy_(state_block(seed))
             self.enc_state.copy_(state_block(seed, -1))          # (no step ever draws at this iteration: steps count up from 0)
@@ -508,12 +536,8 @@ class BaseEngine(_StepEngine):
         if tuple(x0.shape) != tuple(self.shape):
             raise ValueError(f"x0 {tuple(x0.shape)} does not match the engine's latents {tuple(self.shape)}")
         t = torch.as_tensor(t_index)
-        t = t.reshape(1).expand(B) if t.dim() == 0 else t
         n_tab = int(self.enc_coef[0].shape[0])
-        if t.dim() != 1 or t.shape[0] != B:
-            raise ValueError(f"t_index must be one schedule index or [{B}] of them, got {tuple(t.shape)}")
-        if not t.is_cuda and (int(t.min()) < 0 or int(t.max()) >= n_tab):
-            raise IndexError(f"index {t.tolist()} is out of bounds for the {n_tab}-entry schedule table")
+        t = check_schedule_index(t.reshape(1).expand(B) if t.dim() == 0 else t, B, n_tab)
         lib = _l.load()
         n = self.noise.numel()
         with plan._enqueue():
@@ -552,25 +576,20 @@ class DdpmEngine(_StepEngine):
     def supported(model, x, cond, uc=None):
         """'crossattn' models with `c_crossattn` / `fps` conditioning only (a tensor or a list is `c_crossattn`, as apply_model takes
         them); a guidance branch must have the same keys and fps (the shared prefix adds ONE fps embedding)"""
-        unet = getattr(getattr(model, "model", None), "diffusion_model", None)
-        if not isinstance(unet, UNetModel) or getattr(model.model, "conditioning_key", None) != "crossattn" or not x.is_cuda:
+        if not isinstance(unet_of(model), UNetModel) or conditioning_key(model) != "crossattn" or not x.is_cuda or cond is None:
             return False
-        as_dict = lambda c: c if isinstance(c, dict) else {"c_crossattn": c if isinstance(c, list) else [c]}
-        if cond is None:
-            return False
-        cond = as_dict(cond)
+        cond = as_cond_dict(cond)
         if "c_crossattn" not in cond or not set(cond.keys()) <= {"c_crossattn", "fps"}:
             return False
         reps = 1
         if uc is not None:
-            uc = as_dict(uc)
+            uc = as_cond_dict(uc)
             if set(uc.keys()) != set(cond.keys()) or not same_fps([cond.get("fps", 16), uc.get("fps", 16)]):
                 return False
             reps = 2
         return reps * x.shape[0] <= 64
 
     def __init__(self, model, x, cond, uc, cfg_scale, timesteps, mask=None, x0=None, seed=0, keep_x_recon=False):
-        from .ddpm import mask_operand
         self.model = model
         self.unet = unet = model.model.diffusion_model
         dev = x.device
@@ -583,12 +602,11 @@ class DdpmEngine(_StepEngine):
         if not 1 <= S <= model.num_timesteps:
             raise ValueError(f"timesteps = {timesteps}: the schedule has {model.num_timesteps} rows")
         self.guided = uc is not None
-        cc = torch.cat(cond["c_crossattn"], 1)
+        n_ctx = lambda c: sum(int(k.shape[1]) for k in c["c_crossattn"])
         if self.guided:
-            cu = torch.cat(uc["c_crossattn"], 1)
-            self.plan = plan = _Plan(unet, 2 * B, T, H, W, ((B, int(cc.shape[1])), (B, int(cu.shape[1]))), torch.float32, dev, shared_x=True)
+            self.plan = plan = _Plan(unet, 2 * B, T, H, W, ((B, n_ctx(cond)), (B, n_ctx(uc))), torch.float32, dev, shared_x=True)
         else:
-            self.plan = plan = _Plan(unet, B, T, H, W, int(cc.shape[1]), torch.float32, dev)
+            self.plan = plan = _Plan(unet, B, T, H, W, n_ctx(cond), torch.float32, dev)
         self.coef = model._ddpm_dev(dev)["coef"]
         self.t_table = torch.arange(S, dtype=torch.int64, device=dev)           # `for i in reversed(range(0, timesteps))`, :632,639
         self.state = torch.zeros(8, dtype=torch.int32, device=dev)
@@ -626,7 +644,6 @@ class DdpmEngine(_StepEngine):
 
     def reset(self, x, cond, uc=None, seed=0, mask=None, x0=None):
         """start a new trajectory on the same plan: latents x_T, contexts, fps, mask and x0, step 0, a new noise stream"""
-        from .ddpm import mask_operand
         plan, dev = self.plan, self.device
         B, T = self.shape[0], self.shape[2]
         if (uc is not None) != self.guided or (mask is not None) != self.masked:
@@ -639,7 +656,7 @@ class DdpmEngine(_StepEngine):
             self.state.copy_(state_block(seed))
             plan.x_in.copy_(x.to(torch.float32))
             plan.fps_rows.copy_(torch.cat([fps_rows(c.get("fps", 16), B, T, dev) for c in branches]))
-            plan.set_context([torch.cat(c["c_crossattn"], 1).expand(B, -1, -1) for c in branches])
+            plan.set_context([context(c).expand(B, -1, -1) for c in branches])
             if self.masked:
                 m, mflag, inner = mask_operand(mask, self.shape, dev)
                 if m.shape != self.mask.shape or inner != self.mask_inner:

@@ -24,7 +24,8 @@ import torch
 
 from . import lib as _l
 from . import ops
-from .unet import same_fps
+from .conditioning import _f32c, check_schedule_index, cond_image_rows, guidance_eps
+from .fifo_graph import BaseEngine, EngineCache, ddim_coef
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
@@ -63,8 +64,35 @@ def _st():
     return C.c_void_p(ops.current_stream())
 
 
-def _f32c(t):
-    return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
+def cfg_combine(e, scale):
+    """e_u + s (e_c - e_u) (ddim.py:304) of `guidance_eps`'s answer, one launch; a single eps (no guidance) as it is"""
+    if torch.is_tensor(e):
+        return e
+    e_c, e_u = _f32c(e[0]), _f32c(e[1])
+    out = torch.empty_like(e_c)
+    _l.check(_l.load().moca_cfg_combine_f32(_l.ptr(e_c), _l.ptr(e_u), _l.ptr(out), float(scale), e_c.numel(), _st()), "moca_cfg_combine_f32")
+    return out
+
+
+def noise_queue(z, alphas_per_frame, frame_index, noises):
+    """The noising queue of `prepare_latents` (funcs.py:53-79) and `ddim_inversion` (ddim.py:1008-1022) as one launch: output frame j =
+    alpha_j ** 0.5 * z[:, :, frame_index[j]] + (1 - alpha_j) ** 0.5 * eps_j over z [b,c,tz,h,w] (cuda, fp32).  The O(Q) coefficients are
+    host scalars evaluated like the reference's 0-dim fp32 tensors (`sqrt_f32`: correctly rounded on every host).  `noises[j]`
+    [b,c,1,h,w] fix the draws, else one torch.randn stands for the Q torch.randn_like calls of the reference."""
+    b, c, tz, h, w = z.shape
+    alphas = torch.as_tensor(alphas_per_frame, dtype=torch.float32)
+    Q = alphas.shape[0]
+    coef_z, coef_n = sqrt_f32(alphas), sqrt_f32(1 - alphas)
+    fidx = torch.as_tensor(frame_index, dtype=torch.int32)
+    if noises is None:
+        noise = torch.randn(b, c, Q, h, w, device=z.device)
+    else:
+        noise = torch.cat([n.to(z.device, torch.float32).reshape(b, c, 1, h, w) for n in noises[:Q]], dim=2).contiguous()
+    out = torch.empty(b, c, Q, h, w, dtype=torch.float32, device=z.device)
+    cz, cn, fi = coef_z.to(z.device), coef_n.to(z.device), fidx.to(z.device)      # (named: a temporary's block would be reused by the next)
+    _l.check(_l.load().moca_fifo_prepare_queue_f32(_l.ptr(z), _l.ptr(noise), _l.ptr(out), _l.ptr(cz), _l.ptr(cn), _l.ptr(fi), b * c, tz, Q,
+                                                   h * w, _st()), "moca_fifo_prepare_queue_f32")
+    return out
 
 
 class DDIMSampler(object):
@@ -78,7 +106,7 @@ class DDIMSampler(object):
         self.cfg_mode = "batched"            # "batched": cond+uncond as one B=2 launch; "concurrent": two B=1
                                              # hipGraphs on two streams (UNetModel.forward_concurrent)
         self.beta = 0.9                      # momentum decay (ddim.py:397)
-        self._base_engine = None
+        self._engines = EngineCache()        # the step graph of `sample` / `decode`
         self.use_graph = True                # `sample`: one hipGraph per DDIM step (fifo_graph.BaseEngine) where the call allows it
         self.share_prefix = True             # the two CFG branches share everything before the first cross-attention (same x, same
                                              # t): computed once (UNetModel.forward_segments(shared_x=True)); False: plain B = 2 batch
@@ -104,52 +132,8 @@ class DDIMSampler(object):
     # ---- UNet with classifier-free guidance ----------------------------------------------
     def _cfg_eps(self, x, t, c, uc, scale, **kwargs):
         """e_u + s (e_c - e_u)  (ddim.py:290-304,362-374)"""
-        if uc is None or scale == 1.:
-            return self.model.apply_model(x, t, c, **kwargs)
-        batched = False
-        if isinstance(c, dict) and isinstance(uc, dict) and x.shape[0] * 2 <= 64:
-            cc = torch.cat(c["c_crossattn"], 1)
-            cu = torch.cat(uc["c_crossattn"], 1)
-            batched = cc.shape == cu.shape and set(c.keys()) == set(uc.keys()) <= {"c_crossattn", "fps"}
-        unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-        fa = kwargs.get("features_adapter")          # adapter maps (openaimodel3d.py:562-567): the same list for both branches
-        if batched and self.cfg_mode == "concurrent" and hasattr(unet, "forward_concurrent") and not kwargs.get("no_concurrent") \
-                and fa is None:
-            f_c, f_u = c.get("fps", 16), uc.get("fps", 16)
-            e_c, e_u = unet.forward_concurrent([dict(x=x, timesteps=t, context=cc, fps=f_c),
-                                                dict(x=x, timesteps=t, context=cu, fps=f_u)])
-        elif batched and self.share_prefix and hasattr(unet, "forward_segments") and \
-                getattr(self.model.model, "conditioning_key", None) == "crossattn" and same_fps([c.get("fps", 16), uc.get("fps", 16)]):
-            # both branches in ONE forward that shares everything before the first cross-attention (same x, same t)
-            B = x.shape[0]
-            e = unet.forward_segments(x, t, [cc, cu], fps=[c.get("fps", 16), uc.get("fps", 16)], shared_x=True, features_adapter=fa)
-            e_c, e_u = e[:B], e[B:]
-        elif batched:
-            B = x.shape[0]
-            cond = {"c_crossattn": [torch.cat([cc, cu], 0)]}
-            if "fps" in c:
-                f_c, f_u = c["fps"], uc["fps"]
-                if isinstance(f_c, int):
-                    cond["fps"] = f_c
-                else:
-                    cond["fps"] = torch.cat([torch.as_tensor(f_c).reshape(-1).expand(B), torch.as_tensor(f_u).reshape(-1).expand(B)], 0)
-            tt = torch.as_tensor(t, device=x.device).reshape(-1)
-            if tt.shape[0] == B:                     # uniform timestep per sample
-                t2 = torch.cat([tt, tt], 0)
-            else:                                    # FIFO: per-frame timesteps, B == 1 -> per-(b,t) rows
-                t2 = torch.cat([tt, tt], 0)
-            if fa is not None:                       # [x, x]: the frames of every map twice
-                kwargs = dict(kwargs, features_adapter=[torch.cat([f, f], 0) for f in fa])
-            e = self.model.apply_model(torch.cat([x, x], 0), t2, cond, **kwargs)
-            e_c, e_u = e[:B], e[B:]
-        else:
-            e_c = self.model.apply_model(x, t, c, **kwargs)
-            e_u = self.model.apply_model(x, t, uc, **kwargs)
-        e_c, e_u = _f32c(e_c), _f32c(e_u)
-        out = torch.empty_like(e_c)
-        _l.check(_l.load().moca_cfg_combine_f32(_l.ptr(e_c), _l.ptr(e_u), _l.ptr(out), float(scale), e_c.numel(), _st()),
-                 "moca_cfg_combine_f32")
-        return out
+        e = guidance_eps(self.model, x, t, c, uc, scale, share_prefix=self.share_prefix, cfg_mode=self.cfg_mode, **kwargs)
+        return cfg_combine(e, scale)
 
     @torch.no_grad()
     def unet(self, x, c, t, unconditional_guidance_scale=1., unconditional_conditioning=None, **kwargs):
@@ -192,27 +176,39 @@ class DDIMSampler(object):
         """the cached step graph (fifo_graph.BaseEngine) for this call, reset to a new trajectory; built when the key changes.  `n_rows`:
         the rows of the schedule tables the captured kernels index (all of them for `sample`, the first t_start for `decode`): part of
         the key, so neither picks up the other's engine"""
-        from .fifo_graph import BaseEngine
         cu, cn = cond["c_crossattn"], uc["c_crossattn"]
         key = (tuple(img.shape), sum(c.shape[1] for c in cu), sum(c.shape[1] for c in cn), float(scale),
                self.ddim_timesteps.tobytes(), np.asarray(self.ddim_sigmas).tobytes(), str(img.device),
                tuple(int(c.shape[1]) for c in cond.get("c_concat") or ()),
                None if features_adapter is None else tuple(tuple(f.shape) for f in features_adapter), int(n_rows))
-        if self._base_engine is not None and self._base_engine[0] != key:
-            self._base_engine[1].close()
-            self._base_engine = None
-        if self._base_engine is None:
-            self._base_engine = (key, BaseEngine(self.model, self, img, cond, uc, scale, seed=seed, features_adapter=features_adapter,
-                                                 n_rows=n_rows))
-        else:
-            self._base_engine[1].reset(img, cond, uc, seed, features_adapter=features_adapter)
-        return self._base_engine[1]
+        return self._engines.get(key, lambda: BaseEngine(self.model, self, img, cond, uc, scale, seed=seed, features_adapter=features_adapter,
+                                                         n_rows=n_rows),
+                                 lambda eng: eng.reset(img, cond, uc, seed, features_adapter=features_adapter))
+
+    _base_engine = property(lambda self: self._engines.entry, doc="None, or the (key, engine) of the cached step graph")
 
     def release(self):
         """free the cached step graph of `sample` (plan buffers + hipGraph)"""
-        if self._base_engine is not None:
-            self._base_engine[1].close()
-            self._base_engine = None
+        self._engines.release()
+
+    def _run_steps(self, x, cond, uc, scale, n_steps, noises, use_graph, features_adapter=None):
+        """the loop of `sample` and `decode`: n_steps calls of p_sample_ddim over `ddim_timesteps[:n_steps]` flipped -- step i at schedule
+        index n_steps - 1 - i, `noises[i]` fixing its draw -- as one hipGraph per step (fifo_graph.BaseEngine: latents, schedule and
+        noise stay on the device) where `use_graph` and `BaseEngine.supported` allow it, else host-issued"""
+        noise = lambda i: None if noises is None else noises[i]
+        if n_steps > 0 and use_graph and self.share_prefix and BaseEngine.supported(self.model, x, cond, uc, scale,
+                                                                                    features_adapter=features_adapter):
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())                  # the host generator seeds the device stream
+            eng = self._engine_for(x, cond, uc, scale, seed, n_steps, features_adapter=features_adapter)
+            for i in range(n_steps):
+                eng.step(noise=noise(i))
+            return eng.latents().to(x.dtype)
+        unet_kwargs = {} if features_adapter is None else {"features_adapter": list(features_adapter)}
+        for i, step in enumerate(np.flip(self.ddim_timesteps[:n_steps])):
+            ts = torch.full((x.shape[0],), int(step), device=x.device, dtype=torch.long)
+            x, _ = self.p_sample_ddim(x, cond, ts, index=n_steps - i - 1, use_original_steps=False, unconditional_guidance_scale=scale,
+                                      unconditional_conditioning=uc, noise=noise(i), **unet_kwargs)
+        return x
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, eta=0., x_T=None, verbose=False,
@@ -227,28 +223,9 @@ class DDIMSampler(object):
         img = torch.randn(size, device=device) if x_T is None else x_T
         if latents_dir is not None:
             torch.save(img, f"{latents_dir}/0.pt")                    # :233-234
-        time_range = np.flip(self.ddim_timesteps)
         total_steps = self.ddim_timesteps.shape[0]
-        kwargs.pop("temporal_length", None); kwargs.pop("conditional_guidance_scale_temporal", None)
-        unet_kwargs = {} if features_adapter is None else {"features_adapter": list(features_adapter)}
-        from .fifo_graph import BaseEngine
-        if self.use_graph and self.share_prefix and BaseEngine.supported(self.model, img, conditioning, unconditional_conditioning,
-                                                                         unconditional_guidance_scale, features_adapter=features_adapter):
-            # the loop body as one hipGraph per step (fifo_graph.BaseEngine): latents, schedule and noise stay on the device
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())                  # the host generator seeds the device stream
-            eng = self._engine_for(img, conditioning, unconditional_conditioning, unconditional_guidance_scale, seed, total_steps,
-                                   features_adapter=features_adapter)
-            for i in range(total_steps):
-                eng.step(noise=None if noises is None else noises[i])
-            img = eng.latents().to(img.dtype)
-            time_range = []
-        for i, step in enumerate(time_range):
-            index = total_steps - i - 1
-            ts = torch.full((batch_size,), int(step), device=device, dtype=torch.long)
-            img, pred_x0 = self.p_sample_ddim(img, conditioning, ts, index=index,
-                                              unconditional_guidance_scale=unconditional_guidance_scale,
-                                              unconditional_conditioning=unconditional_conditioning,
-                                              noise=None if noises is None else noises[i], **unet_kwargs)
+        img = self._run_steps(img, conditioning, unconditional_conditioning, unconditional_guidance_scale, total_steps, noises, self.use_graph,
+                              features_adapter=features_adapter)
         if latents_dir is not None:
             torch.save(img, f"{latents_dir}/{total_steps}.pt")        # :249-250
         return img, {}
@@ -273,12 +250,8 @@ class DDIMSampler(object):
         if not x0.is_cuda:
             raise ValueError("stochastic_encode runs on the GPU: x0 must be a cuda tensor")
         ca, cb = self.encode_tables(use_original_steps)
-        t = torch.as_tensor(t)
         B = x0.shape[0]
-        if t.dim() != 1 or t.shape[0] != B:
-            raise ValueError(f"t must hold one schedule index per sample, shape [{B}], got {tuple(t.shape)}")
-        if not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) >= ca.shape[0]):
-            raise IndexError(f"index {t.tolist()} is out of bounds for the {ca.shape[0]}-entry schedule table")
+        t = check_schedule_index(t, B, ca.shape[0])
         noise = torch.randn_like(x0) if noise is None else _f32c(noise.to(x0.device))                    # :662-663
         if noise.shape != x0.shape:
             raise ValueError(f"noise {tuple(noise.shape)} does not match x0 {tuple(x0.shape)}")
@@ -299,27 +272,9 @@ class DDIMSampler(object):
             raise NotImplementedError(
                 "decode(use_original_steps=True) cannot run in the reference: p_sample_ddim reads self.model.ddim_sigmas_for_original_num_steps "
                 "(ddim.py:325), which exists only on the sampler, and self.model.scale_arr_prev (ddim.py:352), which is never registered")
-        timesteps = self.ddim_timesteps[:t_start]                     # :677-678 (numpy slicing: a t_start past the schedule is the whole of it)
-        time_range = np.flip(timesteps)
-        total_steps = timesteps.shape[0]
-        x_dec = x_latent
-        use_graph = self.use_graph if use_graph is None else use_graph
-        from .fifo_graph import BaseEngine
-        if total_steps > 0 and use_graph and self.share_prefix and BaseEngine.supported(
-                self.model, x_dec, cond, unconditional_conditioning, unconditional_guidance_scale):
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            eng = self._engine_for(x_dec, cond, unconditional_conditioning, unconditional_guidance_scale, seed, total_steps)
-            for i in range(total_steps):
-                eng.step(noise=None if noises is None else noises[i])
-            return eng.latents().to(x_latent.dtype)
-        for i, step in enumerate(time_range):
-            index = total_steps - i - 1
-            ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
-            x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
-                                          unconditional_guidance_scale=unconditional_guidance_scale,
-                                          unconditional_conditioning=unconditional_conditioning,
-                                          noise=None if noises is None else noises[i])
-        return x_dec
+        n_steps = self.ddim_timesteps[:t_start].shape[0]              # :677-678 (numpy slicing: a t_start past the schedule is the whole of it)
+        return self._run_steps(x_latent, cond, unconditional_conditioning, unconditional_guidance_scale, n_steps, noises,
+                               self.use_graph if use_graph is None else use_graph)
 
     @staticmethod
     def inversion_frame_index(num_inference_steps, n_frames):
@@ -345,22 +300,13 @@ class DDIMSampler(object):
             latents = torch.cat([latents, torch.zeros_like(latents[:, :1])], dim=1)
         N = int(num_inference_steps)
         z = latents.to("cuda", torch.float32).contiguous()
-        b, c, tz, h, w = z.shape
-        alphas = torch.as_tensor(np.asarray(self.ddim_alphas), dtype=torch.float32)[:N]
+        alphas = np.asarray(self.ddim_alphas)[:N]
         if alphas.shape[0] != N:
             raise IndexError(f"num_inference_steps = {N} runs past the {alphas.shape[0]}-step schedule (ddim.py:1010)")
-        coef_z, coef_n = sqrt_f32(alphas), sqrt_f32(1 - alphas)       # the 0-dim fp32 tensors alpha ** 0.5, beta ** 0.5 of :1010-1011,1021
-        fidx = torch.tensor(self.inversion_frame_index(N, frames.shape[2]), dtype=torch.int32)
-        if int(fidx.max()) >= tz:
-            raise IndexError(f"frame index {int(fidx.max())} is out of range for {tz} latent frames (ddim.py:1017)")
-        if noises is None:
-            noise = torch.randn(b, c, N, h, w, device=z.device)       # the N torch.randn_like draws of :1020 as one tensor
-        else:
-            noise = torch.cat([n.to(z.device, torch.float32).reshape(b, c, 1, h, w) for n in noises[:N]], dim=2).contiguous()
-        out = torch.empty(b, c, N, h, w, dtype=torch.float32, device=z.device)
-        cz, cn, fi = coef_z.to(z.device), coef_n.to(z.device), fidx.to(z.device)
-        _l.check(_l.load().moca_fifo_prepare_queue_f32(_l.ptr(z), _l.ptr(noise), _l.ptr(out), _l.ptr(cz), _l.ptr(cn), _l.ptr(fi), b * c, tz, N,
-                                                       h * w, _st()), "moca_fifo_prepare_queue_f32")
+        fidx = self.inversion_frame_index(N, frames.shape[2])
+        if max(fidx) >= z.shape[2]:
+            raise IndexError(f"frame index {max(fidx)} is out of range for {z.shape[2]} latent frames (ddim.py:1017)")
+        out = noise_queue(z, alphas, fidx, noises)
         if latents_dir is not None:
             for i in range(N):
                 torch.save(out[:, :, [i]].clone(), f"{latents_dir}/step_{i}.pt")          # :1024-1025
@@ -380,36 +326,11 @@ class DDIMSampler(object):
         x = torch.cat(windows, 0)
         t = torch.cat([torch.as_tensor(np.asarray(ts).copy(), device=x.device).to(torch.long).reshape(-1) for ts in ts_list], 0)
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
-        cc = torch.cat(c["c_crossattn"], 1).expand(W, -1, -1)
         fps_c = c.get("fps", 16)
-
-        def fps_rows(f, n):
-            return f if isinstance(f, int) else torch.as_tensor(f, device=x.device).reshape(-1)[:1].expand(n)
-
-        if uc is None or scale == 1.:
-            e = self.model.apply_model(x, t, {"c_crossattn": [cc], "fps": fps_rows(fps_c, W)}, **kwargs)
-            return list(e.split(1, 0))
-        cu = torch.cat(uc["c_crossattn"], 1).expand(W, -1, -1)
-        fps_u = uc.get("fps", fps_c)
-        unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-        if self.share_prefix and hasattr(unet, "forward_segments") and getattr(self.model.model, "conditioning_key", None) == "crossattn" \
-                and same_fps([fps_c, fps_u]):
-            fr_c = fps_rows(fps_c, W)
-            e = unet.forward_segments(x, t, [cc, cu], fps=[fr_c, fr_c if fps_u is fps_c else fps_rows(fps_u, W)], shared_x=True)
-            e_c, e_u = e[:W], e[W:]
-        elif cc.shape == cu.shape and isinstance(fps_c, int) == isinstance(fps_u, int):
-            fps2 = fps_c if isinstance(fps_c, int) else torch.cat([fps_rows(fps_c, W), fps_rows(fps_u, W)], 0)
-            e = self.model.apply_model(torch.cat([x, x], 0), torch.cat([t, t], 0),
-                                       {"c_crossattn": [torch.cat([cc, cu], 0)], "fps": fps2}, **kwargs)
-            e_c, e_u = e[:W], e[W:]
-        else:   # e.g. 154 conditional tokens (two prompts) vs 77 unconditional: two batched calls
-            e_c = self.model.apply_model(x, t, {"c_crossattn": [cc], "fps": fps_rows(fps_c, W)}, **kwargs)
-            e_u = self.model.apply_model(x, t, {"c_crossattn": [cu], "fps": fps_rows(fps_u, W)}, **kwargs)
-        e_c, e_u = _f32c(e_c), _f32c(e_u)
-        out = torch.empty_like(e_c)
-        _l.check(_l.load().moca_cfg_combine_f32(_l.ptr(e_c), _l.ptr(e_u), _l.ptr(out), float(scale), e_c.numel(), _st()),
-                 "moca_cfg_combine_f32")
-        return list(out.split(1, 0))
+        wide = lambda d, fps: {"c_crossattn": [k.expand(W, -1, -1) for k in d["c_crossattn"]], "fps": fps}    # one context per window
+        e = guidance_eps(self.model, x, t, wide(c, fps_c), None if uc is None else wide(uc, uc.get("fps", fps_c)), scale,
+                         share_prefix=self.share_prefix, rows=W, share_any=True, **kwargs)
+        return list(cfg_combine(e, scale).split(1, 0))
 
     # ---- MoCA FIFO step -----------------------------------------------------------------------
     @torch.no_grad()
@@ -484,13 +405,7 @@ class DDIMSampler(object):
         enh = np.ones((f,), dtype=np.float32)
         midx = np.full((f,), -1, dtype=np.int32)
         for i, index in enumerate(indices):
-            a_t, a_prev = f32(self.ddim_alphas[index]), f32(self.ddim_alphas_prev[index])
-            sigma, s1m = f32(self.ddim_sigmas[index]), f32(self.ddim_sqrt_one_minus_alphas[index])
-            coef[i, 0] = np.sqrt(a_t)                                  # a_t.sqrt()            :415
-            coef[i, 1] = np.sqrt(a_prev)                               # a_prev.sqrt()         :562
-            coef[i, 2] = sigma
-            coef[i, 3] = s1m
-            coef[i, 4] = np.sqrt(f32(1.) - a_prev - sigma * sigma)     # :418
+            coef[i, :5] = ddim_coef(self, index)                       # :415,562,418
             coef[i, 5] = f32(2) * (f32(1.0) - f32(ts_np[i]) / f32(1000.0))   # correction_strength :428
             enh[i] = 1.5 if ts_np[i] <= 300 else 1.0                   # :582
             mi = i
@@ -545,16 +460,7 @@ class DDIMSampler(object):
             enh[:] = 2.0                                        # enhancement_factor = 2 (:847)
         if davis_masks is not None:
             mask_d = _f32c(davis_masks.to(device)).reshape(b, 1, Fm, H * W)
-            if cond_image is None:
-                cond_d = torch.zeros(b, Cc, H * W, device=device)     # :573-574
-            else:
-                ci = cond_image.to(device)
-                if ci.shape[1] != Cc:
-                    if ci.shape[1] == 3:                               # :575-578
-                        ci = torch.cat([ci, torch.ones_like(ci[:, :1])], dim=1)
-                    else:
-                        raise ValueError(f"Conditional image must have 3 or 4 channels, got {ci.shape[1]}")
-                cond_d = _f32c(ci).reshape(-1, Cc, H * W).expand(b, Cc, H * W).contiguous()
+            cond_d = cond_image_rows(cond_image, Cc, H * W, device).expand(b, Cc, H * W).contiguous()      # :573-578
             midx_d = torch.from_numpy(midx).to(device)
             enh_d = torch.from_numpy(enh).to(device)
             ws = torch.empty(max(Fm, 1), dtype=torch.float32, device=device)

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .conditioning import CONTEXT_FREE_KEYS, HYBRID_KEYS  # noqa: F401  (re-exported: the keys DiffusionWrapper.forward branches on)
 from .ddpm import DdpmMixin
 from .unet import UNetModel
 
@@ -57,13 +58,6 @@ def load_unet_config(yaml_path):
     with open(yaml_path) as f:
         cfg = yaml.safe_load(f)
     return cfg["model"]["params"]["unet_config"], cfg["model"]["params"]
-
-
-# conditioning latents concatenated to x along the channel axis + a cross-attention context (ddpm3d.py:713-717,724-733,747-759)
-HYBRID_KEYS = ("hybrid", "hybrid-adm", "hybrid-time", "hybrid-adm-mask", "hybrid-time-adm")
-# keys whose branch calls the UNet with context=None: the reference's own UNet fails there (openaimodel3d.py:547,
-# `context.repeat_interleave` on None)
-CONTEXT_FREE_KEYS = (None, "concat", "adm", "resblockcond", "concat-time-mask", "concat-adm-mask")
 
 
 class DiffusionWrapper(nn.Module):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Record the two "as at another commit" fixtures of tests/test_temporal_variants_{cpu,gpu}.py from a CHECKOUT of that commit (its tree
-with its own built libmoca_hip.so), so that they can be audited and re-recorded when a plan optimisation or a compiler bump
-legitimately changes them:
+"""Record the "as at another commit" fixtures of tests/test_temporal_variants_{cpu,gpu}.py and tests/test_sampler_routes_cpu.py from a
+CHECKOUT of that commit (its tree with its own built libmoca_hip.so), so that they can be audited and re-recorded when a plan
+optimisation or a compiler bump legitimately changes them:
 
   tests/golden/plan_full_launches.npz            (--plans, no GPU)  the launch lists of tests/plan_cpu.py::fixture_plans (seven plans of
                                                  the FULL configuration, the hybrid `pieces` plan of the reduced one), one line per
@@ -10,10 +10,15 @@ legitimately changes them:
   tests/golden/temporal_attention_parent_sha.npz (--sha, on the GPU)  sha256 of the outputs of moca_temporal_attention_f16 and of the
                                                  non-causal MOCA_EP_TATTN launch on the host-generated operands of
                                                  tests/temporal_variants_ref.py
+  tests/golden/sampler_routes.npz                (--samplers, no GPU)  the traces of tests/sampler_routes_cpu.py::record: the UNet entry
+                                                 points and launches of the sampling layer (guidance routing, host-issued loops,
+                                                 ddim_step, queue noising, the host-driven FIFO loop, `supported()` tables) as
+                                                 lines, the coefficient tables as arrays
 
     git worktree add ../base <commit> && make -C ../base/moca_video_amd/csrc
     python tools/record_parent_fixtures.py --tree ../base --plans          (any host)
     python tools/record_parent_fixtures.py --tree ../base --sha            (on the MI355X)
+    python tools/record_parent_fixtures.py --tree ../base --samplers       (any host)
 
 The package is imported from --tree, the helpers (tests/plan_cpu.py, tests/temporal_variants_ref.py) and the output directory are this
 checkout's.  A tree older than the host-recordable plan (no `UNetModel._pack(dev)`, a stream created unconditionally) is recorded
@@ -86,11 +91,19 @@ def record_sha():
     np.savez_compressed(os.path.join(GOLD, "temporal_attention_parent_sha.npz"), names=np.asarray(names), sha256=np.asarray(shas))
 
 
+def record_samplers():
+    import sampler_routes_cpu
+    out = sampler_routes_cpu.record()
+    print(f"{len(out)} traces, {sum(len(v) for k, v in out.items() if v.dtype.kind == 'U')} lines")
+    np.savez_compressed(os.path.join(GOLD, "sampler_routes.npz"), **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", required=True, help="checkout (with its built library) to record from")
     ap.add_argument("--plans", action="store_true")
     ap.add_argument("--sha", action="store_true")
+    ap.add_argument("--samplers", action="store_true")
     a = ap.parse_args()
     tree = os.path.abspath(a.tree)
     sys.path.insert(0, tree)
@@ -101,6 +114,8 @@ def main():
         record_plans()
     if a.sha:
         record_sha()
+    if a.samplers:
+        record_samplers()
 
 
 if __name__ == "__main__":
