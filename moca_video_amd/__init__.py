@@ -12,7 +12,8 @@ Public surface mirrors the reference interfaces for this path only:
   prepare_latents, shift_latents, fifo_ddim_sampling, base_ddim_sampling   scripts/evaluation/funcs.py
   fifo_ddim_sampling_multiprompts   funcs.py:375-468 (one video, prompts switched inside the one-graph loop)
   v2v_ddim_sampling    DDIMSampler.stochastic_encode + decode (ddim.py:652-692): noise a clip's latents, denoise under a new prompt
-  load_multiprompts, run_multiprompts   its prompt file and driver (moca_video_amd.io)
+  freeinit_ddim_sampling   FreeInit (Wu et al., 2023) over base_ddim_sampling: re-noise with the initial noise, freq_mix_3d, sample again
+  load_multiprompts, run_multiprompts  its prompt file and driver (moca_video_amd.io)
   instantiate_from_config       utils/utils.py:27-42
   AutoencoderKL                 lvdm/models/autoencoder.py:13-107 + lvdm/modules/networks/ae_modules.py:364-579
   FrozenOpenCLIPEmbedder        lvdm/modules/encoders/condition.py:174-235 (text tower on token ids)
@@ -34,9 +35,9 @@ from .tokenizer import SimpleTokenizer  # noqa: E402
 from .image_proj import ImageProjModel, Resampler  # noqa: E402
 from .clip_vision import FrozenOpenCLIPImageEmbedder, FrozenOpenCLIPImageEmbedderV2  # noqa: E402
 from .wrapper import LatentVisualDiffusion  # noqa: E402
-from .fifo import fifo_ddim_sampling_multiprompts, v2v_ddim_sampling  # noqa: E402
+from .fifo import fifo_ddim_sampling_multiprompts, freeinit_ddim_sampling, v2v_ddim_sampling  # noqa: E402
 from .io import load_multiprompts, run_multiprompts  # noqa: E402
 
 __all__ = ["UNetModel", "DiffusionWrapper", "DenoiseModel", "AutoencoderKL", "FrozenOpenCLIPEmbedder", "SimpleTokenizer", "ImageProjModel", "Resampler",
            "FrozenOpenCLIPImageEmbedder", "FrozenOpenCLIPImageEmbedderV2", "LatentVisualDiffusion", "instantiate_from_config",
-           "load_unet_config", "fifo_ddim_sampling_multiprompts", "v2v_ddim_sampling", "load_multiprompts", "run_multiprompts"]
+           "load_unet_config", "fifo_ddim_sampling_multiprompts", "v2v_ddim_sampling", "freeinit_ddim_sampling", "load_multiprompts", "run_multiprompts"]

@@ -10,7 +10,7 @@ import torch
 
 from .conditioning import refuse_concat, refuse_image_attention, refuse_long_window
 from .fifo_graph import FifoEngine, fifo_windows, lookahead_schedule
-from .freeinit import freq_mix_3d, get_freq_filter
+from .freeinit import freeinit_steps, freq_mix_3d, get_freq_filter
 from .sampler import DDIMSampler, noise_queue
 
 
@@ -114,6 +114,35 @@ def base_ddim_sampling(model, cond, noise_shape, ddim_steps=50, ddim_eta=1.0, cf
     sampler.release()                        # the step graph's buffers: the FIFO stage that follows builds its own plan
     images = model.decode_first_stage_2DAE(samples) if getattr(model, "first_stage_model", None) is not None else None
     return images, sampler, samples
+
+
+def freeinit_ddim_sampling(model, cond, noise_shape, ddim_steps=50, ddim_eta=1.0, cfg_scale=1.0, uc_emb=None, num_iters=5,
+                           filter_type="butterworth", n=4, d_s=0.25, d_t=0.25, use_fast_sampling=False, x_T=None, z_rands=None,
+                           noises=None, use_graph=True, return_all=False):
+    """FreeInit (Wu et al., 2023) on `base_ddim_sampling`: sample, re-noise the result to t = num_timesteps - 1 with the INITIAL noise,
+    keep its low spatio-temporal frequencies (`get_freq_filter(noise_shape, filter_type, n, d_s, d_t)`) and take the high ones from
+    fresh noise (`freq_mix_3d`), sample again -- `num_iters` trajectories in all (`DDIMSampler.sample_freeinit`).  Every trajectory takes
+    `ddim_steps` steps, or with `use_fast_sampling` `freeinit_steps`' coarse-to-fine counts.  num_iters = 1 is `base_ddim_sampling`.
+    `x_T` fixes the initial noise, `z_rands[k-1]` the fresh noise of trajectory k >= 1, `noises[k][i]` the draw of its step i.
+    Returns (images, sampler, samples) like `base_ddim_sampling` (the decode of the last trajectory); with `return_all`, `samples` is
+    the list of every trajectory's latents."""
+    steps = freeinit_steps(ddim_steps, num_iters, use_fast_sampling)
+    if len(noise_shape) != 5:
+        raise ValueError(f"noise_shape = {tuple(noise_shape)}: FreeInit filters over (T, H, W) of [B, C, T, H, W] latents")
+    if z_rands is not None and len(z_rands) != num_iters - 1:
+        raise ValueError(f"z_rands holds {len(z_rands)} tensors for {num_iters - 1} re-initialisations")
+    if noises is not None and len(noises) != num_iters:
+        raise ValueError(f"noises holds {len(noises)} lists for {num_iters} iterations")
+    LPF = get_freq_filter(tuple(noise_shape), model.device, filter_type, n, d_s, d_t)
+    sampler = DDIMSampler(model)
+    sampler.use_graph = use_graph
+    uc = base_uncond(model, cond, noise_shape[0], cfg_scale, uc_emb)
+    last, every = sampler.sample_freeinit(steps, noise_shape[0], tuple(noise_shape[1:]), LPF, conditioning=cond, eta=ddim_eta, x_T=x_T,
+                                          z_rands=z_rands, noises=noises, unconditional_guidance_scale=cfg_scale,
+                                          unconditional_conditioning=uc, return_all=return_all)
+    sampler.release()
+    images = model.decode_first_stage_2DAE(last) if getattr(model, "first_stage_model", None) is not None else None
+    return images, sampler, (every if return_all else last)
 
 
 def v2v_ddim_sampling(model, cond, latents=None, frames=None, ddim_steps=50, t_start=25, ddim_eta=1.0, cfg_scale=1.0, uc_emb=None,

@@ -474,16 +474,16 @@ class BaseEngine(_StepEngine):
         unet._check_adapter(features_adapter)
         self.plan = plan = _Plan(unet, 2 * B, T, H, W, segs, torch.float32, dev, shared_x=True, pieces=pieces,
                                  adapter=None if features_adapter is None else unet.adapter_sites)
-        coef = np.zeros((S, 8), np.float32)                  # {the five of ddim_coef, scale, scale_prev (1 without use_scale), unused}
         use_scale = bool(sampler.use_scale)
-        for i in range(S):
-            coef[i, :5] = ddim_coef(sampler, i)
-            coef[i, 5:7] = (sampler.ddim_scale_arr[i], sampler.ddim_scale_arr_prev[i]) if use_scale else 1.0
-        self.coef = torch.from_numpy(coef).to(dev)
-        self.t_table = torch.from_numpy(np.ascontiguousarray(np.asarray(sampler.ddim_timesteps, dtype=np.int64)[:S])).to(dev)
-        self.enc_coef = tuple(c.to(dev) for c in sampler.encode_tables())     # `encode`: the whole schedule's q_sample tables
+        self._built = self._schedule_tables(sampler, S)      # host copies: `reset` puts them back after a `set_schedule`
+        self.coef, self.t_table = (t.to(dev) for t in self._built)
+        self.it0, self._schedule_set = 0, False              # where a trajectory's iteration counter starts (`set_schedule`)
+        self.enc_coef = self._built_enc = tuple(c.to(dev) for c in sampler.encode_tables())     # `encode`: the whole schedule's q_sample tables
         self.state = torch.zeros(8, dtype=torch.int32, device=dev)
         self.enc_state = torch.zeros(8, dtype=torch.int32, device=dev)        # the noise stream of `encode`: same seed, iteration -1
+        self.model = model
+        self._reinit_bufs = None                             # `reinit` (FreeInit): made by its first call
+        self._reinit_src = (None, None)
         n = x.numel()
         self.noise = torch.zeros(n, dtype=torch.float32, device=dev)
         self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev) if keep_pred_x0 else None
@@ -502,8 +502,103 @@ class BaseEngine(_StepEngine):
                                                  _l.ptr(self.coef), S, float(cfg_scale), 1 if use_scale else 0, n, S_()), "moca_base_ddim_step_f32")
         self._wrap_plan(pre, post)
 
+    @staticmethod
+    def _schedule_tables(sampler, n_rows):
+        """host tables over the first `n_rows` rows of the sampler's schedule: coef [n_rows][8] = {the five of ddim_coef, scale,
+        scale_prev (1 without use_scale), unused} and the int64 timesteps"""
+        coef = np.zeros((n_rows, 8), np.float32)
+        use_scale = bool(sampler.use_scale)
+        for i in range(n_rows):
+            coef[i, :5] = ddim_coef(sampler, i)
+            coef[i, 5:7] = (sampler.ddim_scale_arr[i], sampler.ddim_scale_arr_prev[i]) if use_scale else 1.0
+        t_table = np.ascontiguousarray(np.asarray(sampler.ddim_timesteps, dtype=np.int64)[:n_rows])
+        return torch.from_numpy(coef), torch.from_numpy(t_table)
+
+    def _write_schedule(self, coef, t_table):
+        """enqueue the tables into rows 0 .. len-1 of the device tables and move the start of the iteration counter so that step i of a
+        trajectory reads row len - 1 - i through the captured S (row S - 1 - iter)"""
+        n = int(t_table.shape[0])
+        with self.plan._enqueue():
+            self.coef[:n].copy_(coef)
+            self.t_table[:n].copy_(t_table)
+            self.state[1:2].fill_(self.S - n)
+        self.it0 = self.n_iter = self.S - n
+
+    def set_schedule(self, sampler):
+        """Run the next trajectories over `sampler`'s current schedule of S' <= S steps WITHOUT a new capture (FreeInit's coarse-to-fine
+        iterations).  S is a launch argument baked into the captured `moca_base_set_timestep` / `moca_base_ddim_step_f32`, which read
+        table row S - 1 - iter: the S' rows of the new schedule go to rows 0 .. S'-1 of the device tables and the iteration counter
+        starts at S - S', so step i reads row S' - 1 - i.  The graph, the plan and its buffers are untouched; `encode` follows the
+        new schedule.  Enqueued, not synchronised; holds until the next `set_schedule` or `reset` (which puts the engine's own schedule
+        back).  Call it between trajectories: it sets the counter to the start of one."""
+        n = len(sampler.ddim_timesteps)
+        if not 1 <= n <= self.S:
+            raise ValueError(f"set_schedule: a schedule of {n} steps does not fit the {self.S} rows this engine was captured for")
+        self._write_schedule(*self._schedule_tables(sampler, n))
+        self.enc_coef = tuple(c.to(self.device) for c in sampler.encode_tables())
+        self._schedule_set = True
+
+    def reinit(self, initial_noise, lpf, z_rand=None, seed=0):
+        """FreeInit's noise re-initialisation of the latents in the plan's input buffer (`freeinit.freeinit_reinit` on the device), on
+        the plan's stream, enqueued and not synchronised: x_in <- freq_mix_3d(q_sample(x_in, t = num_timesteps - 1, initial_noise),
+        z_rand, lpf) with the model's DDPM tables (`moca_ddpm_step_f32` in its q_sample mode: `use_scale` multiplies by scale_arr[t]),
+        then the state block back to the start of a trajectory with the new `seed`.  `z_rand` None: drawn by `moca_fifo_randn_f32` from
+        the engine's own Philox stream (the new seed at iteration -2, which neither a step nor `encode` uses).  `initial_noise` and the
+        filter volume `lpf` ([..., T, H, W], constant over the leading dims) are written to the device once per run: again only when
+        another tensor object is handed in, or after `reset`.  Contexts, fps rows, adapter maps and c_concat columns are not touched."""
+        plan, dev = self.plan, self.device
+        B, Cc, T, H, W = self.shape
+        n = self.noise.numel()
+        lib = _l.load()
+        model = self.model
+        if self._reinit_bufs is None:
+            f32 = dict(dtype=torch.float32, device=dev)
+            self._reinit_bufs = dict(
+                coef=model._ddpm_dev(dev)["coef"], flags=model._ddpm_flags(x0_param=False),
+                t_last=torch.full((B,), model.num_timesteps - 1, dtype=torch.int64, device=dev),
+                state=torch.zeros(8, dtype=torch.int32, device=dev), init_noise=torch.empty(n, **f32), lpf=torch.empty(T * H * W, **f32),
+                z_T=torch.empty(n, **f32), ws=torch.empty(int(lib.moca_freq_mix_ws_bytes(B * Cc, T, H, W)) // 4, **f32))
+        b = self._reinit_bufs
+        if tuple(initial_noise.shape) != tuple(self.shape):
+            raise ValueError(f"initial_noise {tuple(initial_noise.shape)} does not match the engine's latents {tuple(self.shape)}")
+        if tuple(lpf.shape[-3:]) != (T, H, W):
+            raise ValueError(f"lpf {tuple(lpf.shape)} is no filter over the engine's (T, H, W) = {(T, H, W)}")
+        if z_rand is not None and z_rand.numel() != n:
+            raise ValueError(f"z_rand {tuple(z_rand.shape)} does not match the engine's latents {tuple(self.shape)}")
+        with plan._enqueue():
+            h = C.c_void_p(plan.stream.cuda_stream)
+            def upload(dst, src):
+                src = src.to(dev, torch.float32)
+                dst.copy_(src.reshape(-1), non_blocking=True)
+                src.record_stream(plan.stream)
+            if self._reinit_src[0] is not initial_noise:
+                upload(b["init_noise"], initial_noise)
+            if self._reinit_src[1] is not lpf:
+                upload(b["lpf"], lpf[(0,) * (lpf.dim() - 3)])
+            self._reinit_src = (initial_noise, lpf)
+            _l.check(lib.moca_ddpm_step_f32(None, None, _l.ptr(b["z_T"]), None, None, None, None, None, None, _l.ptr(plan.x_in),
+                                            _l.ptr(b["init_noise"]), _l.ptr(b["coef"]), _l.ptr(b["t_last"]), 1, B, int(b["coef"].shape[0]),
+                                            n // B, 0, 1.0, 1.0, b["flags"], h), "moca_ddpm_step_f32")
+            if z_rand is not None:
+                upload(self.noise, z_rand)
+            else:
+                self._fill_state(b["state"], seed, -2)
+                _l.check(lib.moca_fifo_randn_f32(_l.ptr(b["state"]), _l.ptr(self.noise), n, h), "moca_fifo_randn_f32")
+            _l.check(lib.moca_freq_mix_3d_f32(_l.ptr(b["z_T"]), _l.ptr(self.noise), _l.ptr(b["lpf"]), _l.ptr(plan.x_in), B * Cc, T, H, W,
+                                              _l.ptr(b["ws"]), h), "moca_freq_mix_3d_f32")
+            self._fill_state(self.state, seed, self.it0)
+            self._fill_state(self.enc_state, seed, -1)
+        self.n_iter = self.it0
+
+    @staticmethod
+    def _fill_state(st, seed, it):
+        """`state_block(seed, it)` into the device block `st` by fills on the current stream: no host buffer, nothing to wait for"""
+        for i, v in enumerate((0, it, seed & 0xffffffff, (seed >> 32) & 0xffffffff, 0)):
+            st[i:i + 1].fill_(v - (1 << 32) if v >= 1 << 31 else v)
+
     def reset(self, x, cond, uc, seed=0, features_adapter=None):
-        """start a new trajectory on the same plan: latents x_T, contexts, fps, adapter maps, iteration 0, a new noise stream"""
+        """start a new trajectory on the same plan: latents x_T, contexts, fps, adapter maps, iteration 0, a new noise stream; the
+        engine's own schedule, should `set_schedule` have replaced it"""
         plan, dev = self.plan, self.device
         if (features_adapter is None) != (plan.adapter_in is None):
             raise ValueError("features_adapter goes with an engine built for it")
@@ -511,6 +606,10 @@ class BaseEngine(_StepEngine):
         fps = (16, 16) if self.hybrid else (cond.get("fps", 16), uc.get("fps", 16))
         self._refuse_unequal_fps(fps)
         cc, cu = (context(c).expand(B, -1, -1) for c in (cond, uc))
+        if self._schedule_set:
+            self._write_schedule(*self._built)
+            self.enc_coef, self._schedule_set = self._built_enc, False
+        self._reinit_src = (None, None)
         with plan._enqueue():
             self.state.copy_(state_block(seed))
             self.enc_state.copy_(state_block(seed, -1))          # (no step ever draws at this iteration: steps count up from 0)

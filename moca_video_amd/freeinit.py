@@ -2,7 +2,11 @@
 (:51-70) with its four filter builders (:73-156) on the fp32 HIP kernels of
 csrc/freeinit.hip.  The reference builds each filter with a T*H*W-iteration Python loop on
 every call (funcs.py:95); here it is a closed-form kernel and results are cached per
-(shape, type, n, d_s, d_t, device)."""
+(shape, type, n, d_s, d_t, device).
+
+`freeinit_steps` and `freeinit_reinit` are the two pieces of the FreeInit sampling loop (Wu et al., 2023;
+`fifo.freeinit_ddim_sampling`) that belong to these utilities: the step count of every iteration and the noise
+re-initialisation between two of them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -68,3 +72,26 @@ def freq_mix_3d(x, noise, LPF):
     if original_dtype != torch.float32:
         out = out.to(original_dtype)
     return out
+
+
+def freeinit_steps(ddim_steps, num_iters, use_fast_sampling=False):
+    """the DDIM step count of every FreeInit iteration: `ddim_steps` each, or -- coarse-to-fine `use_fast_sampling` --
+    max(1, int(ddim_steps / num_iters * (k + 1))) for iteration k, and always `ddim_steps` for the last one"""
+    ddim_steps, num_iters = int(ddim_steps), int(num_iters)
+    if num_iters < 1:
+        raise ValueError(f"num_iters = {num_iters}: FreeInit samples at least once")
+    if ddim_steps < 1:
+        raise ValueError(f"ddim_steps = {ddim_steps}")
+    steps = [max(1, int(ddim_steps / num_iters * (k + 1))) if use_fast_sampling else ddim_steps for k in range(num_iters)]
+    steps[-1] = ddim_steps
+    return steps
+
+
+def freeinit_reinit(model, z0, initial_noise, z_rand, LPF):
+    """The noise re-initialisation between two FreeInit iterations: the previous iteration's samples `z0` diffused to the last
+    timestep with the run's INITIAL noise (`DenoiseModel.q_sample`: a `use_scale` model multiplies by scale_arr[t] in the
+    reference's order), its low spatio-temporal frequencies kept and the high ones taken from the fresh noise `z_rand`
+    (`freq_mix_3d`).  Returns fp32 latents of z0's shape (the mix, like the reference's, drops a batch of 1: put back here)."""
+    t = torch.full((z0.shape[0],), model.num_timesteps - 1, dtype=torch.long)
+    z_T = model.q_sample(z0, t, noise=initial_noise)
+    return freq_mix_3d(z_T.float(), z_rand.to(z_T.device), LPF).reshape(z0.shape).contiguous()

@@ -230,6 +230,62 @@ class DDIMSampler(object):
             torch.save(img, f"{latents_dir}/{total_steps}.pt")        # :249-250
         return img, {}
 
+    @torch.no_grad()
+    def sample_freeinit(self, steps, batch_size, shape, LPF, conditioning=None, eta=0., x_T=None, z_rands=None, noises=None,
+                        unconditional_guidance_scale=1., unconditional_conditioning=None, features_adapter=None, return_all=False,
+                        verbose=False):
+        """FreeInit (Wu et al., 2023) over `sample`: len(steps) trajectories of steps[k] DDIM steps (`freeinit.freeinit_steps`; the last
+        is the longest); trajectory 0 starts from the initial noise (`x_T`, else drawn), every later one from the previous samples
+        re-noised to the last timestep with that SAME initial noise and mixed with fresh noise under the low-pass filter `LPF`
+        (`freeinit.freeinit_reinit`).  `z_rands[k-1]` fixes the fresh noise of trajectory k, `noises[k][i]` the draw of its step i.
+
+        Where `sample` runs on the step graph, the whole run stays on ONE cached engine, captured for steps[-1] rows: `reset` at the
+        start, `BaseEngine.set_schedule` where the step count changes (no new capture), `BaseEngine.reinit` between trajectories (latents,
+        initial noise, filter and fresh noise stay on the device), one read-back at the end -- one per trajectory with `return_all`.
+        Elsewhere the same loop is composed on the host from `freeinit_reinit` and host-issued steps.
+        Returns (samples of the last trajectory, the list of every trajectory's samples or None)."""
+        from .freeinit import freeinit_reinit
+        steps = [int(s) for s in steps]
+        if not steps or max(steps) != steps[-1] or min(steps) < 1:
+            raise ValueError(f"steps = {steps}: at least one trajectory, every one of 1 .. steps[-1] steps")
+        if z_rands is not None and len(z_rands) != len(steps) - 1:
+            raise ValueError(f"z_rands holds {len(z_rands)} tensors for {len(steps) - 1} re-initialisations")
+        if noises is not None and len(noises) != len(steps):
+            raise ValueError(f"noises holds {len(noises)} lists for {len(steps)} trajectories")
+        cond, uc, scale = conditioning, unconditional_conditioning, unconditional_guidance_scale
+        self.make_schedule(ddim_num_steps=steps[-1], ddim_eta=eta, verbose=verbose)
+        device = self.model.betas.device
+        initial_noise = torch.randn((batch_size,) + tuple(shape), device=device) if x_T is None else x_T
+        z_rand = lambda k: None if z_rands is None else z_rands[k - 1]
+        noise = lambda k, i: None if noises is None else noises[k][i]
+        new_seed = lambda: int(torch.randint(0, 2 ** 62, (1,)).item())          # the host generator seeds the device streams
+        every = []
+        if self.use_graph and self.share_prefix and BaseEngine.supported(self.model, initial_noise, cond, uc, scale,
+                                                                          features_adapter=features_adapter):
+            eng = self._engine_for(initial_noise, cond, uc, scale, new_seed(), steps[-1], features_adapter=features_adapter)
+            for k, S in enumerate(steps):
+                if S != eng.S - eng.it0:                                          # (the engine's schedule is the sampler's throughout)
+                    self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+                    eng.set_schedule(self)
+                if k > 0:
+                    eng.reinit(initial_noise, LPF, z_rand=z_rand(k), seed=new_seed())
+                for i in range(S):
+                    eng.step(noise=noise(k, i))
+                if return_all:
+                    every.append(eng.latents().to(initial_noise.dtype))
+            x = every[-1] if return_all else eng.latents().to(initial_noise.dtype)
+            return x, (every if return_all else None)
+        unet_kwargs = dict(features_adapter=features_adapter)
+        x = initial_noise
+        for k, S in enumerate(steps):
+            if k > 0:
+                zr = z_rand(k)
+                x = freeinit_reinit(self.model, x, initial_noise, torch.randn_like(initial_noise, dtype=torch.float32) if zr is None else zr, LPF)
+            self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+            x = self._run_steps(x, cond, uc, scale, S, None if noises is None else noises[k], False, **unet_kwargs)
+            every.append(x)
+        return x, (every if return_all else None)
+
     # ---- start from an existing latent: noise it, denoise it ---------------------------------------------------------------
     def encode_tables(self, use_original_steps=False):
         """the two coefficient tables of `stochastic_encode` (ddim.py:655-660) as fp32 host tensors, evaluated as the reference evaluates
