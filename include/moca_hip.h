@@ -223,6 +223,21 @@ int moca_groupnorm_nhwc_f16(const void* x, void* y, const float* gamma, const fl
                             int32_t F, int32_t HW, int32_t C, int32_t frames_per_stat,
                             float eps, int32_t silu, float* ws, void* stream);
 int64_t moca_groupnorm_ws_bytes(int32_t F, int32_t HW, int32_t C);
+/* The kernels moca_groupnorm_nhwc_f16 would run this shape on under the current MOCA_TUNE_GN_SLAB (MOCA_GN_ROUTE_*), or 0 where it
+ * would return MOCA_E_BADARG for the shape: everything the entry does up to, but not including, the launch.                       */
+#define MOCA_GN_ROUTE_STREAM    1   /* gn_partial -> gn_finalize -> gn_apply, grid (F, nchunk), block (C / 8, ppb)               */
+#define MOCA_GN_ROUTE_SLAB2     2   /* gn_slab_kernel<2>: C / 32 even, no multiple of 4                                          */
+#define MOCA_GN_ROUTE_SLAB4     3   /* gn_slab_kernel<4>: C / 32 a multiple of 4, not of 8                                       */
+#define MOCA_GN_ROUTE_SLAB8     4   /* gn_slab_kernel<8>: C / 32 a multiple of 8, slab outside the register kernel's range       */
+#define MOCA_GN_ROUTE_SLABREG1  5   /* gn_slab_reg_kernel<1 .. 4>: 256 .. 4096 16-byte chunks per slab, <CPT> of them per thread */
+#define MOCA_GN_ROUTE_SLABREG2  6
+#define MOCA_GN_ROUTE_SLABREG3  7
+#define MOCA_GN_ROUTE_SLABREG4  8
+int moca_groupnorm_route(int32_t F, int32_t HW, int32_t C, int32_t frames_per_stat);
+/* Pixel chunks per frame of the (F, nchunk) grid that the streaming GroupNorm passes, moca_groupnorm_colsum_f16, moca_groupnorm_gstat_f16,
+ * moca_groupnorm_gstat_cat_f16, moca_concat_channels_gstat_f16 and moca_gstat_accum_f16 share: chunk i covers pixels
+ * [i * pc, min((i + 1) * pc, HW)), pc = ceil(HW / nchunk).  0 for F <= 0 or HW <= 0.                                           */
+int moca_groupnorm_nchunk(int32_t F, int32_t HW);
 /* The same GroupNorm when the producer of x was a moca_gemm_f16 call with MOCA_EP_COLSUM: the statistics pass over x
  * is replaced by a reduction of colsum [F*HW/tile_rows][C][2] (no row tile may straddle two statistics groups:
  * (frames_per_stat * HW) % tile_rows == 0); two launches (finalize, apply)

@@ -453,15 +453,14 @@ __global__ void gstat_accum_kernel(const half_t* __restrict__ x, int64_t* __rest
 template <int VEC>
 __global__ __launch_bounds__(256) void gn_slab_kernel(const half_t* __restrict__ x, half_t* __restrict__ y,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      int R, int C, int cpg, int S, int xcd_map, double inv_count,
+                                                      int R, int C, int cpg, int S, double inv_count,
                                                       float eps, int silu) {
     typedef _Float16 vec_t __attribute__((ext_vector_type(VEC)));
     __shared__ float s_red[2][4];
     __shared__ float s_sc[128], s_sh[128];               // cpg <= 128
     const int tid = threadIdx.x, L = blockIdx.x;
-    int slab, split;
-    if (xcd_map) { const int w = L >> 3; slab = (L & 7) + 8 * (w / S); split = w % S; }   // consecutive ids go round-robin over the 8 XCDs
-    else { slab = L / S; split = L % S; }
+    // consecutive block ids go round-robin over the 8 XCDs: the S blocks of a slab share one (the slab count is a multiple of 32)
+    const int w = L >> 3, slab = (L & 7) + 8 * (w / S), split = w % S;
     const int sg = slab / GN_GROUPS, g = slab % GN_GROUPS;
     const int vpr = cpg / VEC;                            // vectors per row
     const int dr = 256 / vpr, dv = 256 % vpr;             // advancing a flat index by 256 = dr rows + dv vectors
@@ -662,72 +661,109 @@ extern "C" int64_t moca_groupnorm_ws_bytes(int32_t F, int32_t HW, int32_t C) {
     return ((int64_t)F * nchunk * GN_GROUPS * 2 + (int64_t)F * GN_GROUPS * 2) * 4;
 }
 
+namespace {
+
+// Everything moca_groupnorm_nhwc_f16 decides before its first launch: the launch and moca_groupnorm_route() both read it from here.
+struct gn_plan_t {
+    int route;        // MOCA_GN_ROUTE_*, 0 = MOCA_E_BADARG
+    int nchunk, ppb;  // streaming path: grid (F, nchunk), block (C / 8, ppb)
+    int n_slabs, R;   // slab paths: (statistics group, channel group) slabs of R rows
+    int S;            // gn_slab_kernel: blocks per slab
+    int cpt, threads; // gn_slab_reg_kernel: 16-byte chunks per thread, threads per block
+};
+
+gn_plan_t gn_plan(int32_t F, int32_t HW, int32_t C, int32_t frames_per_stat) {
+    gn_plan_t pl = {};
+    if (F <= 0 || HW <= 0 || C <= 0 || C % (8 * 1) || C % GN_GROUPS || frames_per_stat <= 0 || F % frames_per_stat) return pl;
+    const int nch8 = C / 8;
+    if (nch8 > 1024) return pl;
+    pl.ppb = 256 / nch8;
+    if (pl.ppb < 1) pl.ppb = 1;
+    pl.nchunk = gn_nchunk(F, HW);
+    pl.threads = nch8 * pl.ppb;
+    pl.route = MOCA_GN_ROUTE_STREAM;
+    // small tensors: one launch (gn_slab_kernel)
+    const int slab_mode = moca_tuning_get(MOCA_TUNE_GN_SLAB);   // 0: always the streaming path, 2: always the slab path (tests)
+    const int cpg = C / GN_GROUPS;
+    const int64_t bytes = (int64_t)F * HW * C * 2;
+    const int64_t R64 = (int64_t)frames_per_stat * HW;
+    if (slab_mode && cpg % 2 == 0 && cpg <= 128 && R64 < (1 << 24) &&
+        (slab_mode == 2 || bytes <= (8 << 20) || (frames_per_stat == 1 && HW <= 160 && bytes <= (28 << 20)))) {
+        // (measured on the bench workload, profiles/r01_plan_profile_*.txt: the slab kernel's 20..160-byte row segments
+        //  lose to the streaming path's full-row reads as soon as the tensor is more than a few MB)
+        pl.R = (int)R64;
+        pl.n_slabs = (F / frames_per_stat) * GN_GROUPS;
+        {   // slab in registers: <= 4096 chunks of 16 B, rows of >= 160 B ... or many rows
+            const int nchunks = pl.R * (cpg / 8);
+            if (cpg % 8 == 0 && nchunks <= 4096 && nchunks >= 256) {
+                pl.cpt = (nchunks + 1023) / 1024;
+                pl.threads = ((nchunks + pl.cpt - 1) / pl.cpt + 63) / 64 * 64;
+                pl.route = MOCA_GN_ROUTE_SLABREG1 + pl.cpt - 1;
+                return pl;
+            }
+        }
+        int S = 1024 / pl.n_slabs;
+        if (S > 16) S = 16;
+        if (S > pl.R) S = pl.R;
+        if (S < 1) S = 1;
+        pl.S = S;
+        pl.threads = 256;
+        pl.route = cpg % 8 == 0 ? MOCA_GN_ROUTE_SLAB8 : cpg % 4 == 0 ? MOCA_GN_ROUTE_SLAB4 : MOCA_GN_ROUTE_SLAB2;
+    }
+    return pl;
+}
+
+}  // namespace
+
+extern "C" int moca_groupnorm_route(int32_t F, int32_t HW, int32_t C, int32_t frames_per_stat) {
+    return gn_plan(F, HW, C, frames_per_stat).route;
+}
+
+extern "C" int moca_groupnorm_nchunk(int32_t F, int32_t HW) {
+    if (F <= 0 || HW <= 0) return 0;
+    return gn_nchunk(F, HW);
+}
+
 extern "C" int moca_groupnorm_nhwc_f16(const void* x, void* y, const float* gamma, const float* beta,
                                        int32_t F, int32_t HW, int32_t C, int32_t frames_per_stat,
                                        float eps, int32_t silu, float* ws, void* stream) {
     if (!x || !y || !gamma || !beta || !ws) return MOCA_E_BADARG;
-    if (F <= 0 || HW <= 0 || C <= 0 || C % (8 * 1) || C % GN_GROUPS || frames_per_stat <= 0 || F % frames_per_stat) return MOCA_E_BADARG;
-    const int nch8 = C / 8;
-    if (nch8 > 1024) return MOCA_E_BADARG;
-    int ppb = 256 / nch8;
-    if (ppb < 1) ppb = 1;
-    const int nchunk = gn_nchunk(F, HW);
+    const gn_plan_t pl = gn_plan(F, HW, C, frames_per_stat);
+    if (!pl.route) return MOCA_E_BADARG;
+    const int nchunk = pl.nchunk;
     float* partial = ws;
     float* meanrstd = ws + (int64_t)F * nchunk * GN_GROUPS * 2;
     hipStream_t st = moca_stream(stream);
     const double inv_count = 1.0 / ((double)frames_per_stat * HW * (C / GN_GROUPS));
-    {   // small tensors: one launch (gn_slab_kernel)
-        const int slab_mode = moca_tuning_get(MOCA_TUNE_GN_SLAB);   // 0: always the streaming path, 2: always the slab path (tests)
-        const int cpg = C / GN_GROUPS;
-        const int64_t bytes = (int64_t)F * HW * C * 2;
-        const int64_t R64 = (int64_t)frames_per_stat * HW;
-        if (slab_mode && cpg % 2 == 0 && cpg <= 128 && R64 < (1 << 24) &&
-            (slab_mode == 2 || bytes <= (8 << 20) || (frames_per_stat == 1 && HW <= 160 && bytes <= (28 << 20)))) {
-            // (measured on the bench workload, profiles/r01_plan_profile_*.txt: the slab kernel's 20..160-byte row segments
-            //  lose to the streaming path's full-row reads as soon as the tensor is more than a few MB)
-            const int R = (int)R64;
-            const int n_slabs = (F / frames_per_stat) * GN_GROUPS;
-            {   // slab in registers: <= 4096 chunks of 16 B, rows of >= 160 B ... or many rows
-                const int nchunks = R * (cpg / 8);
-                if (cpg % 8 == 0 && nchunks <= 4096 && nchunks >= 256) {
-                    const int cpt = (nchunks + 1023) / 1024;
-                    const int thr = ((nchunks + cpt - 1) / cpt + 63) / 64 * 64;
-                    const half_t* xi = reinterpret_cast<const half_t*>(x);
-                    half_t* yo = reinterpret_cast<half_t*>(y);
-#define MOCA_SLABREG(CPT) hipLaunchKernelGGL(gn_slab_reg_kernel<CPT>, dim3(n_slabs), dim3(thr), 0, st, xi, yo, gamma, beta, R, C, cpg, inv_count, eps, silu)
-                    if (cpt == 1) MOCA_SLABREG(1); else if (cpt == 2) MOCA_SLABREG(2); else if (cpt == 3) MOCA_SLABREG(3); else MOCA_SLABREG(4);
+    const half_t* xi = reinterpret_cast<const half_t*>(x);
+    half_t* yo = reinterpret_cast<half_t*>(y);
+    const int cpg = C / GN_GROUPS;
+    if (pl.route >= MOCA_GN_ROUTE_SLABREG1 && pl.route <= MOCA_GN_ROUTE_SLABREG4) {
+#define MOCA_SLABREG(CPT) hipLaunchKernelGGL(gn_slab_reg_kernel<CPT>, dim3(pl.n_slabs), dim3(pl.threads), 0, st, xi, yo, gamma, beta, pl.R, C, cpg, inv_count, eps, silu)
+        if (pl.cpt == 1) MOCA_SLABREG(1); else if (pl.cpt == 2) MOCA_SLABREG(2); else if (pl.cpt == 3) MOCA_SLABREG(3); else MOCA_SLABREG(4);
 #undef MOCA_SLABREG
-                    MOCA_CHECK_LAUNCH();
-                    return MOCA_OK;
-                }
-            }
-            int S = 1024 / n_slabs;
-            if (S > 16) S = 16;
-            if (S > R) S = R;
-            if (S < 1) S = 1;
-            const int xcd_map = (n_slabs % 8 == 0) ? 1 : 0;
-            const dim3 g1(n_slabs * S), b1(256);
-            const half_t* xi = reinterpret_cast<const half_t*>(x);
-            half_t* yo = reinterpret_cast<half_t*>(y);
-            if (cpg % 8 == 0)
-                hipLaunchKernelGGL(gn_slab_kernel<8>, g1, b1, 0, st, xi, yo, gamma, beta, R, C, cpg, S, xcd_map, inv_count, eps, silu);
-            else if (cpg % 4 == 0)
-                hipLaunchKernelGGL(gn_slab_kernel<4>, g1, b1, 0, st, xi, yo, gamma, beta, R, C, cpg, S, xcd_map, inv_count, eps, silu);
-            else
-                hipLaunchKernelGGL(gn_slab_kernel<2>, g1, b1, 0, st, xi, yo, gamma, beta, R, C, cpg, S, xcd_map, inv_count, eps, silu);
-            MOCA_CHECK_LAUNCH();
-            return MOCA_OK;
-        }
+        MOCA_CHECK_LAUNCH();
+        return MOCA_OK;
     }
-    const dim3 grid(F, nchunk), block(nch8, ppb);
-    const size_t lds = (size_t)ppb * C * 2 * sizeof(float);
-    hipLaunchKernelGGL(gn_partial_kernel, grid, block, lds, st, reinterpret_cast<const half_t*>(x), partial, HW, C, nchunk);
+    if (pl.route != MOCA_GN_ROUTE_STREAM) {
+        const dim3 g1(pl.n_slabs * pl.S), b1(256);
+        if (pl.route == MOCA_GN_ROUTE_SLAB8)
+            hipLaunchKernelGGL(gn_slab_kernel<8>, g1, b1, 0, st, xi, yo, gamma, beta, pl.R, C, cpg, pl.S, inv_count, eps, silu);
+        else if (pl.route == MOCA_GN_ROUTE_SLAB4)
+            hipLaunchKernelGGL(gn_slab_kernel<4>, g1, b1, 0, st, xi, yo, gamma, beta, pl.R, C, cpg, pl.S, inv_count, eps, silu);
+        else
+            hipLaunchKernelGGL(gn_slab_kernel<2>, g1, b1, 0, st, xi, yo, gamma, beta, pl.R, C, cpg, pl.S, inv_count, eps, silu);
+        MOCA_CHECK_LAUNCH();
+        return MOCA_OK;
+    }
+    const dim3 grid(F, nchunk), block(C / 8, pl.ppb);
+    const size_t lds = (size_t)pl.ppb * C * 2 * sizeof(float);
+    hipLaunchKernelGGL(gn_partial_kernel, grid, block, lds, st, xi, partial, HW, C, nchunk);
     MOCA_CHECK_LAUNCH();
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(F / frames_per_stat, GN_GROUPS), dim3(FIN_T), 0, st, partial, meanrstd,
                        frames_per_stat, nchunk, inv_count, eps);
     MOCA_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_apply_kernel, grid, block, 0, st, reinterpret_cast<const half_t*>(x), reinterpret_cast<half_t*>(y),
-                       gamma, beta, meanrstd, HW, C, nchunk, frames_per_stat, silu);
+    hipLaunchKernelGGL(gn_apply_kernel, grid, block, 0, st, xi, yo, gamma, beta, meanrstd, HW, C, nchunk, frames_per_stat, silu);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }

@@ -28,6 +28,8 @@ MOCA_TUNE_GEMM_WS = 10
 MOCA_DDPM_X0, MOCA_DDPM_CLIP, MOCA_DDPM_SCALE, MOCA_DDPM_MASK_C0 = 1, 2, 4, 8
 (MOCA_ROUTE_SMALL64, MOCA_ROUTE_SMALL128, MOCA_ROUTE_GLDS128, MOCA_ROUTE_GLDS160, MOCA_ROUTE_G4, MOCA_ROUTE_W80, MOCA_ROUTE_W80W,
  MOCA_ROUTE_SQ256, MOCA_ROUTE_G4P, MOCA_ROUTE_SQP, MOCA_ROUTE_TATTN, MOCA_ROUTE_WS) = range(1, 13)
+(MOCA_GN_ROUTE_STREAM, MOCA_GN_ROUTE_SLAB2, MOCA_GN_ROUTE_SLAB4, MOCA_GN_ROUTE_SLAB8, MOCA_GN_ROUTE_SLABREG1, MOCA_GN_ROUTE_SLABREG2,
+ MOCA_GN_ROUTE_SLABREG3, MOCA_GN_ROUTE_SLABREG4) = range(1, 9)
 
 _ERR = {0: "ok", -1: "bad argument (shape/alignment contract)", -2: "HIP launch/runtime error",
         -3: "no gfx950 device", -4: "graph capture/replay failed"}
@@ -100,6 +102,8 @@ SIGNATURES = {
     "moca_groupnorm_colsum_f16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),
     "moca_groupnorm_nhwc_f16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]),
     "moca_groupnorm_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "moca_groupnorm_route": (C.c_int, [_i32, _i32, _i32, _i32]),
+    "moca_groupnorm_nchunk": (C.c_int, [_i32, _i32]),
     "moca_groupnorm_gstat_f16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "moca_memset_zero": (C.c_int, [_vp, _i64, _vp]),
     "moca_concat_channels_gstat_f16": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),

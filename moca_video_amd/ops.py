@@ -322,6 +322,16 @@ def groupnorm(x, y, gamma, beta, *, F, HW, Cn, frames_per_stat, eps, silu, ws):
     return y
 
 
+def groupnorm_route(F, HW, Cn, frames_per_stat):
+    """the kernels groupnorm() would run this shape on under the current MOCA_TUNE_GN_SLAB (lib.MOCA_GN_ROUTE_*), 0 if it would refuse it"""
+    return int(_l.load().moca_groupnorm_route(F, HW, Cn, frames_per_stat))
+
+
+def groupnorm_nchunk(F, HW):
+    """pixel chunks per frame of the (F, nchunk) grid of the streaming GroupNorm, gstat, concat and accum kernels"""
+    return int(_l.load().moca_groupnorm_nchunk(F, HW))
+
+
 def groupnorm_colsum(x, y, gamma, beta, colsum, *, tile_rows, F, HW, Cn, frames_per_stat, eps, silu, ws):
     _l.check(_l.load().moca_groupnorm_colsum_f16(_l.ptr(x), _l.ptr(y), _l.ptr(gamma), _l.ptr(beta), _l.ptr(colsum), tile_rows, F, HW, Cn,
                                                  frames_per_stat, eps, 1 if silu else 0, _l.ptr(ws), _st()),

@@ -565,6 +565,7 @@ MUTANTS = {
 # ----------------------------------------------------------------------------------------------------------------- ledger
 # every entry point of lib.SIGNATURES: the GPU tests ("module::test") that launch it and check what it computed, or why none does
 _S = "test_small_kernels_gpu::"
+N_ = "test_norm_edges_gpu::"
 LEDGER = {
     "moca_gemm_f16": ["test_gemm_edges_gpu::test_index_probe", "test_gemm_edges_gpu::test_geometry_random_operands", "test_kernels_gpu::test_gemm_linear"],
     "moca_gemm_colsum_rows": ["test_gemm_edges_gpu::test_statistics_at_m_tail", "test_kernels_gpu::test_gemm_colsum_feeds_groupnorm"],
@@ -576,17 +577,19 @@ LEDGER = {
     "moca_gemm_wgroup_ok": ["test_gemm_edges_gpu::test_wgroup_never_on_persistent_kernels", "test_kernels_gpu::test_gemm_groupnorm_folded_into_per_group_weights"],
     "moca_gemm_route": ["test_gemm_edges_gpu::test_wgroup_never_on_persistent_kernels"],
     "moca_groupnorm_fold_weights_f16": ["test_groupnorm_gpu::test_gemm_groupnorm_fold_constant_group_and_poison",
-                                        "test_kernels_gpu::test_gemm_groupnorm_folded_into_per_group_weights"],
+                                        "test_kernels_gpu::test_gemm_groupnorm_folded_into_per_group_weights", N_ + "test_fold_weights_edges"],
     "moca_gemm_splitk_groupnorm_ok": ["test_groupnorm_gpu::test_gemm_splitk_groupnorm_large_group_mean"],
     "moca_gemm_splitk_groupnorm_f16": ["test_groupnorm_gpu::test_gemm_splitk_groupnorm_large_group_mean", "test_kernels_gpu::test_gemm_splitk_groupnorm"],
-    "moca_groupnorm_gstat_cat_f16": ["test_groupnorm_gpu::test_groupnorm_from_gstat_accum_and_concat", "test_kernels_gpu::test_groupnorm_virtual_cat"],
-    "moca_gstat_accum_f16": ["test_groupnorm_gpu::test_groupnorm_from_gstat_accum_and_concat"],
-    "moca_groupnorm_colsum_f16": ["test_groupnorm_gpu::test_groupnorm_from_gemm_column_sums_and_tiled_gstat", "test_kernels_gpu::test_gemm_colsum_feeds_groupnorm"],
-    "moca_groupnorm_nhwc_f16": ["test_groupnorm_gpu::test_groupnorm_large_group_mean", "test_kernels_gpu::test_groupnorm"],
-    "moca_groupnorm_ws_bytes": ["test_groupnorm_gpu::test_groupnorm_large_group_mean", "test_kernels_gpu::test_groupnorm"],
-    "moca_groupnorm_gstat_f16": ["test_groupnorm_gpu::test_groupnorm_from_320_gstat", "test_kernels_gpu::test_groupnorm_gstat_rejects_misaligned_affine_parameters"],
+    "moca_groupnorm_gstat_cat_f16": ["test_groupnorm_gpu::test_groupnorm_from_gstat_accum_and_concat", "test_kernels_gpu::test_groupnorm_virtual_cat", N_ + "test_spike_probe", N_ + "test_streaming_store_variants"],
+    "moca_gstat_accum_f16": ["test_groupnorm_gpu::test_groupnorm_from_gstat_accum_and_concat", N_ + "test_spike_probe", N_ + "test_accumulators_exact"],
+    "moca_groupnorm_colsum_f16": ["test_groupnorm_gpu::test_groupnorm_from_gemm_column_sums_and_tiled_gstat", "test_kernels_gpu::test_gemm_colsum_feeds_groupnorm", N_ + "test_spike_probe"],
+    "moca_groupnorm_nhwc_f16": ["test_groupnorm_gpu::test_groupnorm_large_group_mean", "test_kernels_gpu::test_groupnorm", N_ + "test_spike_probe", N_ + "test_surroundings"],
+    "moca_groupnorm_ws_bytes": ["test_groupnorm_gpu::test_groupnorm_large_group_mean", "test_kernels_gpu::test_groupnorm", N_ + "test_surroundings"],
+    "moca_groupnorm_route": [N_ + "test_spike_probe"],        # host query: asserted before every standalone launch, which then must be right
+    "moca_groupnorm_nchunk": [N_ + "test_spike_probe", N_ + "test_streaming_store_variants"],   # host query: places the probes of every chunked kernel
+    "moca_groupnorm_gstat_f16": ["test_groupnorm_gpu::test_groupnorm_from_320_gstat", "test_kernels_gpu::test_groupnorm_gstat_rejects_misaligned_affine_parameters", N_ + "test_spike_probe", N_ + "test_streaming_store_variants"],
     "moca_memset_zero": [_S + "test_memset_zero"],
-    "moca_concat_channels_gstat_f16": ["test_groupnorm_gpu::test_groupnorm_from_gstat_accum_and_concat", "test_kernels_gpu::test_concat_with_groupnorm_statistics"],
+    "moca_concat_channels_gstat_f16": ["test_groupnorm_gpu::test_groupnorm_from_gstat_accum_and_concat", "test_kernels_gpu::test_concat_with_groupnorm_statistics", N_ + "test_accumulators_exact", N_ + "test_streaming_store_variants"],
     "moca_layernorm_f16": [_S + "test_layernorm", _S + "test_layernorm_gamma_zero", "test_kernels_gpu::test_layernorm"],
     "moca_attention_f16": ["test_kernels_gpu::test_attention", "test_attention_edges_gpu::test_logit_regimes"],
     "moca_attention_ip_f16": ["test_i2v_gpu::test_attention_ip_segment_maxima_differ", "test_i2v_gpu::test_attention_ip_without_image_tokens_is_attention"],

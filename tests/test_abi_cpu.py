@@ -81,6 +81,12 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert l.moca_set_tuning(99, 1) == -1 and l.moca_set_tuning(lib.MOCA_TUNE_GEMM_G4, 1) == 1
     assert l.moca_gemm_splitk_ws_bytes(640, 1280, 4) == 4 * 640 * 1280 * 4
     assert l.moca_groupnorm_ws_bytes(16, 2560, 320) > 0
+    # host queries of the GroupNorm dispatch: the default rule on three shapes, 0 for what moca_groupnorm_nhwc_f16 refuses
+    assert l.moca_groupnorm_route(4, 100, 320, 1) == lib.MOCA_GN_ROUTE_SLAB2 and l.moca_groupnorm_route(16, 40, 1280, 16) == lib.MOCA_GN_ROUTE_SLABREG4
+    assert l.moca_groupnorm_route(16, 2560, 320, 1) == lib.MOCA_GN_ROUTE_STREAM
+    assert l.moca_groupnorm_route(4, 100, 48, 1) == 0 and l.moca_groupnorm_route(4, 100, 320, 3) == 0 and l.moca_groupnorm_route(0, 100, 320, 1) == 0
+    assert l.moca_groupnorm_nchunk(4, 100) == 13 and l.moca_groupnorm_nchunk(16, 2560) == 128 and l.moca_groupnorm_nchunk(1, 3) == 1
+    assert l.moca_groupnorm_nchunk(0, 100) == 0 and l.moca_groupnorm_nchunk(4, 0) == 0
     with pytest.raises(lib.MocaHipError):
         lib.check(-1, "x")
     # attention entries: the checks follow the widest access of the kernels on each operand (include/moca_hip.h).  Every call below
