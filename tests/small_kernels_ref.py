@@ -566,6 +566,7 @@ MUTANTS = {
 # every entry point of lib.SIGNATURES: the GPU tests ("module::test") that launch it and check what it computed, or why none does
 _S = "test_small_kernels_gpu::"
 N_ = "test_norm_edges_gpu::"
+K_ = "test_step_kernels_gpu::"
 LEDGER = {
     "moca_gemm_f16": ["test_gemm_edges_gpu::test_index_probe", "test_gemm_edges_gpu::test_geometry_random_operands", "test_kernels_gpu::test_gemm_linear"],
     "moca_gemm_colsum_rows": ["test_gemm_edges_gpu::test_statistics_at_m_tail", "test_kernels_gpu::test_gemm_colsum_feeds_groupnorm"],
@@ -615,20 +616,20 @@ LEDGER = {
     "moca_cfg_combine_f32": [_S + "test_cfg_combine", "test_loops_gpu::test_fifo_step_windows_equals_per_window_kernel"],
     "moca_ddim_update_f32": [_S + "test_ddim_update", "test_sampler_gpu::test_p_sample_ddim_cfg"],
     "moca_q_sample_f32": ["test_v2v_gpu::test_q_sample_kernel_bit_equal_to_torch"],
-    "moca_fifo_ddim_step_f32": ["test_loops_gpu::test_fifo_step_windows_equals_per_window_kernel", "test_sampler_gpu::test_ddim_step_moca"],
-    "moca_fifo_randn_f32": ["test_loops_gpu::test_fifo_randn_kernel_is_philox_box_muller"],
-    "moca_fifo_gather_windows_f32": ["test_loops_gpu::test_fifo_graph_iteration_vs_reference_golden_masks"],
-    "moca_fifo_step_windows_f32": ["test_loops_gpu::test_fifo_step_windows_equals_per_window_kernel"],
-    "moca_sam_select_masks_f32": ["test_loops_gpu::test_sam_select_kernel_equals_host_bookkeeping"],
-    "moca_fifo_advance_f32": ["test_loops_gpu::test_fifo_step_windows_equals_per_window_kernel"],
-    "moca_fifo_prepare_queue_f32": ["test_sampler_gpu::test_fifo_queue"],
-    "moca_base_set_timestep": ["test_loops_gpu::test_base_step_graph_equals_p_sample_ddim"],
-    "moca_base_ddim_step_f32": ["test_loops_gpu::test_base_step_graph_equals_p_sample_ddim"],
+    "moca_fifo_ddim_step_f32": ["test_loops_gpu::test_fifo_step_windows_equals_per_window_kernel", "test_sampler_gpu::test_ddim_step_moca", K_ + "test_moca_step"],
+    "moca_fifo_randn_f32": ["test_loops_gpu::test_fifo_randn_kernel_is_philox_box_muller", K_ + "test_randn"],
+    "moca_fifo_gather_windows_f32": ["test_loops_gpu::test_fifo_graph_iteration_vs_reference_golden_masks", K_ + "test_gather_windows"],
+    "moca_fifo_step_windows_f32": ["test_loops_gpu::test_fifo_step_windows_equals_per_window_kernel", K_ + "test_step_windows"],
+    "moca_sam_select_masks_f32": ["test_loops_gpu::test_sam_select_kernel_equals_host_bookkeeping", K_ + "test_sam_select_scripted"],
+    "moca_fifo_advance_f32": ["test_loops_gpu::test_fifo_step_windows_equals_per_window_kernel", K_ + "test_advance"],
+    "moca_fifo_prepare_queue_f32": ["test_sampler_gpu::test_fifo_queue", K_ + "test_prepare_queue"],
+    "moca_base_set_timestep": ["test_loops_gpu::test_base_step_graph_equals_p_sample_ddim", K_ + "test_base_set_timestep"],
+    "moca_base_ddim_step_f32": ["test_loops_gpu::test_base_step_graph_equals_p_sample_ddim", K_ + "test_base_step"],
     "moca_ddpm_step_f32": ["test_ddpm_gpu::test_ddpm_step_kernel_bit_equal_to_torch"],
-    "moca_mask_frame_sums_f32": ["test_loops_gpu::test_fifo_step_windows_equals_per_window_kernel"],
+    "moca_mask_frame_sums_f32": ["test_loops_gpu::test_fifo_step_windows_equals_per_window_kernel", K_ + "test_mask_frame_sums", K_ + "test_moca_step"],
     "moca_freq_mix_3d_f32": [_S + "test_freq_mix_3d", "test_sampler_gpu::test_freeinit_filters_and_mix"],
     "moca_freq_mix_ws_bytes": [_S + "test_freq_mix_3d"],
-    "moca_freq_filter_f32": ["test_sampler_gpu::test_freeinit_filters_and_mix"],
+    "moca_freq_filter_f32": ["test_sampler_gpu::test_freeinit_filters_and_mix", K_ + "test_freq_filter"],
 }
 LEDGER_EXEMPT = {
     "moca_gemm_splitk_ws_bytes": "size query, no launch: its value is asserted on the CPU (test_gemm_edges_cpu::test_normalise_splits, test_abi_cpu)",

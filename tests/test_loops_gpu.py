@@ -504,31 +504,7 @@ def test_fifo_graph_device_noise_is_reproducible(dm):
 
 
 # ---------------------------------------------------------------------------------------------------------------- kernels
-def _philox_numpy(seed, it, n):
-    """Philox4x32-10, counter (i, i >> 32, iteration, 0x4d6f4341), key = seed words; Box-Muller like csrc/fifo.hip"""
-    n4 = (n + 3) // 4
-    c = np.zeros((n4, 4), np.uint64)
-    c[:, 0] = np.arange(n4) & 0xffffffff
-    c[:, 1] = np.arange(n4) >> 32
-    c[:, 2] = it
-    c[:, 3] = 0x4d6f4341
-    k0, k1 = np.uint64(seed & 0xffffffff), np.uint64((seed >> 32) & 0xffffffff)
-    M = np.uint64(0xffffffff)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[:, 0]
-        p1 = np.uint64(0xCD9E8D57) * c[:, 2]
-        n0 = ((p1 >> np.uint64(32)) ^ c[:, 1] ^ k0) & M
-        n2 = ((p0 >> np.uint64(32)) ^ c[:, 3] ^ k1) & M
-        c = np.stack([n0, p1 & M, n2, p0 & M], 1)
-        k0 = (k0 + np.uint64(0x9E3779B9)) & M
-        k1 = (k1 + np.uint64(0xBB67AE85)) & M
-    u = (c.astype(np.float32) + np.float32(0.5)) * np.float32(2.3283064365386963e-10)
-    out = np.zeros((n4, 4), np.float64)
-    for h in range(2):
-        r = np.sqrt(-2.0 * np.log(u[:, 2 * h].astype(np.float64)))
-        th = 6.283185307179586 * u[:, 2 * h + 1].astype(np.float64)
-        out[:, 2 * h], out[:, 2 * h + 1] = r * np.cos(th), r * np.sin(th)
-    return out.reshape(-1)[:n]
+from step_kernels_ref import philox_numpy as _philox_numpy  # noqa: E402  (the Philox + Box-Muller restatement lives with the other step references)
 
 
 def test_fifo_randn_kernel_is_philox_box_muller():
