@@ -567,16 +567,22 @@ MUTANTS = {
 _S = "test_small_kernels_gpu::"
 N_ = "test_norm_edges_gpu::"
 K_ = "test_step_kernels_gpu::"
+F_ = "test_gemm_fused_gpu::"
 LEDGER = {
-    "moca_gemm_f16": ["test_gemm_edges_gpu::test_index_probe", "test_gemm_edges_gpu::test_geometry_random_operands", "test_kernels_gpu::test_gemm_linear"],
+    "moca_gemm_f16": ["test_gemm_edges_gpu::test_index_probe", "test_gemm_edges_gpu::test_geometry_random_operands", "test_kernels_gpu::test_gemm_linear",
+                      F_ + "test_ln_store_loop", F_ + "test_fold_tiled_routes", F_ + "test_fold_persistent_routes", F_ + "test_two_source_a", F_ + "test_wgroup",
+                      F_ + "test_gstat_virtual_concat", F_ + "test_tattn"],
     "moca_gemm_colsum_rows": ["test_gemm_edges_gpu::test_statistics_at_m_tail", "test_kernels_gpu::test_gemm_colsum_feeds_groupnorm"],
-    "moca_gemm_ln_ok": ["test_kernels_gpu::test_gemm_layernorm_epilogue"],
+    "moca_gemm_ln_ok": ["test_kernels_gpu::test_gemm_layernorm_epilogue", F_ + "test_ln_store_loop"],
     "moca_gemm_rowsum_cols": ["test_gemm_edges_gpu::test_epilogue_matrix", "test_kernels_gpu::test_gemm_rowsum_feeds_lnfold"],
-    "moca_gemm_lnfold_ok": ["test_kernels_gpu::test_gemm_rowsum_feeds_lnfold", "test_kernels_gpu::test_gemm_lnfold_offset_rows"],
-    "moca_gemm_tattn_ok": ["test_kernels_gpu::test_gemm_temporal_attention_fused"],
-    "moca_gemm_cat_ok": ["test_kernels_gpu::test_gemm_two_source_a"],
-    "moca_gemm_wgroup_ok": ["test_gemm_edges_gpu::test_wgroup_never_on_persistent_kernels", "test_kernels_gpu::test_gemm_groupnorm_folded_into_per_group_weights"],
-    "moca_gemm_route": ["test_gemm_edges_gpu::test_wgroup_never_on_persistent_kernels"],
+    "moca_gemm_lnfold_ok": ["test_kernels_gpu::test_gemm_rowsum_feeds_lnfold", "test_kernels_gpu::test_gemm_lnfold_offset_rows",
+                            F_ + "test_fold_tiled_routes", F_ + "test_fold_persistent_routes", F_ + "test_tattn"],
+    "moca_gemm_tattn_ok": ["test_kernels_gpu::test_gemm_temporal_attention_fused", F_ + "test_tattn", F_ + "test_tattn_refused"],
+    "moca_gemm_cat_ok": ["test_kernels_gpu::test_gemm_two_source_a", F_ + "test_two_source_a"],
+    "moca_gemm_wgroup_ok": ["test_gemm_edges_gpu::test_wgroup_never_on_persistent_kernels", "test_kernels_gpu::test_gemm_groupnorm_folded_into_per_group_weights",
+                            F_ + "test_wgroup", F_ + "test_ln_store_loop"],
+    "moca_gemm_route": ["test_gemm_edges_gpu::test_wgroup_never_on_persistent_kernels", F_ + "test_ln_store_loop", F_ + "test_fold_tiled_routes",
+                        F_ + "test_two_source_a", F_ + "test_tattn"],
     "moca_groupnorm_fold_weights_f16": ["test_groupnorm_gpu::test_gemm_groupnorm_fold_constant_group_and_poison",
                                         "test_kernels_gpu::test_gemm_groupnorm_folded_into_per_group_weights", N_ + "test_fold_weights_edges"],
     "moca_gemm_splitk_groupnorm_ok": ["test_groupnorm_gpu::test_gemm_splitk_groupnorm_large_group_mean"],
