@@ -7,11 +7,12 @@ Public surface mirrors the reference interfaces for this path only:
                        q_sample, predict_start_from_noise, q_posterior, p_mean_variance, p_sample, p_sample_loop with masked
                        inpainting (ddpm3d.py:136-153,212-225,412-420,565-657; moca_video_amd.ddpm)
   DDIMSampler          lvdm/models/samplers/ddim.py (make_schedule, p_sample_ddim, unet, ddim_step, fifo_onestep,
-                       stochastic_encode, decode, ddim_inversion)
+                       stochastic_encode, decode, ddim_inversion; encode: deterministic DDIM inversion, upstream's third method)
   freq_mix_3d, get_freq_filter   utils/freeinit_utils.py
   prepare_latents, shift_latents, fifo_ddim_sampling, base_ddim_sampling   scripts/evaluation/funcs.py
   fifo_ddim_sampling_multiprompts   funcs.py:375-468 (one video, prompts switched inside the one-graph loop)
   v2v_ddim_sampling    DDIMSampler.stochastic_encode + decode (ddim.py:652-692): noise a clip's latents, denoise under a new prompt
+  v2v_invert_sampling  DDIMSampler.encode + decode: the clip's own DDIM inversion in place of the noising, then denoise under a new prompt
   freeinit_ddim_sampling   FreeInit (Wu et al., 2023) over base_ddim_sampling: re-noise with the initial noise, freq_mix_3d, sample again
   load_multiprompts, run_multiprompts  its prompt file and driver (moca_video_amd.io)
   instantiate_from_config       utils/utils.py:27-42
@@ -35,9 +36,9 @@ from .tokenizer import SimpleTokenizer  # noqa: E402
 from .image_proj import ImageProjModel, Resampler  # noqa: E402
 from .clip_vision import FrozenOpenCLIPImageEmbedder, FrozenOpenCLIPImageEmbedderV2  # noqa: E402
 from .wrapper import LatentVisualDiffusion  # noqa: E402
-from .fifo import fifo_ddim_sampling_multiprompts, freeinit_ddim_sampling, v2v_ddim_sampling  # noqa: E402
+from .fifo import fifo_ddim_sampling_multiprompts, freeinit_ddim_sampling, v2v_ddim_sampling, v2v_invert_sampling  # noqa: E402
 from .io import load_multiprompts, run_multiprompts  # noqa: E402
 
 __all__ = ["UNetModel", "DiffusionWrapper", "DenoiseModel", "AutoencoderKL", "FrozenOpenCLIPEmbedder", "SimpleTokenizer", "ImageProjModel", "Resampler",
            "FrozenOpenCLIPImageEmbedder", "FrozenOpenCLIPImageEmbedderV2", "LatentVisualDiffusion", "instantiate_from_config",
-           "load_unet_config", "fifo_ddim_sampling_multiprompts", "v2v_ddim_sampling", "freeinit_ddim_sampling", "load_multiprompts", "run_multiprompts"]
+           "load_unet_config", "fifo_ddim_sampling_multiprompts", "v2v_ddim_sampling", "v2v_invert_sampling", "freeinit_ddim_sampling", "load_multiprompts", "run_multiprompts"]

@@ -173,6 +173,37 @@ def v2v_ddim_sampling(model, cond, latents=None, frames=None, ddim_steps=50, t_s
     return images, sampler, samples
 
 
+def v2v_invert_sampling(model, cond, latents=None, frames=None, ddim_steps=50, t_start=25, ddim_eta=0.0, cfg_scale=1.0, uc_emb=None,
+                        src_cond=None, src_cfg_scale=1.0, noises=None, use_graph=True):
+    """`v2v_ddim_sampling` with the clip taken to schedule index `t_start` by its own deterministic DDIM inversion
+    (`DDIMSampler.encode`) instead of by noise (`stochastic_encode`): t_start inversion steps under `src_cond` (default: `cond`) with
+    guidance `src_cfg_scale` -- the state is then at level ddim_alphas[t_start - 1], where `decode(x, cond, t_start)` starts -- and
+    t_start denoising steps under `cond` with guidance `cfg_scale`.  With src_cond = cond, eta 0 (the default here) and no guidance
+    the two halves are a round trip; a new `cond` edits the clip and keeps what the inversion kept of it.  There is no encode draw, so
+    no `noise=` (and `t_start` may be the whole schedule); `noises[i]` fixes the draw of decode step i when eta > 0.  Its own function
+    beside `v2v_ddim_sampling`, whose parameter list is pinned.  Returns (images, sampler, samples) like `base_ddim_sampling`."""
+    if (latents is None) == (frames is None):
+        raise ValueError("v2v_invert_sampling wants exactly one of latents= and frames=")
+    if not 1 <= int(t_start) <= int(ddim_steps):
+        raise ValueError(f"t_start = {t_start}: the clip is inverted over t_start steps and decoded over as many, "
+                         f"so 1 <= t_start <= ddim_steps = {int(ddim_steps)}")
+    t_start = int(t_start)
+    if frames is not None:
+        latents = model.encode_first_stage_2DAE(frames.to(model.device))
+    x0 = latents.to(model.device)
+    sampler = DDIMSampler(model)
+    sampler.use_graph = use_graph
+    sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_eta=ddim_eta, verbose=False)
+    src_cond = cond if src_cond is None else src_cond
+    x_enc, _ = sampler.encode(x0, src_cond, t_start, unconditional_guidance_scale=src_cfg_scale,
+                              unconditional_conditioning=base_uncond(model, src_cond, x0.shape[0], src_cfg_scale, uc_emb))
+    uc = base_uncond(model, cond, x0.shape[0], cfg_scale, uc_emb)
+    samples = sampler.decode(x_enc, cond, t_start, unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc, noises=noises)
+    sampler.release()
+    images = model.decode_first_stage_2DAE(samples) if getattr(model, "first_stage_model", None) is not None else None
+    return images, sampler, samples
+
+
 def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg_scale=1.0, uc_emb=None,
                        latents=None, latents_dir=None, conditioned_image=None, masks=None, gamma=0.5, emit=None,
                        n_iterations=None, batch_windows=True, noises=None, shift_noises=None, decode=False, decode_batch=8,

@@ -64,6 +64,23 @@ def ddim_coef(sampler, index):
     return np.sqrt(a_t), np.sqrt(a_prev), sig, f32(sampler.ddim_sqrt_one_minus_alphas[index]), np.sqrt(f32(1.) - a_prev - sig * sig)
 
 
+def invert_coef(sampler, i):
+    """the coefficients of DDIM inversion step `i`, which takes the latents from schedule level ddim_alphas_prev[i] (a_cur) up to
+    ddim_alphas[i] (a_next) with the model evaluated at ddim_timesteps[i]: the tail of p_sample_ddim (ddim.py:328-357) with its tables
+    swapped and sigma 0.  -> the five of `ddim_coef` in its order -- sqrt(a_cur), sqrt(a_next), 0, sqrt(1 - a_cur), sqrt(1 - a_next) --
+    and the two scales (s_cur, s_next) = (ddim_scale_arr_prev[i], ddim_scale_arr[i]), 1 without `use_scale`: a row of the 8-wide step
+    table.  fp32 scalars with correctly rounded roots like `ddim_coef`'s; sqrt(1 - a_cur) is built the way the reference builds
+    `ddim_sqrt_one_minus_alphas` (ddim.py:88), as np.sqrt(1. - ddim_alphas_prev), and then taken as fp32."""
+    f32 = np.float32
+    a_cur, a_next = f32(sampler.ddim_alphas_prev[i]), f32(sampler.ddim_alphas[i])
+    s1m_cur = f32(np.sqrt(1. - np.asarray(sampler.ddim_alphas_prev))[i])
+    if bool(sampler.use_scale):
+        s_cur, s_next = f32(sampler.ddim_scale_arr_prev[i]), f32(sampler.ddim_scale_arr[i])
+    else:
+        s_cur = s_next = f32(1)
+    return np.sqrt(a_cur), np.sqrt(a_next), f32(0), s1m_cur, np.sqrt(f32(1.) - a_next), s_cur, s_next
+
+
 def mask_kind(mask, shape):
     """how the DDPM step kernel reads `mask` against latents of `shape`: "c0" (one channel, channel stride 0) or "full"
     (`img_orig * mask`, ddpm3d.py:648, broadcasts: everything else is expanded to the latents' shape)"""
@@ -657,6 +674,112 @@ class BaseEngine(_StepEngine):
         with self._step():
             if noise is not None:
                 self._fix_noise((self.noise, noise))
+
+    def last_pred_x0(self):
+        return self._copy(self.pred_x0, self.shape)
+
+
+class InvertEngine(_StepEngine):
+    """One step of deterministic DDIM inversion (`DDIMSampler.encode`) as ONE hipGraph: [timestep rows of step i] + the UNet forward +
+    [guidance + update in place, i += 1] -- `BaseEngine`'s two launches around the forward, `moca_base_set_timestep` and
+    `moca_base_ddim_step_f32`, on another table.  Step i takes the latents in the plan's input buffer from schedule level
+    ddim_alphas_prev[i] to ddim_alphas[i] with the model evaluated at ddim_timesteps[i] (`invert_coef`).  What differs from `BaseEngine`:
+
+      * nothing is drawn: no `moca_fifo_randn_f32` launch.  The step kernel's noise operand is a buffer of zeros that nothing ever
+        writes (sigma is 0 in every row, and 0 x an uninitialised NaN would not be 0);
+      * the captured kernels read table row S - 1 - iter, so inversion row i is STORED at row S - 1 - i and the iteration counter counts
+        up as everywhere.  The rows ascend from the clean end of the schedule, so one engine over the whole schedule serves every
+        t_enc <= S: `encode(x0, c, t_enc)` is t_enc steps after a `reset` (no truncated tables as `decode` needs them);
+      * without guidance (`uc` None or scale 1: the normal case of inversion) the plan holds the B latents and ONE context segment and
+        the step kernel's eps_u is NULL; with guidance 2 B rows with the shared prefix, as `BaseEngine`."""
+
+    @staticmethod
+    def supported(model, x, cond, uc=None, scale=1.0):
+        """`BaseEngine.supported`'s conditions on the model, the device, the keys and the fps for 'crossattn' models, without its
+        `scale != 1.0` clause (the hybrid keys stay on the host-issued path)"""
+        if not isinstance(unet_of(model), UNetModel) or conditioning_key(model) != "crossattn" or not x.is_cuda:
+            return False
+        if not isinstance(cond, dict) or "c_crossattn" not in cond or not set(cond.keys()) <= {"c_crossattn", "fps"}:
+            return False
+        if uc is None or scale == 1.0:
+            return x.shape[0] <= 64
+        return isinstance(uc, dict) and set(uc.keys()) == set(cond.keys()) and 2 * x.shape[0] <= 64 and \
+            same_fps([cond.get("fps", 16), uc.get("fps", 16)])      # (the shared prefix adds ONE fps embedding)
+
+    def __init__(self, model, sampler, x, cond, uc=None, cfg_scale=1.0, keep_pred_x0=False):
+        self.unet = unet = model.model.diffusion_model
+        dev = x.device
+        self.device = dev
+        if unet._packed is None:
+            unet._pack()
+        B, Cc, T, H, W = x.shape
+        self.shape = (B, Cc, T, H, W)
+        self.S = S = len(sampler.ddim_timesteps)
+        self.guided = uc is not None and cfg_scale != 1.0
+        n_ctx = lambda c: sum(int(k.shape[1]) for k in c["c_crossattn"])
+        if self.guided:
+            self.plan = plan = _Plan(unet, 2 * B, T, H, W, ((B, n_ctx(cond)), (B, n_ctx(uc))), torch.float32, dev, shared_x=True)
+        else:
+            self.plan = plan = _Plan(unet, B, T, H, W, n_ctx(cond), torch.float32, dev)
+        self.coef, self.t_table = (t.to(dev) for t in self._schedule_tables(sampler))
+        self.state = torch.zeros(8, dtype=torch.int32, device=dev)
+        n = x.numel()
+        self.zeros = torch.zeros(n, dtype=torch.float32, device=dev)           # the noise operand: sigma = 0 times finite zeros
+        self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev) if keep_pred_x0 else None
+        self.reset(x, cond, uc)
+        lib = _l.load()
+        eps = plan.out.reshape(plan.B, -1)
+        st_ = _l.ptr(self.state)
+        use_scale = 1 if sampler.use_scale else 0
+        S_ = lambda: C.c_void_p(ops.current_stream())
+
+        def pre():
+            _l.check(lib.moca_base_set_timestep(st_, _l.ptr(self.t_table), S, _l.ptr(plan.t_rows), plan.t_rows.numel(), S_()), "moca_base_set_timestep")
+
+        def post():
+            _l.check(lib.moca_base_ddim_step_f32(st_, _l.ptr(plan.x_in), _l.ptr(eps[:B]), _l.ptr(eps[B:]) if self.guided else None,
+                                                 _l.ptr(self.zeros), _l.ptr(self.pred_x0), _l.ptr(self.coef), S, float(cfg_scale), use_scale, n,
+                                                 S_()), "moca_base_ddim_step_f32")
+        self._wrap_plan(pre, post)
+
+    @staticmethod
+    def _schedule_tables(sampler):
+        """host tables over the sampler's whole schedule, inversion row i at table row S - 1 - i: coef [S][8] = {the seven of
+        `invert_coef`, unused} and the int64 timesteps"""
+        S = len(sampler.ddim_timesteps)
+        coef = np.zeros((S, 8), np.float32)
+        t_table = np.zeros((S,), np.int64)
+        for i in range(S):
+            coef[S - 1 - i, :7] = invert_coef(sampler, i)
+            t_table[S - 1 - i] = sampler.ddim_timesteps[i]
+        return torch.from_numpy(coef), torch.from_numpy(t_table)
+
+    def reset(self, x, cond, uc=None):
+        """start the inversion of another clip on the same plan and the same captured graph: latents x0, contexts, fps, step 0"""
+        plan, dev = self.plan, self.device
+        B, T = self.shape[0], self.shape[2]
+        if tuple(x.shape) != self.shape:
+            raise ValueError(f"x {tuple(x.shape)} does not match the engine's latents {self.shape}")
+        branches = [cond] + ([uc] if self.guided else [])
+        self._refuse_unequal_fps([c.get("fps", 16) for c in branches])
+        with plan._enqueue():
+            self.state.copy_(state_block(0))
+            plan.x_in.copy_(x.to(torch.float32))
+            plan.fps_rows.copy_(torch.cat([fps_rows(c.get("fps", 16), B, T, dev) for c in branches]))
+            plan.set_context([context(c).expand(B, -1, -1) for c in branches])
+        self.sync_to()
+        self.n_iter = 0
+
+    def step(self):
+        """one inversion step (enqueued, not synchronised)"""
+        if self.n_iter >= self.S:
+            raise ValueError(f"the schedule has {self.S} levels: step {self.n_iter} would wrap around to the first")
+        with self._step():
+            pass
+
+    def t_rows(self):
+        """the timestep rows the UNet of the last step was given (a copy)"""
+        return self._copy(self.plan.t_rows)
 
     def last_pred_x0(self):
         return self._copy(self.pred_x0, self.shape)

@@ -1,8 +1,8 @@
 """MI355X host-side mirror of `lvdm.models.samplers.ddim.DDIMSampler` for the hot path:
 `make_schedule` (ddim.py:62-106), `sample`/`ddim_sampling` (:109-252), `p_sample_ddim`
 (:274-359), `fifo_onestep` (:255-271), `unet` (:362-374), the MoCA `ddim_step`
-(:377-649) and the start-from-a-video path: `stochastic_encode` (:652-671), `decode` (:674-692) and
-`ddim_inversion` (:972-1032).  All per-element arithmetic runs in the fp32 HIP kernels of
+(:377-649) and the start-from-a-video path: `stochastic_encode` (:652-671), `decode` (:674-692),
+`ddim_inversion` (:972-1032) and `encode`, the deterministic DDIM inversion that upstream's sampler keeps beside them.  All per-element arithmetic runs in the fp32 HIP kernels of
 csrc/sampler.hip; only O(steps) scalar schedule math stays on the host (numpy, as in
 the reference).
 
@@ -25,7 +25,7 @@ import torch
 from . import lib as _l
 from . import ops
 from .conditioning import _f32c, check_schedule_index, cond_image_rows, guidance_eps
-from .fifo_graph import BaseEngine, EngineCache, ddim_coef
+from .fifo_graph import BaseEngine, EngineCache, InvertEngine, ddim_coef, invert_coef
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
@@ -332,20 +332,120 @@ class DDIMSampler(object):
         return self._run_steps(x_latent, cond, unconditional_conditioning, unconditional_guidance_scale, n_steps, noises,
                                self.use_graph if use_graph is None else use_graph)
 
+    def _invert_engine_for(self, x0, cond, uc, scale):
+        """the cached step graph of `encode` (fifo_graph.InvertEngine) reset to the clip `x0`; built when the key changes.  It shares the
+        one-entry cache of `sample` / `decode`, whose keys are tuples that start with a shape: the leading "invert" keeps the two apart.
+        The engine covers the whole schedule, so t_enc is no part of the key."""
+        guided = uc is not None and scale != 1.0
+        n_ctx = lambda c: sum(int(k.shape[1]) for k in c["c_crossattn"])
+        key = ("invert", tuple(x0.shape), n_ctx(cond), n_ctx(uc) if guided else None, float(scale) if guided else 1.0,
+               self.ddim_timesteps.tobytes(), bool(self.use_scale), str(x0.device))
+        return self._engines.get(key, lambda: InvertEngine(self.model, self, x0, cond, uc if guided else None, scale),
+                                 lambda eng: eng.reset(x0, cond, uc if guided else None))
+
+    def invert_update(self, x, e_t, i, zeros=None):
+        """inversion step `i` of `encode` on the host-issued path: `moca_ddim_update_f32` with the scalars of `invert_coef` -- the
+        alphas and scales swapped, sigma 0 -- and a noise operand of zeros (`zeros`, else made here).  Draws nothing.
+        Returns (x_next, pred_x0)."""
+        x, e_t = _f32c(x), _f32c(e_t)
+        zeros = torch.zeros_like(x) if zeros is None else zeros
+        x_next, pred_x0 = torch.empty_like(x), torch.empty_like(x)
+        f32 = np.float32
+        _, _, sigma, s1m_cur, _, s_cur, s_next = invert_coef(self, i)
+        _l.check(_l.load().moca_ddim_update_f32(
+            _l.ptr(x), _l.ptr(e_t), _l.ptr(zeros), _l.ptr(x_next), _l.ptr(pred_x0),
+            f32(self.ddim_alphas_prev[i]), f32(self.ddim_alphas[i]), sigma, s1m_cur, 1 if self.use_scale else 0, s_cur, s_next,
+            x.numel(), _st()), "moca_ddim_update_f32")
+        return x_next, pred_x0
+
+    def _encode_host(self, x0, c, t_enc, uc, scale, inter=None, callback=None):
+        """the host-issued loop of `encode`: step i evaluates the model at ddim_timesteps[i] (`_cfg_eps`) and updates with the
+        coefficients of level index i (`invert_update`), one zero tensor serving every step as the noise operand"""
+        x = _f32c(x0)
+        zeros = torch.zeros_like(x)
+        for i in range(t_enc):
+            ts = torch.full((x.shape[0],), int(self.ddim_timesteps[i]), device=x.device, dtype=torch.long)
+            e_t = self._cfg_eps(x, ts, c, uc, scale)
+            x, _ = self.invert_update(x, e_t, i, zeros)
+            if inter is not None:
+                inter.append(x)
+            if callback is not None:
+                callback(i)
+        return x
+
+    @torch.no_grad()
+    def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, callback=None, use_graph=None):
+        """Deterministic DDIM inversion, the `encode` of upstream's sampler (same parameters, in its order; `use_graph` is ours, as in
+        `decode`): t_enc steps i = 0 .. t_enc - 1, step i taking the latents from schedule level ddim_alphas_prev[i] to ddim_alphas[i]
+        with the model evaluated at t = ddim_timesteps[i]:
+
+            e       = e_u + g (e_c - e_u)                      (g = 1 or no unconditional conditioning: e = e_c, one UNet call)
+            pred_x0 = (x - sqrt(1 - a_cur) e) / sqrt(a_cur) [/ s_cur]
+            x_next  = sqrt(a_next) [s_next] pred_x0 + sqrt(1 - a_next) e
+
+        -- the tail of p_sample_ddim (ddim.py:328-357) with its tables swapped and sigma 0 (`invert_coef`); without `use_scale` upstream's
+        own formula.  After step i the state is at level ddim_alphas[i], where `decode(x, c, t_start=i + 1)` starts:
+        `decode(encode(x0, c, n)[0], c, n)` at eta 0 is a round trip.  Draws nothing: the host generator is left as it was.
+
+        Returns (x_T, out): out["x_encoded_steps"] = t_enc and, with `return_intermediates`, out["intermediates"] = the t_enc states
+        after each step and out["intermediate_steps"] = their timesteps.  `callback(i)` runs after step i.  Where `use_graph` (default:
+        `self.use_graph`) and `InvertEngine.supported` allow it every step is one hipGraph and the latents stay on the device; else
+        host-issued: `_cfg_eps` and `moca_ddim_update_f32`."""
+        if use_original_steps:
+            raise NotImplementedError("encode(use_original_steps=True): inversion over the 1000 DDPM steps is not built; like "
+                                      "decode(use_original_steps=True) it has no tables to run on here")
+        S = len(self.ddim_timesteps)
+        if isinstance(t_enc, bool) or int(t_enc) != t_enc or not 1 <= int(t_enc) <= S:
+            raise ValueError(f"t_enc = {t_enc}: inversion takes 1 .. {S} steps of the {S}-step schedule")
+        t_enc = int(t_enc)
+        if not (torch.is_tensor(x0) and x0.is_cuda):
+            raise ValueError("encode runs on the GPU: x0 must be a cuda tensor")
+        uc, scale = unconditional_conditioning, unconditional_guidance_scale
+        guided = uc is not None and scale != 1.0
+        use_graph = self.use_graph if use_graph is None else use_graph
+        inter = [] if return_intermediates else None
+        if use_graph and (self.share_prefix or not guided) and InvertEngine.supported(self.model, x0, c, uc, scale):
+            eng = self._invert_engine_for(x0, c, uc, scale)
+            for i in range(t_enc):
+                eng.step()
+                if inter is not None:
+                    inter.append(eng.latents().to(x0.dtype))
+                if callback is not None:
+                    callback(i)
+            x = inter[-1] if inter is not None else eng.latents().to(x0.dtype)
+        else:
+            x = self._encode_host(x0, c, t_enc, uc, scale, inter, callback).to(x0.dtype)
+        out = {"x_encoded_steps": t_enc}
+        if inter is not None:
+            out.update(intermediates=inter, intermediate_steps=[int(t) for t in self.ddim_timesteps[:t_enc]])
+        return x, out
+
     @staticmethod
     def inversion_frame_index(num_inference_steps, n_frames):
         """ddim.py:1014: the input frame behind output frame i, idx(i) = max(0, i - (num_inference_steps - n_frames))"""
         return [max(0, i - (num_inference_steps - n_frames)) for i in range(num_inference_steps)]
 
     @torch.no_grad()
-    def ddim_inversion(self, frames, num_inference_steps, eta=1.0, latents_dir=None, noises=None, anchor_noise=None):
-        """ddim.py:972-1032.  Despite the name a NOISING queue: output frame i = ddim_alphas[i] ** 0.5 * z[:, :, idx(i)] +
+    def ddim_inversion(self, frames, num_inference_steps, eta=1.0, latents_dir=None, noises=None, anchor_noise=None,
+                       deterministic=False, cond=None, unconditional_guidance_scale=1.0, unconditional_conditioning=None):
+        """ddim.py:972-1032.  Noising by default, inversion with `deterministic=True`.  By default, despite the name, a NOISING queue: output frame i = ddim_alphas[i] ** 0.5 * z[:, :, idx(i)] +
         (1 - ddim_alphas[i]) ** 0.5 * randn with z = encode_first_stage_2DAE(frames) (RGBA cut to RGB, a 3-channel z padded with a zero
         fourth channel) and idx(i) = max(0, i - (num_inference_steps - T)) -- `prepare_latents` (funcs.py:53-79) without lookahead over
         this sampler's tables, one `moca_fifo_prepare_queue_f32` launch.  `eta` is unused, as upstream; needs a prior `make_schedule`.
-        `noises[i]` [B,C,1,h,w] fix the per-frame draws, `anchor_noise` [B,4,T,h,w] the VAE posterior draw."""
+        `noises[i]` [B,C,1,h,w] fix the per-frame draws, `anchor_noise` [B,4,T,h,w] the VAE posterior draw.
+
+        `deterministic=True`: the queue of the same shape taken from the clip's own DDIM inversion instead of from noise -- output frame
+        i = X_i[:, :, idx(i)] with X_i the state after inversion step i of the whole clip z, i.e. z at level ddim_alphas[i], from
+        `encode(z, cond, num_inference_steps, return_intermediates=True)` under `cond` (required) and the optional guidance pair.  Nothing
+        is drawn but the VAE posterior sample, so `noises=` is refused.  The result goes into `fifo_ddim_sampling(latents=...)` like the
+        noised queue; lookahead copies stay the caller's business."""
         if frames.dim() != 5:
             raise ValueError(f"Expected frames to have 5 dimensions [B, C, T, H, W], got {frames.dim()}")
+        if deterministic and cond is None:
+            raise ValueError("ddim_inversion(deterministic=True) evaluates the model: it needs cond=")
+        if deterministic and noises is not None:
+            raise ValueError("ddim_inversion(deterministic=True) draws no per-frame noise: noises= has nothing to fix")
         if frames.shape[1] == 4:                                      # RGBA -> RGB (:990-991)
             frames = frames[:, :3]
         kw = {} if anchor_noise is None else {"noise": anchor_noise}
@@ -362,7 +462,12 @@ class DDIMSampler(object):
         fidx = self.inversion_frame_index(N, frames.shape[2])
         if max(fidx) >= z.shape[2]:
             raise IndexError(f"frame index {max(fidx)} is out of range for {z.shape[2]} latent frames (ddim.py:1017)")
-        out = noise_queue(z, alphas, fidx, noises)
+        if deterministic:
+            _, enc = self.encode(z, cond, N, return_intermediates=True, unconditional_guidance_scale=unconditional_guidance_scale,
+                                 unconditional_conditioning=unconditional_conditioning)
+            out = torch.stack([x[:, :, j] for x, j in zip(enc["intermediates"], fidx)], dim=2)
+        else:
+            out = noise_queue(z, alphas, fidx, noises)
         if latents_dir is not None:
             for i in range(N):
                 torch.save(out[:, :, [i]].clone(), f"{latents_dir}/step_{i}.pt")          # :1024-1025
