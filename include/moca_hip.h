@@ -200,6 +200,7 @@ int moca_gemm_cat_ok(const moca_gemm_params* p);
 #define MOCA_ROUTE_SQP       10  /* persistent 256 x 256 kernel                                             */
 #define MOCA_ROUTE_TATTN     11  /* staggered kernel, 320 x 192 tiles, temporal attention in the epilogue   */
 #define MOCA_ROUTE_WS        12  /* weight-stationary streaming kernel (320 -> 320 linears)                 */
+#define MOCA_ROUTE_W80H      13  /* staggered kernel, 320 x 160 tiles, LDS-resident halo tile (3 x 3 convs) */
 int moca_gemm_route(const moca_gemm_params* p);
 /* The split-K reduce of a MOCA_EP_SLABS call AND the GroupNorm(32)(+SiLU) that consumes its output (openaimodel3d.py:149-153,173-178,
  * 252-263 at the 5 x 8-latent level, where every conv runs split-K) in one launch: x = fp16(sum of slabs + bias + row add + residual)
@@ -627,7 +628,8 @@ int moca_event_destroy(void* ev);
 #define MOCA_TUNE_SQP_WALK   8   /* tile walk of the persistent 256 x 256 kernel: 0 strided over the XCD's blocks, 1 a contiguous range per block           */
 #define MOCA_TUNE_SLAB_F16   9   /* split-K partial slabs of the 256-row kernel: 0 fp32, 1 fp16 (A/B of VERDICT r4 #5's candidate; changes results within the fp16 tolerance) */
 #define MOCA_TUNE_GEMM_WS    10  /* weight-stationary streaming kernel of the 320 -> 320 linears (gemm_ws.hip): 0 never, 1 where it applies                */
-#define MOCA_TUNE_COUNT      11
+#define MOCA_TUNE_CONV_HALO  11  /* LDS-resident halo tile for the stride-1 3 x 3 convs of the 320 x 160 staggered kernel (gemm_halo.hip): 0 the per-tap gather, 1 the halo where it applies */
+#define MOCA_TUNE_COUNT      12
 int moca_set_tuning(int32_t knob, int32_t value);
 /* Measurement aid, no counterpart in the reference (tools/clock_in_step.py): `blocks` one-wave blocks each record `nsamples` pairs
  * (shader-cycle counter, 100 MHz real-time counter) ~8 us apart into buf = u64 [blocks][nsamples][2] (device memory, zeroed by the

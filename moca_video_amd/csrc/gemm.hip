@@ -505,7 +505,7 @@ enum Route : int {
     R_NONE = 0,                                       // refused
     R_SMALL64 = MOCA_ROUTE_SMALL64, R_SMALL128 = MOCA_ROUTE_SMALL128, R_GLDS128 = MOCA_ROUTE_GLDS128, R_GLDS160 = MOCA_ROUTE_GLDS160,
     R_G4 = MOCA_ROUTE_G4, R_W80 = MOCA_ROUTE_W80, R_W80W = MOCA_ROUTE_W80W, R_SQ256 = MOCA_ROUTE_SQ256, R_G4P = MOCA_ROUTE_G4P,
-    R_SQP = MOCA_ROUTE_SQP, R_TATTN = MOCA_ROUTE_TATTN, R_WS = MOCA_ROUTE_WS,
+    R_SQP = MOCA_ROUTE_SQP, R_TATTN = MOCA_ROUTE_TATTN, R_WS = MOCA_ROUTE_WS, R_W80H = MOCA_ROUTE_W80H,
 };
 
 void normalise_splits(moca_gemm_params& p) {
@@ -537,6 +537,15 @@ bool persistent_ok(const moca_gemm_params& p, int BN, int blocks) {
     return ((p.M + 255) / 256) * (p.N / BN) >= blocks;
 }
 
+// which calls the halo form of the 320 x 160 staggered kernel (gemm_halo.hip) can run: stride-1 3 x 3 convs whose 320-row tiles are
+// whole image rows of one frame, image rows of 64 or 32 pixels (the row pitch is a compile-time immediate of its fragment reads),
+// 32-channel slices, no split-K (a second A source and per-row-group weights exist for linears only).
+bool halo_ok(const moca_gemm_params& p) {
+    if (p.a_mode != MOCA_A_CONV3X3 || p.stride != 1 || p.up || p.up_phase || p.nopad_lo || p.splits != 1 || p.a2 || p.wgroup_rows) return false;
+    if ((p.inW != 64 && p.inW != 32) || p.inH % (320 / p.inW) || p.C % 32 || p.C > 8192) return false;
+    return !(p.flags & ~(MOCA_EP_COLSUM | MOCA_EP_GSTAT | MOCA_EP_ROWSUM));
+}
+
 // The kernel family a (validated, split-normalised) call WITH ITS FLAGS runs on.  The only reader of the MOCA_TUNE_GEMM_* kernel-choice
 // knobs and the only place that knows the order.  (MOCA_TUNE_GEMM_MF32 and MOCA_TUNE_SQP_WALK pick a variant inside a launcher.)
 Route route_of(const moca_gemm_params& p) {
@@ -561,8 +570,11 @@ Route route_of(const moca_gemm_params& p) {
     // 160 and whose 320-row tiles fill the chip.  (MOCA_TUNE_GEMM_W80: 0 never, 2 drops the tile-count rule -- tests.)
     const int w80_mode = moca_tuning_get(MOCA_TUNE_GEMM_W80);
     const int tiles320 = ((p.M + 319) / 320) * (p.N / 160);
+    // MOCA_TUNE_CONV_HALO = 1: the convs halo_ok() names run on the halo form of that kernel (which also takes C % 64 == 32)
+    const bool halo = moca_tuning_get(MOCA_TUNE_CONV_HALO) && halo_ok(p);
     if (w80_mode && p.N % 160 == 0 && !(p.flags & (MOCA_EP_GEGLU | MOCA_EP_OUT_F32 | MOCA_FORCE_SMALL_TILE)) && p.M > 160 &&
-        (tiles320 * p.splits >= 200 || w80_mode == 2) && fast_gather(p) && buffer_addressable(p)) {
+        (tiles320 * p.splits >= 200 || w80_mode == 2) && (fast_gather(p) || halo) && buffer_addressable(p)) {
+        if (halo) return R_W80H;
         // which form of the staggered kernel.  The 160 x 320 tiling is required by the LayerNorm store loop and taken by every
         // N % 320 == 0 contraction: A is fetched once per 320 columns instead of once per 160 (linears: 37 vs 38 us at M = 81920,
         // N = K = 320; 99 vs 103 at K = 1280; 182 vs 193 / 366 vs 384 at M = 327680; N = 640: 22.7 vs 25.1).
@@ -613,6 +625,7 @@ RouteInfo route_info(Route r) {
         case R_GLDS160: return {256, 160, GLDS};
         case R_G4: return {256, 128, MOCA_EP_GEGLU | MOCA_EP_LNFOLD | CAN_SPLITK | CAN_UP_PHASE};
         case R_W80: return {320, 160, W80};
+        case R_W80H: return {320, 160, EP_STATS | MOCA_EP_ROWSUM};  // halo_ok(): no split-K, one source, no row groups
         case R_W80W: return {160, 320, W80 | MOCA_EP_LN};           // a block owns whole rows of N = 320: the LayerNorm store loop
         case R_SQ256: return {256, 256, MOCA_EP_GEGLU | MOCA_EP_LNFOLD | CAN_SPLITK};
         case R_G4P: return {256, 128, MOCA_EP_GEGLU | MOCA_EP_LNFOLD};
@@ -769,6 +782,7 @@ int launch_route(Route r, const moca_gemm_params& p, hipStream_t st) {
         case R_G4P: return moca_gemm_g4p_launch(p, st);
         case R_W80: return moca_gemm_w80s_launch(0, p, st);
         case R_W80W: return moca_gemm_w80s_launch(1, p, st);
+        case R_W80H: return moca_gemm_w80h_launch(p, st);
         case R_SQ256: return moca_gemm_w80s_launch(2, p, st);
         case R_G4: return moca_gemm_g4_launch(p, st);
         case R_GLDS128: return moca_gemm_glds_launch(128, p, st);

@@ -7,3 +7,4 @@
 #include "gemm.hip"
 #include "gemm_tiled.hip"
 #include "gemm_persistent.hip"
+#include "gemm_halo.hip"

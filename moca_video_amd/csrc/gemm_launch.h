@@ -10,6 +10,8 @@ int moca_gemm_glds_launch(int bn, const moca_gemm_params& p, hipStream_t st);
 int moca_gemm_g4_launch(const moca_gemm_params& p, hipStream_t st);
 // and the staggered kernel, shape = its SHAPE (0: 320 x 160, 1: 160 x 320, 2: 256 x 256, 3: 320 x 192 with temporal attention)
 int moca_gemm_w80s_launch(int shape, const moca_gemm_params& p, hipStream_t st);
+// gemm_halo.hip: the 320 x 160 staggered kernel with the LDS-resident halo tile (stride-1 3 x 3 convs, inW = 64 or 32)
+int moca_gemm_w80h_launch(const moca_gemm_params& p, hipStream_t st);
 // gemm_persistent.hip: g4p (g4q under MOCA_TUNE_GEMM_MF32) and sqp
 int moca_gemm_g4p_launch(const moca_gemm_params& p, hipStream_t st);
 int moca_gemm_sqp_launch(const moca_gemm_params& p, hipStream_t st);

@@ -25,9 +25,10 @@ MOCA_EP_ROWSUM, MOCA_EP_LNFOLD, MOCA_EP_GSTAT, MOCA_EP_TATTN, MOCA_EP_SLABS = 64
 MOCA_TUNE_GEMM_W80, MOCA_TUNE_GEMM_G4, MOCA_TUNE_GEMM_SQ256, MOCA_TUNE_GEMM_WIDE, MOCA_TUNE_GN_SLAB, MOCA_TUNE_GEMM_G4P, MOCA_TUNE_GEMM_MF32, MOCA_TUNE_GEMM_SQP, MOCA_TUNE_SQP_WALK = 0, 1, 2, 3, 4, 5, 6, 7, 8
 MOCA_TUNE_SLAB_F16 = 9
 MOCA_TUNE_GEMM_WS = 10
+MOCA_TUNE_CONV_HALO = 11
 MOCA_DDPM_X0, MOCA_DDPM_CLIP, MOCA_DDPM_SCALE, MOCA_DDPM_MASK_C0 = 1, 2, 4, 8
 (MOCA_ROUTE_SMALL64, MOCA_ROUTE_SMALL128, MOCA_ROUTE_GLDS128, MOCA_ROUTE_GLDS160, MOCA_ROUTE_G4, MOCA_ROUTE_W80, MOCA_ROUTE_W80W,
- MOCA_ROUTE_SQ256, MOCA_ROUTE_G4P, MOCA_ROUTE_SQP, MOCA_ROUTE_TATTN, MOCA_ROUTE_WS) = range(1, 13)
+ MOCA_ROUTE_SQ256, MOCA_ROUTE_G4P, MOCA_ROUTE_SQP, MOCA_ROUTE_TATTN, MOCA_ROUTE_WS, MOCA_ROUTE_W80H) = range(1, 14)
 (MOCA_GN_ROUTE_STREAM, MOCA_GN_ROUTE_SLAB2, MOCA_GN_ROUTE_SLAB4, MOCA_GN_ROUTE_SLAB8, MOCA_GN_ROUTE_SLABREG1, MOCA_GN_ROUTE_SLABREG2,
  MOCA_GN_ROUTE_SLABREG3, MOCA_GN_ROUTE_SLABREG4) = range(1, 9)
 

@@ -68,7 +68,7 @@ def classify(n):
     for pat, k in (("clock_sampler", None), ("attention_v4", "attention_v4 (spatial self-attention, long keys)"), ("attention_short", "attention_short (77-token context)"),
                    ("temporal_attention", "temporal attention"), ("gemm_sqp", "gemm_sqp (GEGLU, persistent 256x256)"), ("gemm_g4", "gemm_g4 / g4p (GEGLU 256x128)"),
                    ("gemm_ws", "gemm_ws (weight-stationary 320->320)"), ("gemm_glds", "gemm_glds (256-row, 1280-channel levels)"), ("splitk", "split-K reduce (+GroupNorm)"),
-                   ("gemm_f16", "gemm_small")):
+                   ("gemm_f16", "gemm_small"), ("gemm_w80h", "gemm_w80h 320x160 (3x3 convs, halo tile)")):
         if pat in n:
             return k
     if "gemm_w80s" in n:
