@@ -77,13 +77,7 @@ def launch_ddpm_step(coef, t, *, B, per, x=None, out=None, eps_c=None, eps_u=Non
                                           int(mask_inner), float(cfg_scale), float(temperature), int(flags), st), "moca_ddpm_step_f32")
 
 
-def engine_key(shape, cond, uc, timesteps, scale, mask, clip_denoised, parameterization, device):
-    """what a cached `DdpmEngine` is good for: latent shape, context lengths (None: no guidance branch), the number of steps, the
-    guidance scale, whether and how a mask is read, clip_denoised, the parameterization and the device"""
-    ctx_len = lambda c: None if c is None else sum(int(t.shape[1]) for t in c["c_crossattn"])
-    kind = None if mask is None else mask_kind(mask, shape)
-    return (tuple(int(s) for s in shape), ctx_len(cond), ctx_len(uc), int(timesteps), float(scale), kind, bool(clip_denoised),
-            str(parameterization), str(device))
+engine_key = DdpmEngine.key          # (the name the key had when it lived here)
 
 
 def _table_property(name):
@@ -244,7 +238,7 @@ class DdpmMixin:
 
     # ---- the loop --------------------------------------------------------------------------------------------------------------
     def _ddpm_engine_for(self, img, cond, uc, scale, timesteps, mask, x0, seed):
-        key = engine_key(img.shape, cond, uc, timesteps, scale, mask, self.clip_denoised, self.parameterization, img.device)
+        key = DdpmEngine.key(img.shape, cond, uc, timesteps, scale, mask, self.clip_denoised, self.parameterization, img.device)
         return self._ddpm_engines.get(key, lambda: DdpmEngine(self, img, cond, uc, scale, timesteps, mask=mask, x0=x0, seed=seed),
                                       lambda eng: eng.reset(img, cond, uc, seed, mask=mask, x0=x0))
 

@@ -16,7 +16,14 @@ iteration needs lives on the device and depends on nothing the host has to look 
     mask shift are five more launches on the same stream.
 
 The recorded sequence (gather + ~640 UNet launches + tail) is run eagerly once, captured on the second iteration and replayed
-as one `hipGraphLaunch` from then on; the host never synchronises inside the loop."""
+as one `hipGraphLaunch` from then on; the host never synchronises inside the loop.
+
+The module's classes: `_StepEngine` (the wrap of a plan's recorded forward into an engine's launches, one enqueue per step, the
+accessors) under all four engines; `FifoEngine`, the loop above; `_TrajectoryEngine` under the three engines that step B latents in the
+plan's input buffer by one schedule-table row per replay -- `BaseEngine` (DDIM sampling), `InvertEngine` (DDIM inversion), `DdpmEngine`
+(`p_sample_loop`) -- which owns the one- or two-branch plan, the reset core, the launches around the forward and the shared clauses
+of `supported()`.  Each of the three says beside `supported()` what a built engine is good for (`key`), which is what `EngineCache`
+compares."""
 from __future__ import annotations
 
 import contextlib
@@ -81,22 +88,9 @@ def invert_coef(sampler, i):
     return np.sqrt(a_cur), np.sqrt(a_next), f32(0), s1m_cur, np.sqrt(f32(1.) - a_next), s_cur, s_next
 
 
-def mask_kind(mask, shape):
-    """how the DDPM step kernel reads `mask` against latents of `shape`: "c0" (one channel, channel stride 0) or "full"
-    (`img_orig * mask`, ddpm3d.py:648, broadcasts: everything else is expanded to the latents' shape)"""
-    ms = (1,) * (len(shape) - mask.dim()) + tuple(mask.shape)
-    return "c0" if ms[1] == 1 and shape[1] > 1 else "full"
-
-
-def mask_operand(mask, shape, device):
-    """-> (contiguous fp32 mask as the kernel reads it, kernel flag, elements per mask channel)"""
-    B, Cc = int(shape[0]), int(shape[1])
-    inner = int(np.prod(shape[2:]))
-    m = mask.to(device, torch.float32)
-    m = m.reshape((1,) * (len(shape) - m.dim()) + tuple(m.shape))
-    if mask_kind(mask, shape) == "c0":
-        return m.expand(B, 1, *shape[2:]).contiguous(), _l.MOCA_DDPM_MASK_C0, inner
-    return m.expand(*shape).contiguous(), 0, inner * Cc
+def n_ctx(cond):
+    """the tokens of a cond dict's cross-attention context (`context(cond)`: its `c_crossattn` entries side by side)"""
+    return sum(int(k.shape[1]) for k in cond["c_crossattn"])
 
 
 class EngineCache:
@@ -132,8 +126,16 @@ def state_block(seed, it=0):
 
 
 class _StepEngine:
-    """what the three one-graph engines share: a `_Plan` whose recorded UNet forward is wrapped into the engine's own launches, one
+    """what the four one-graph engines share: a `_Plan` whose recorded UNet forward is wrapped into the engine's own launches, one
     enqueue per step on the plan's stream, accessors that wait for that stream before they copy"""
+
+    def _bind(self, model, x):
+        """the constructor preamble: the model's UNet, packed, and the device of the latents `x` -> (unet, device)"""
+        self.unet = unet = model.model.diffusion_model
+        self.device = x.device
+        if unet._packed is None:
+            unet._pack()
+        return unet, x.device
 
     def _wrap_plan(self, pre, post):
         """a step = pre() + the UNet forward + post(), recorded and captured as one sequence"""
@@ -153,10 +155,6 @@ class _StepEngine:
         for dst, src in pairs:
             dst.copy_(src.reshape(-1).to(self.device, torch.float32))
         self.state[4:5].fill_(1)
-
-    def _refuse_unequal_fps(self, fps):
-        if not same_fps(fps):
-            raise ValueError(f"{type(self).__name__} shares the UNet prefix between the two guidance branches: their fps must be equal")
 
     def sync_to(self, stream=None):
         (stream or torch.cuda.current_stream(self.device)).wait_stream(self.plan.stream)
@@ -196,11 +194,7 @@ class FifoEngine(_StepEngine):
         refuse_long_window(args)
         refuse_image_attention(model)
         refuse_concat(model, cond)
-        self.unet = unet = model.model.diffusion_model
-        dev = latents.device
-        self.device = dev
-        if unet._packed is None:
-            unet._pack()
+        unet, dev = self._bind(model, latents)
         f = args.video_length
         wins = list(fifo_windows(args))
         self.wins, self.nW, self.f = wins, len(wins), f
@@ -432,10 +426,105 @@ class FifoEngine(_StepEngine):
         return v(self.x_prev), v(self.pred_x0)
 
 
-class BaseEngine(_StepEngine):
+class _TrajectoryEngine(_StepEngine):
+    """What `BaseEngine`, `InvertEngine` and `DdpmEngine` share: B latents that live in the plan's input buffer and take one sampler
+    step per replay, the step's schedule row picked by the state block's iteration counter (row S - 1 - iter of `t_table` and of the
+    engine's coefficient table).  With guidance the plan holds 2 B rows -- the conditional and the unconditional branch of the SAME
+    latents, one context segment each, everything before the first cross-attention computed once (`shared_x`) -- else B rows and one
+    segment.  A subclass adds its tables and buffers, the step kernel (`_wrap_step`) and what its `reset` writes beside the core
+    (`_restart`)."""
+    pred_x0 = None
+
+    @staticmethod
+    def _supports(model, x, branches):
+        """the clauses every `supported()` starts with: our UNet, latents on the device, every branch a dict with the conditional
+        branch's keys, at most 64 rows in the plan"""
+        return (isinstance(unet_of(model), UNetModel) and x.is_cuda and all(isinstance(c, dict) for c in branches)
+                and all(set(c.keys()) == set(branches[0].keys()) for c in branches[1:]) and len(branches) * x.shape[0] <= 64)
+
+    @staticmethod
+    def _supports_crossattn(model, branches):
+        """'crossattn' models with `c_crossattn` / `fps` conditioning only, one fps for all branches (the shared prefix adds ONE fps
+        embedding)"""
+        return (conditioning_key(model) == "crossattn" and set(branches[0].keys()) <= {"c_crossattn", "fps"}
+                and same_fps([c.get("fps", 16) for c in branches]))
+
+    def _open(self, model, x, branches, S, pieces=None, features_adapter=None):
+        """the head of every constructor: the preamble, the plan for `branches` ([cond] or [cond, uc]) -- with the `c_concat` channel
+        counts `pieces` and buffers for the `features_adapter` maps where given -- and the state block -> (device, elements of x)"""
+        unet, dev = self._bind(model, x)
+        unet._check_adapter(features_adapter)                # (the list length fails as in UNetModel.forward)
+        B, _, T, H, W = self.shape = tuple(x.shape)
+        self.S, self.guided = S, len(branches) == 2
+        L = tuple((B, n_ctx(c)) for c in branches) if self.guided else n_ctx(branches[0])
+        self.plan = _Plan(unet, len(branches) * B, T, H, W, L, torch.float32, dev, shared_x=self.guided, pieces=pieces,
+                          adapter=None if features_adapter is None else unet.adapter_sites)
+        self.state = torch.zeros(8, dtype=torch.int32, device=dev)
+        return dev, x.numel()
+
+    def _wrap_step(self, draw, step):
+        """the launch sequence of one replay: [timestep rows of table row S - 1 - iter; the Philox draws over the buffer `draw`, None:
+        nothing is drawn] + the UNet forward + [`step(lib, state, eps_c, eps_u, stream)`: the engine's step kernel on the conditional
+        rows of `plan.out` and the unconditional ones, NULL without guidance]"""
+        lib, plan, B = _l.load(), self.plan, self.shape[0]
+        eps = plan.out.reshape((2 if self.guided else 1) * B, -1)
+        st_ = _l.ptr(self.state)
+        S_ = lambda: C.c_void_p(ops.current_stream())
+
+        def pre():
+            _l.check(lib.moca_base_set_timestep(st_, _l.ptr(self.t_table), self.S, _l.ptr(plan.t_rows), plan.t_rows.numel(), S_()), "moca_base_set_timestep")
+            if draw is not None:
+                _l.check(lib.moca_fifo_randn_f32(st_, _l.ptr(draw), draw.numel(), S_()), "moca_fifo_randn_f32")
+
+        def post():
+            step(lib, st_, _l.ptr(eps[:B]), _l.ptr(eps[B:]) if self.guided else None, S_())
+        self._wrap_plan(pre, post)
+
+    def _wrap_ddim_step(self, draw, noise, cfg_scale, use_scale):
+        """`_wrap_step` with `moca_base_ddim_step_f32`, in place on the plan's input buffer, `noise` its noise operand"""
+        plan, n = self.plan, noise.numel()
+        self._wrap_step(draw, lambda lib, st_, eps_c, eps_u, stream: _l.check(lib.moca_base_ddim_step_f32(
+            st_, _l.ptr(plan.x_in), eps_c, eps_u, _l.ptr(noise), _l.ptr(self.pred_x0), _l.ptr(self.coef), self.S, float(cfg_scale),
+            1 if use_scale else 0, n, stream), "moca_base_ddim_step_f32"))
+
+    def _refuse_other_shape(self, x):
+        if tuple(x.shape) != self.shape:
+            raise ValueError(f"x {tuple(x.shape)} does not match the engine's latents {self.shape}")
+
+    @contextlib.contextmanager
+    def _restart(self, x, cond, uc, seed=0, fps=None):
+        """the core of every `reset`, `with self._restart(...):` -- a new trajectory on the same plan and the same captured graph: the
+        state block (iteration 0, the noise stream of `seed`), the latents `x`, the fps rows and the context of every branch (`fps`:
+        one per branch, default the branches' own), all enqueued on the plan's stream; the body, what the engine adds, is enqueued
+        behind them; then the current stream waits for the plan's"""
+        plan, dev = self.plan, self.device
+        B, T = self.shape[0], self.shape[2]
+        branches = [cond, uc] if self.guided else [cond]
+        fps = [c.get("fps", 16) for c in branches] if fps is None else fps
+        if not same_fps(fps):
+            raise ValueError(f"{type(self).__name__} shares the UNet prefix between the two guidance branches: their fps must be equal")
+        ctxs = [context(c).expand(B, -1, -1) for c in branches]
+        with plan._enqueue():
+            self.state.copy_(state_block(seed))
+            plan.x_in.copy_(x.to(torch.float32))
+            plan.fps_rows.copy_(torch.cat([fps_rows(fp, B, T, dev) for fp in fps]))
+            plan.set_context(ctxs)
+            yield
+        self.sync_to()
+        self.n_iter = 0
+
+    def t_rows(self):
+        """the timestep rows the UNet of the last step was given (a copy)"""
+        return self._copy(self.plan.t_rows)
+
+    def last_pred_x0(self):
+        return self._copy(self.pred_x0, self.shape)
+
+
+class BaseEngine(_TrajectoryEngine):
     """One step of base sampling -- `DDIMSampler.ddim_sampling`'s loop body (ddim.py:226-252: two UNet calls on the same latents, guidance,
-    the DDIM update with `use_scale`, fresh noise) -- as ONE hipGraph: [timestep rows of step i] + the shared-prefix UNet forward of
-    the B latents x (conditional, unconditional) + [noise, guidance + update in place, i += 1].  The latents live in the plan's input
+    the DDIM update with `use_scale`, fresh noise) -- as ONE hipGraph: [timestep rows of step i, noise] + the shared-prefix UNet forward
+    of the B latents x (conditional, unconditional) + [guidance + update in place, i += 1].  The latents live in the plan's input
     buffer, the schedule in device tables indexed by the state block's iteration counter; the host only replays.
 
     `n_rows` (default: the whole schedule) builds the tables over the FIRST n_rows schedule rows, so that the S of the captured kernels
@@ -448,8 +537,7 @@ class BaseEngine(_StepEngine):
         unet, key = unet_of(model), conditioning_key(model)
         if features_adapter is not None and key != "crossattn":
             return False                                     # (the host-issued path's wrapper names the refusal)
-        ok = isinstance(unet, UNetModel) and x.is_cuda and isinstance(cond, dict) and isinstance(uc, dict) and scale != 1.0
-        if not ok or set(cond.keys()) != set(uc.keys()) or 2 * x.shape[0] > 64:
+        if scale == 1.0 or not _TrajectoryEngine._supports(model, x, [cond, uc]):
             return False
         if key in ("hybrid", "hybrid-adm-mask"):
             # (the other hybrid keys need c_adm / s: they stay on the host-issued path, which keeps the reference's asserts.)  Both
@@ -465,59 +553,41 @@ class BaseEngine(_StepEngine):
                 p is q or (p.data_ptr() == q.data_ptr() and p.shape == q.shape and p.stride() == q.stride() and p.dtype == q.dtype)
                 for p, q in zip(a, b)))
             return same and set(cond.keys()) <= {"c_crossattn", "fps", "c_concat"}
-        return set(cond.keys()) <= {"c_crossattn", "fps"} and key == "crossattn" and \
-            same_fps([cond.get("fps", 16), uc.get("fps", 16)])      # (the shared prefix adds ONE fps embedding)
+        return _TrajectoryEngine._supports_crossattn(model, [cond, uc])
+
+    @staticmethod
+    def key(sampler, x, cond, uc, cfg_scale, features_adapter=None, n_rows=None):
+        """what an engine built by `BaseEngine(model, sampler, x, cond, uc, cfg_scale, ...)` is good for: everything the plan and the
+        captured launches bake in -- latent shape, context lengths, scale, the schedule's timesteps and sigmas, device, `c_concat`
+        channel counts, adapter map shapes and the table rows (`n_rows` keeps `decode`'s engine and `sample`'s apart)"""
+        return (tuple(x.shape), n_ctx(cond), n_ctx(uc), float(cfg_scale), sampler.ddim_timesteps.tobytes(),
+                np.asarray(sampler.ddim_sigmas).tobytes(), str(x.device), tuple(int(c.shape[1]) for c in cond.get("c_concat") or ()),
+                None if features_adapter is None else tuple(tuple(f.shape) for f in features_adapter),
+                len(sampler.ddim_timesteps) if n_rows is None else int(n_rows))
 
     def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, keep_pred_x0=False, features_adapter=None, n_rows=None):
-        self.unet = unet = model.model.diffusion_model
-        dev = x.device
-        self.device = dev
-        if unet._packed is None:
-            unet._pack()
-        B, Cc, T, H, W = x.shape
-        self.shape = (B, Cc, T, H, W)
         S = len(sampler.ddim_timesteps) if n_rows is None else int(n_rows)
         if not 1 <= S <= len(sampler.ddim_timesteps):
             raise ValueError(f"n_rows = {n_rows}: the schedule has {len(sampler.ddim_timesteps)} rows")
-        self.S = S
-        segs = tuple((B, sum(int(k.shape[1]) for k in c["c_crossattn"])) for c in (cond, uc))
         # hybrid keys: x carries the latent channels only; the c_concat columns of the first conv's input rows are constant over a
-        # trajectory (reset() writes them), the recorded step rewrites the latent columns from plan.x_in; fps is dropped (16)
+        # trajectory (reset() writes them), the recorded step rewrites the latent columns from plan.x_in; fps is dropped (16).
+        # features_adapter: constant over a trajectory like c_concat -- reset() writes the plan's adapter buffers, the recorded step
+        # reads them
         self.hybrid = conditioning_key(model) != "crossattn"
         concat = cond.get("c_concat") if self.hybrid else None
-        pieces = None if concat is None else tuple(int(c.shape[1]) for c in concat)
-        # features_adapter: constant over a trajectory like c_concat -- reset() writes the plan's adapter buffers, the recorded step
-        # reads them; the list length fails as in UNetModel.forward
-        unet._check_adapter(features_adapter)
-        self.plan = plan = _Plan(unet, 2 * B, T, H, W, segs, torch.float32, dev, shared_x=True, pieces=pieces,
-                                 adapter=None if features_adapter is None else unet.adapter_sites)
-        use_scale = bool(sampler.use_scale)
+        dev, n = self._open(model, x, [cond, uc], S, None if concat is None else tuple(int(c.shape[1]) for c in concat), features_adapter)
         self._built = self._schedule_tables(sampler, S)      # host copies: `reset` puts them back after a `set_schedule`
         self.coef, self.t_table = (t.to(dev) for t in self._built)
         self.it0, self._schedule_set = 0, False              # where a trajectory's iteration counter starts (`set_schedule`)
         self.enc_coef = self._built_enc = tuple(c.to(dev) for c in sampler.encode_tables())     # `encode`: the whole schedule's q_sample tables
-        self.state = torch.zeros(8, dtype=torch.int32, device=dev)
         self.enc_state = torch.zeros(8, dtype=torch.int32, device=dev)        # the noise stream of `encode`: same seed, iteration -1
         self.model = model
         self._reinit_bufs = None                             # `reinit` (FreeInit): made by its first call
         self._reinit_src = (None, None)
-        n = x.numel()
         self.noise = torch.zeros(n, dtype=torch.float32, device=dev)
         self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev) if keep_pred_x0 else None
         self.reset(x, cond, uc, seed, features_adapter=features_adapter)
-        lib = _l.load()
-        eps = plan.out.reshape(2 * B, -1)
-        st_ = _l.ptr(self.state)
-        S_ = lambda: C.c_void_p(ops.current_stream())
-
-        def pre():
-            _l.check(lib.moca_base_set_timestep(st_, _l.ptr(self.t_table), S, _l.ptr(plan.t_rows), plan.t_rows.numel(), S_()), "moca_base_set_timestep")
-            _l.check(lib.moca_fifo_randn_f32(st_, _l.ptr(self.noise), n, S_()), "moca_fifo_randn_f32")
-
-        def post():
-            _l.check(lib.moca_base_ddim_step_f32(st_, _l.ptr(plan.x_in), _l.ptr(eps[:B]), _l.ptr(eps[B:]), _l.ptr(self.noise), _l.ptr(self.pred_x0),
-                                                 _l.ptr(self.coef), S, float(cfg_scale), 1 if use_scale else 0, n, S_()), "moca_base_ddim_step_f32")
-        self._wrap_plan(pre, post)
+        self._wrap_ddim_step(self.noise, self.noise, cfg_scale, bool(sampler.use_scale))
 
     @staticmethod
     def _schedule_tables(sampler, n_rows):
@@ -532,13 +602,12 @@ class BaseEngine(_StepEngine):
         return torch.from_numpy(coef), torch.from_numpy(t_table)
 
     def _write_schedule(self, coef, t_table):
-        """enqueue the tables into rows 0 .. len-1 of the device tables and move the start of the iteration counter so that step i of a
-        trajectory reads row len - 1 - i through the captured S (row S - 1 - iter)"""
+        """(inside an enqueue) the tables into rows 0 .. len-1 of the device tables, the start of the iteration counter moved so that
+        step i of a trajectory reads row len - 1 - i through the captured S (row S - 1 - iter)"""
         n = int(t_table.shape[0])
-        with self.plan._enqueue():
-            self.coef[:n].copy_(coef)
-            self.t_table[:n].copy_(t_table)
-            self.state[1:2].fill_(self.S - n)
+        self.coef[:n].copy_(coef)
+        self.t_table[:n].copy_(t_table)
+        self.state[1:2].fill_(self.S - n)
         self.it0 = self.n_iter = self.S - n
 
     def set_schedule(self, sampler):
@@ -551,7 +620,8 @@ class BaseEngine(_StepEngine):
         n = len(sampler.ddim_timesteps)
         if not 1 <= n <= self.S:
             raise ValueError(f"set_schedule: a schedule of {n} steps does not fit the {self.S} rows this engine was captured for")
-        self._write_schedule(*self._schedule_tables(sampler, n))
+        with self.plan._enqueue():
+            self._write_schedule(*self._schedule_tables(sampler, n))
         self.enc_coef = tuple(c.to(self.device) for c in sampler.encode_tables())
         self._schedule_set = True
 
@@ -616,30 +686,20 @@ class BaseEngine(_StepEngine):
     def reset(self, x, cond, uc, seed=0, features_adapter=None):
         """start a new trajectory on the same plan: latents x_T, contexts, fps, adapter maps, iteration 0, a new noise stream; the
         engine's own schedule, should `set_schedule` have replaced it"""
-        plan, dev = self.plan, self.device
+        plan = self.plan
         if (features_adapter is None) != (plan.adapter_in is None):
             raise ValueError("features_adapter goes with an engine built for it")
-        B, T = self.shape[0], self.shape[2]
-        fps = (16, 16) if self.hybrid else (cond.get("fps", 16), uc.get("fps", 16))
-        self._refuse_unequal_fps(fps)
-        cc, cu = (context(c).expand(B, -1, -1) for c in (cond, uc))
-        if self._schedule_set:
-            self._write_schedule(*self._built)
-            self.enc_coef, self._schedule_set = self._built_enc, False
-        self._reinit_src = (None, None)
-        with plan._enqueue():
-            self.state.copy_(state_block(seed))
+        with self._restart(x, cond, uc, seed, fps=(16, 16) if self.hybrid else None):
+            if self._schedule_set:                               # (the built tables end at row S - 1: the counter stays at 0)
+                self._write_schedule(*self._built)
+                self.enc_coef, self._schedule_set = self._built_enc, False
+            self._reinit_src = (None, None)
             self.enc_state.copy_(state_block(seed, -1))          # (no step ever draws at this iteration: steps count up from 0)
-            plan.x_in.copy_(x.to(torch.float32))
-            plan.fps_rows.copy_(torch.cat([fps_rows(fp, B, T, dev) for fp in fps]))
-            plan.set_context([cc, cu])
             if features_adapter is not None:
                 plan.set_adapter(list(features_adapter))
             if plan.pieces is not None:
                 with plan._ops_stream():
                     plan.set_concat(cond["c_concat"])
-        self.sync_to()
-        self.n_iter = 0
 
     def encode(self, x0, t_index, noise=None):
         """`stochastic_encode` (ddim.py:652-671) into the plan's input buffer: x_in = sqrt(a)[t] x0 + sqrt(1 - a)[t] noise on the plan's
@@ -675,11 +735,7 @@ class BaseEngine(_StepEngine):
             if noise is not None:
                 self._fix_noise((self.noise, noise))
 
-    def last_pred_x0(self):
-        return self._copy(self.pred_x0, self.shape)
-
-
-class InvertEngine(_StepEngine):
+class InvertEngine(_TrajectoryEngine):
     """One step of deterministic DDIM inversion (`DDIMSampler.encode`) as ONE hipGraph: [timestep rows of step i] + the UNet forward +
     [guidance + update in place, i += 1] -- `BaseEngine`'s two launches around the forward, `moca_base_set_timestep` and
     `moca_base_ddim_step_f32`, on another table.  Step i takes the latents in the plan's input buffer from schedule level
@@ -697,50 +753,26 @@ class InvertEngine(_StepEngine):
     def supported(model, x, cond, uc=None, scale=1.0):
         """`BaseEngine.supported`'s conditions on the model, the device, the keys and the fps for 'crossattn' models, without its
         `scale != 1.0` clause (the hybrid keys stay on the host-issued path)"""
-        if not isinstance(unet_of(model), UNetModel) or conditioning_key(model) != "crossattn" or not x.is_cuda:
-            return False
-        if not isinstance(cond, dict) or "c_crossattn" not in cond or not set(cond.keys()) <= {"c_crossattn", "fps"}:
-            return False
-        if uc is None or scale == 1.0:
-            return x.shape[0] <= 64
-        return isinstance(uc, dict) and set(uc.keys()) == set(cond.keys()) and 2 * x.shape[0] <= 64 and \
-            same_fps([cond.get("fps", 16), uc.get("fps", 16)])      # (the shared prefix adds ONE fps embedding)
+        branches = [cond] if uc is None or scale == 1.0 else [cond, uc]
+        return _TrajectoryEngine._supports(model, x, branches) and "c_crossattn" in cond and _TrajectoryEngine._supports_crossattn(model, branches)
+
+    @staticmethod
+    def key(sampler, x, cond, uc=None, cfg_scale=1.0):
+        """what an engine built by `InvertEngine(model, sampler, x, cond, uc, cfg_scale)` is good for.  The leading "invert" keeps it
+        apart from `BaseEngine.key`'s tuples, which start with a shape, where both share a cache; the engine covers the whole schedule,
+        so the number of steps taken is no part of it"""
+        guided = uc is not None and cfg_scale != 1.0
+        return ("invert", tuple(x.shape), n_ctx(cond), n_ctx(uc) if guided else None, float(cfg_scale) if guided else 1.0,
+                sampler.ddim_timesteps.tobytes(), bool(sampler.use_scale), str(x.device))
 
     def __init__(self, model, sampler, x, cond, uc=None, cfg_scale=1.0, keep_pred_x0=False):
-        self.unet = unet = model.model.diffusion_model
-        dev = x.device
-        self.device = dev
-        if unet._packed is None:
-            unet._pack()
-        B, Cc, T, H, W = x.shape
-        self.shape = (B, Cc, T, H, W)
-        self.S = S = len(sampler.ddim_timesteps)
-        self.guided = uc is not None and cfg_scale != 1.0
-        n_ctx = lambda c: sum(int(k.shape[1]) for k in c["c_crossattn"])
-        if self.guided:
-            self.plan = plan = _Plan(unet, 2 * B, T, H, W, ((B, n_ctx(cond)), (B, n_ctx(uc))), torch.float32, dev, shared_x=True)
-        else:
-            self.plan = plan = _Plan(unet, B, T, H, W, n_ctx(cond), torch.float32, dev)
+        guided = uc is not None and cfg_scale != 1.0
+        dev, n = self._open(model, x, [cond, uc] if guided else [cond], len(sampler.ddim_timesteps))
         self.coef, self.t_table = (t.to(dev) for t in self._schedule_tables(sampler))
-        self.state = torch.zeros(8, dtype=torch.int32, device=dev)
-        n = x.numel()
         self.zeros = torch.zeros(n, dtype=torch.float32, device=dev)           # the noise operand: sigma = 0 times finite zeros
         self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev) if keep_pred_x0 else None
         self.reset(x, cond, uc)
-        lib = _l.load()
-        eps = plan.out.reshape(plan.B, -1)
-        st_ = _l.ptr(self.state)
-        use_scale = 1 if sampler.use_scale else 0
-        S_ = lambda: C.c_void_p(ops.current_stream())
-
-        def pre():
-            _l.check(lib.moca_base_set_timestep(st_, _l.ptr(self.t_table), S, _l.ptr(plan.t_rows), plan.t_rows.numel(), S_()), "moca_base_set_timestep")
-
-        def post():
-            _l.check(lib.moca_base_ddim_step_f32(st_, _l.ptr(plan.x_in), _l.ptr(eps[:B]), _l.ptr(eps[B:]) if self.guided else None,
-                                                 _l.ptr(self.zeros), _l.ptr(self.pred_x0), _l.ptr(self.coef), S, float(cfg_scale), use_scale, n,
-                                                 S_()), "moca_base_ddim_step_f32")
-        self._wrap_plan(pre, post)
+        self._wrap_ddim_step(None, self.zeros, cfg_scale, sampler.use_scale)
 
     @staticmethod
     def _schedule_tables(sampler):
@@ -756,19 +788,9 @@ class InvertEngine(_StepEngine):
 
     def reset(self, x, cond, uc=None):
         """start the inversion of another clip on the same plan and the same captured graph: latents x0, contexts, fps, step 0"""
-        plan, dev = self.plan, self.device
-        B, T = self.shape[0], self.shape[2]
-        if tuple(x.shape) != self.shape:
-            raise ValueError(f"x {tuple(x.shape)} does not match the engine's latents {self.shape}")
-        branches = [cond] + ([uc] if self.guided else [])
-        self._refuse_unequal_fps([c.get("fps", 16) for c in branches])
-        with plan._enqueue():
-            self.state.copy_(state_block(0))
-            plan.x_in.copy_(x.to(torch.float32))
-            plan.fps_rows.copy_(torch.cat([fps_rows(c.get("fps", 16), B, T, dev) for c in branches]))
-            plan.set_context([context(c).expand(B, -1, -1) for c in branches])
-        self.sync_to()
-        self.n_iter = 0
+        self._refuse_other_shape(x)
+        with self._restart(x, cond, uc):
+            pass
 
     def step(self):
         """one inversion step (enqueued, not synchronised)"""
@@ -777,15 +799,26 @@ class InvertEngine(_StepEngine):
         with self._step():
             pass
 
-    def t_rows(self):
-        """the timestep rows the UNet of the last step was given (a copy)"""
-        return self._copy(self.plan.t_rows)
 
-    def last_pred_x0(self):
-        return self._copy(self.pred_x0, self.shape)
+def mask_kind(mask, shape):
+    """how the DDPM step kernel reads `mask` against latents of `shape`: "c0" (one channel, channel stride 0) or "full"
+    (`img_orig * mask`, ddpm3d.py:648, broadcasts: everything else is expanded to the latents' shape)"""
+    ms = (1,) * (len(shape) - mask.dim()) + tuple(mask.shape)
+    return "c0" if ms[1] == 1 and shape[1] > 1 else "full"
 
 
-class DdpmEngine(_StepEngine):
+def mask_operand(mask, shape, device):
+    """-> (contiguous fp32 mask as the kernel reads it, kernel flag, elements per mask channel)"""
+    B, Cc = int(shape[0]), int(shape[1])
+    inner = int(np.prod(shape[2:]))
+    m = mask.to(device, torch.float32)
+    m = m.reshape((1,) * (len(shape) - m.dim()) + tuple(m.shape))
+    if mask_kind(mask, shape) == "c0":
+        return m.expand(B, 1, *shape[2:]).contiguous(), _l.MOCA_DDPM_MASK_C0, inner
+    return m.expand(*shape).contiguous(), 0, inner * Cc
+
+
+class DdpmEngine(_TrajectoryEngine):
     """One step of `LatentDiffusion.p_sample_loop` (ddpm3d.py:638-648: p_sample at t = i for all samples, then with a mask
     `img = q_sample(x0, ts) * mask + (1 - mask) * img`) as ONE hipGraph: [timestep rows of step k from the state counter
     (`moca_base_set_timestep` over the table arange(timesteps), so step k runs at t = timesteps - 1 - k) + the Philox draws: the step's
@@ -798,41 +831,28 @@ class DdpmEngine(_StepEngine):
     def supported(model, x, cond, uc=None):
         """'crossattn' models with `c_crossattn` / `fps` conditioning only (a tensor or a list is `c_crossattn`, as apply_model takes
         them); a guidance branch must have the same keys and fps (the shared prefix adds ONE fps embedding)"""
-        if not isinstance(unet_of(model), UNetModel) or conditioning_key(model) != "crossattn" or not x.is_cuda or cond is None:
+        if cond is None:
             return False
-        cond = as_cond_dict(cond)
-        if "c_crossattn" not in cond or not set(cond.keys()) <= {"c_crossattn", "fps"}:
-            return False
-        reps = 1
-        if uc is not None:
-            uc = as_cond_dict(uc)
-            if set(uc.keys()) != set(cond.keys()) or not same_fps([cond.get("fps", 16), uc.get("fps", 16)]):
-                return False
-            reps = 2
-        return reps * x.shape[0] <= 64
+        branches = [as_cond_dict(c) for c in (cond, uc) if c is not None]
+        return _TrajectoryEngine._supports(model, x, branches) and "c_crossattn" in branches[0] and \
+            _TrajectoryEngine._supports_crossattn(model, branches)
+
+    @staticmethod
+    def key(shape, cond, uc, timesteps, cfg_scale, mask, clip_denoised, parameterization, device):
+        """what an engine built by `DdpmEngine(model, x, cond, uc, cfg_scale, timesteps, mask=mask)` is good for: latent shape, context
+        lengths (None: no guidance branch), the number of steps, the guidance scale, whether and how a mask is read, the model's
+        clip_denoised and parameterization (the kernel's flags) and the device"""
+        return (tuple(int(s) for s in shape), n_ctx(cond), None if uc is None else n_ctx(uc), int(timesteps), float(cfg_scale),
+                None if mask is None else mask_kind(mask, shape), bool(clip_denoised), str(parameterization), str(device))
 
     def __init__(self, model, x, cond, uc, cfg_scale, timesteps, mask=None, x0=None, seed=0, keep_x_recon=False):
         self.model = model
-        self.unet = unet = model.model.diffusion_model
-        dev = x.device
-        self.device = dev
-        if unet._packed is None:
-            unet._pack()
-        B, Cc, T, H, W = x.shape
-        self.shape = (B, Cc, T, H, W)
-        self.S = S = int(timesteps)
+        S = int(timesteps)
         if not 1 <= S <= model.num_timesteps:
             raise ValueError(f"timesteps = {timesteps}: the schedule has {model.num_timesteps} rows")
-        self.guided = uc is not None
-        n_ctx = lambda c: sum(int(k.shape[1]) for k in c["c_crossattn"])
-        if self.guided:
-            self.plan = plan = _Plan(unet, 2 * B, T, H, W, ((B, n_ctx(cond)), (B, n_ctx(uc))), torch.float32, dev, shared_x=True)
-        else:
-            self.plan = plan = _Plan(unet, B, T, H, W, n_ctx(cond), torch.float32, dev)
+        dev, n = self._open(model, x, [cond] if uc is None else [cond, uc], S)
         self.coef = model._ddpm_dev(dev)["coef"]
         self.t_table = torch.arange(S, dtype=torch.int64, device=dev)           # `for i in reversed(range(0, timesteps))`, :632,639
-        self.state = torch.zeros(8, dtype=torch.int32, device=dev)
-        n = x.numel()
         self.n = n
         self.n_pad = (n + 3) // 4 * 4                                            # q_sample's draw starts 16-byte aligned
         self.masked = mask is not None
@@ -847,48 +867,27 @@ class DdpmEngine(_StepEngine):
             self.x0 = torch.empty(n, dtype=torch.float32, device=dev)
         self.x_recon = torch.empty(n, dtype=torch.float32, device=dev) if keep_x_recon else None
         self.reset(x, cond, uc, seed, mask=mask, x0=x0)
-        lib = _l.load()
-        eps = plan.out.reshape(plan.B, -1)
-        st_ = _l.ptr(self.state)
-        S_ = lambda: C.c_void_p(ops.current_stream())
+        plan, (B, T) = self.plan, (self.shape[0], self.shape[2])
         nq = self.noise[self.n_pad:] if self.masked else None
-
-        def pre():
-            _l.check(lib.moca_base_set_timestep(st_, _l.ptr(self.t_table), S, _l.ptr(plan.t_rows), plan.t_rows.numel(), S_()), "moca_base_set_timestep")
-            _l.check(lib.moca_fifo_randn_f32(st_, _l.ptr(self.noise), self.noise.numel(), S_()), "moca_fifo_randn_f32")
-
-        def post():
-            _l.check(lib.moca_ddpm_step_f32(st_, _l.ptr(plan.x_in), _l.ptr(plan.x_in), _l.ptr(eps[:B]), _l.ptr(eps[B:]) if self.guided else None,
-                                            _l.ptr(self.noise), _l.ptr(self.x_recon), None, _l.ptr(self.mask), _l.ptr(self.x0), _l.ptr(nq),
-                                            _l.ptr(self.coef), _l.ptr(plan.t_rows), T, B, int(self.coef.shape[0]), n // B, self.mask_inner,
-                                            float(cfg_scale), 1.0, self.flags, S_()), "moca_ddpm_step_f32")
-        self._wrap_plan(pre, post)
+        self._wrap_step(self.noise, lambda lib, st_, eps_c, eps_u, stream: _l.check(lib.moca_ddpm_step_f32(
+            st_, _l.ptr(plan.x_in), _l.ptr(plan.x_in), eps_c, eps_u, _l.ptr(self.noise), _l.ptr(self.x_recon), None, _l.ptr(self.mask),
+            _l.ptr(self.x0), _l.ptr(nq), _l.ptr(self.coef), _l.ptr(plan.t_rows), T, B, int(self.coef.shape[0]), n // B, self.mask_inner,
+            float(cfg_scale), 1.0, self.flags, stream), "moca_ddpm_step_f32"))
 
     def reset(self, x, cond, uc=None, seed=0, mask=None, x0=None):
         """start a new trajectory on the same plan: latents x_T, contexts, fps, mask and x0, step 0, a new noise stream"""
-        plan, dev = self.plan, self.device
-        B, T = self.shape[0], self.shape[2]
         if (uc is not None) != self.guided or (mask is not None) != self.masked:
             raise ValueError("guidance and mask go with an engine built for them")
-        if tuple(x.shape) != self.shape:
-            raise ValueError(f"x {tuple(x.shape)} does not match the engine's latents {self.shape}")
-        branches = [cond] + ([uc] if self.guided else [])
-        self._refuse_unequal_fps([c.get("fps", 16) for c in branches])
-        with plan._enqueue():
-            self.state.copy_(state_block(seed))
-            plan.x_in.copy_(x.to(torch.float32))
-            plan.fps_rows.copy_(torch.cat([fps_rows(c.get("fps", 16), B, T, dev) for c in branches]))
-            plan.set_context([context(c).expand(B, -1, -1) for c in branches])
+        self._refuse_other_shape(x)
+        with self._restart(x, cond, uc, seed):
             if self.masked:
-                m, mflag, inner = mask_operand(mask, self.shape, dev)
+                m, mflag, inner = mask_operand(mask, self.shape, self.device)
                 if m.shape != self.mask.shape or inner != self.mask_inner:
                     raise ValueError(f"mask {tuple(mask.shape)} is read another way than the mask the engine was built with")
                 if tuple(x0.shape) != self.shape:
                     raise ValueError(f"x0 {tuple(x0.shape)} does not match the engine's latents {self.shape}")
                 self.mask.copy_(m)
-                self.x0.copy_(x0.reshape(-1).to(dev, torch.float32))
-        self.sync_to()
-        self.n_iter = 0
+                self.x0.copy_(x0.reshape(-1).to(self.device, torch.float32))
 
     def step(self, noise=None, mask_noise=None):
         """one DDPM step (enqueued, not synchronised); `noise` [B,C,T,H,W] fixes p_sample's draw and, on a masked engine, `mask_noise`
@@ -898,10 +897,6 @@ class DdpmEngine(_StepEngine):
         with self._step():
             if noise is not None:
                 self._fix_noise((self.noise[:self.n], noise), *([(self.noise[self.n_pad:], mask_noise)] if self.masked else []))
-
-    def t_rows(self):
-        """the timestep rows the UNet of the last step was given (a copy)"""
-        return self._copy(self.plan.t_rows)
 
     def last_x_recon(self):
         return self._copy(self.x_recon, self.shape)

@@ -173,16 +173,11 @@ class DDIMSampler(object):
         return x_prev, pred_x0
 
     def _engine_for(self, img, cond, uc, scale, seed, n_rows, features_adapter=None):
-        """the cached step graph (fifo_graph.BaseEngine) for this call, reset to a new trajectory; built when the key changes.  `n_rows`:
-        the rows of the schedule tables the captured kernels index (all of them for `sample`, the first t_start for `decode`): part of
-        the key, so neither picks up the other's engine"""
-        cu, cn = cond["c_crossattn"], uc["c_crossattn"]
-        key = (tuple(img.shape), sum(c.shape[1] for c in cu), sum(c.shape[1] for c in cn), float(scale),
-               self.ddim_timesteps.tobytes(), np.asarray(self.ddim_sigmas).tobytes(), str(img.device),
-               tuple(int(c.shape[1]) for c in cond.get("c_concat") or ()),
-               None if features_adapter is None else tuple(tuple(f.shape) for f in features_adapter), int(n_rows))
-        return self._engines.get(key, lambda: BaseEngine(self.model, self, img, cond, uc, scale, seed=seed, features_adapter=features_adapter,
-                                                         n_rows=n_rows),
+        """the cached step graph (fifo_graph.BaseEngine) for this call, reset to a new trajectory; built when `BaseEngine.key` changes.
+        `n_rows`: the rows of the schedule tables the captured kernels index (all of them for `sample`, the first t_start for `decode`)"""
+        return self._engines.get(BaseEngine.key(self, img, cond, uc, scale, features_adapter, n_rows),
+                                 lambda: BaseEngine(self.model, self, img, cond, uc, scale, seed=seed, features_adapter=features_adapter,
+                                                    n_rows=n_rows),
                                  lambda eng: eng.reset(img, cond, uc, seed, features_adapter=features_adapter))
 
     _base_engine = property(lambda self: self._engines.entry, doc="None, or the (key, engine) of the cached step graph")
@@ -333,15 +328,11 @@ class DDIMSampler(object):
                                self.use_graph if use_graph is None else use_graph)
 
     def _invert_engine_for(self, x0, cond, uc, scale):
-        """the cached step graph of `encode` (fifo_graph.InvertEngine) reset to the clip `x0`; built when the key changes.  It shares the
-        one-entry cache of `sample` / `decode`, whose keys are tuples that start with a shape: the leading "invert" keeps the two apart.
-        The engine covers the whole schedule, so t_enc is no part of the key."""
-        guided = uc is not None and scale != 1.0
-        n_ctx = lambda c: sum(int(k.shape[1]) for k in c["c_crossattn"])
-        key = ("invert", tuple(x0.shape), n_ctx(cond), n_ctx(uc) if guided else None, float(scale) if guided else 1.0,
-               self.ddim_timesteps.tobytes(), bool(self.use_scale), str(x0.device))
-        return self._engines.get(key, lambda: InvertEngine(self.model, self, x0, cond, uc if guided else None, scale),
-                                 lambda eng: eng.reset(x0, cond, uc if guided else None))
+        """the cached step graph of `encode` (fifo_graph.InvertEngine) reset to the clip `x0`; built when `InvertEngine.key` changes.  It
+        shares the one-entry cache of `sample` / `decode`."""
+        uc = uc if scale != 1.0 else None
+        return self._engines.get(InvertEngine.key(self, x0, cond, uc, scale), lambda: InvertEngine(self.model, self, x0, cond, uc, scale),
+                                 lambda eng: eng.reset(x0, cond, uc))
 
     def invert_update(self, x, e_t, i, zeros=None):
         """inversion step `i` of `encode` on the host-issued path: `moca_ddim_update_f32` with the scalars of `invert_coef` -- the

@@ -6,7 +6,9 @@ tests/test_sampler_routes_cpu.py compares this tree with it line by line.
 Stand-ins while a trace runs (`tracing()`): `lib.load()` is an object that records every entry point called and returns 0 (it also
 WRITES the outputs of moca_cfg_combine_f32 and moca_ddim_update_f32, so a loop's later operands depend on its earlier ones); `lib.ptr`
 returns a token of the tensor's dtype, shape and a hash of its content at call time; `ops.current_stream` is a constant;
-`torch.empty*` give zeros (a launch that writes nothing must leave something reproducible) and `.to("cuda")` stays on the host.  The
+`torch.empty*` give zeros (a launch that writes nothing must leave something reproducible), `.to("cuda")` stays on the host and
+`torch.cuda.current_stream`, `Tensor.record_stream` and `torch.cuda.Event` order nothing.  The step engines of fifo_graph.py run on a
+plan that holds buffers only (`BufferPlan`, in place of the module's `_Plan`): no engine method is replaced.  The
 model is the schedule model of tests/v2v_ref.py with the DDPM mixin, a stub wrapper and a stub UNet whose three entry points record
 their arguments and return an exact function of ALL of them (x, t, context, fps, adapter maps, c_concat): every operand is a small
 dyadic rational, so the sums are exact in fp32 whatever the host's vector width, and a mixed-up operand changes a later hash."""
@@ -84,10 +86,25 @@ class _FakeLib:
         return call
 
 
+class HostStream:
+    """stands in for a stream and for an event: nothing to order on the host"""
+    cuda_stream = 0
+
+    def wait_stream(self, other):
+        pass
+
+    def synchronize(self):
+        pass
+
+    def record(self, stream=None):
+        pass
+
+
 @contextlib.contextmanager
 def tracing(trace):
     from moca_video_amd import lib, ops
-    saved = (lib.load, lib.ptr, ops.current_stream, torch.empty, torch.empty_like, torch.Tensor.to)
+    saved = (lib.load, lib.ptr, ops.current_stream, torch.empty, torch.empty_like, torch.Tensor.to, torch.cuda.current_stream,
+             torch.Tensor.record_stream, torch.cuda.Event)
     fake = _FakeLib(trace)
     to = torch.Tensor.to
     lib.load = lambda: fake
@@ -95,10 +112,14 @@ def tracing(trace):
     ops.current_stream = lambda: 0
     torch.empty, torch.empty_like = torch.zeros, torch.zeros_like
     torch.Tensor.to = lambda self, *a, **k: to(self, *("cpu" if isinstance(x, str) and x == "cuda" else x for x in a), **k)
+    torch.cuda.current_stream = lambda device=None: HostStream()
+    torch.Tensor.record_stream = lambda self, stream: None
+    torch.cuda.Event = HostStream
     try:
         yield
     finally:
-        lib.load, lib.ptr, ops.current_stream, torch.empty, torch.empty_like, torch.Tensor.to = saved
+        (lib.load, lib.ptr, ops.current_stream, torch.empty, torch.empty_like, torch.Tensor.to, torch.cuda.current_stream,
+         torch.Tensor.record_stream, torch.cuda.Event) = saved
 
 
 # ---- the stub model -----------------------------------------------------------------------------------------------------------
@@ -124,6 +145,7 @@ def _unet_classes():
 
     class StubUNet(UNetModel):
         """passes `isinstance(unet, UNetModel)`; nothing of the real model is built"""
+        adapter_sites = 1
 
         def __init__(self, trace, in_channels=4):
             torch.nn.Module.__init__(self)
@@ -369,9 +391,366 @@ def trace_fifo(lookahead, batch_windows):
     return trace
 
 
+# ---- the step engines on a plan that holds buffers only ---------------------------------------------------------------------------
+class BufferPlan:
+    """what the step engines touch of a `_Plan`, on the host: its buffers, segments, `pieces` and adapter buffers; `set_context` /
+    `set_adapter` / `set_concat` record their operands; `_enqueue` / `_ops_stream` order nothing.  The plan's own launch list is ONE
+    marker step that writes the line "forward", so a replay shows which of the engine's launches run before the forward and which
+    after it."""
+
+    def __init__(self, unet, B, T, H, W, L, in_dtype, device, shared_x=False, pieces=None, adapter=None):
+        self.trace, self.B, self.T, self.device = unet.trace, B, T, device
+        self.segs = [(B, L)] if isinstance(L, int) else [(int(n), int(l)) for n, l in L]
+        self.pieces = None if pieces is None else tuple(int(k) for k in pieces)
+        Bx = B // (len(self.segs) if shared_x else 1)
+        self.x_in = torch.zeros(Bx, unet.in_channels - sum(self.pieces or ()), T, H, W)
+        self.out = torch.zeros(B, 4, T, H, W)
+        self.t_rows, self.fps_rows = torch.zeros(B * T, dtype=torch.int64), torch.zeros(B * T, dtype=torch.int64)
+        self.adapter_in = None if adapter is None else [torch.zeros(Bx * T, 2, H, W) for _ in range(int(adapter))]
+        self.stream = HostStream()
+        self.steps = [lambda: self.trace.append("forward")]
+        self.trace.append(f"_Plan(B={B},T={T},H={H},W={W},segs={show(self.segs)},shared_x={int(shared_x)},pieces={show(self.pieces)},"
+                          f"adapter={show(adapter)})")
+
+    def set_context(self, ctxs):
+        self.trace.append(f"set_context({show(ctxs)})")
+
+    def set_adapter(self, features):
+        self.trace.append(f"set_adapter({show(features)})")
+
+    def set_concat(self, c_concat):
+        self.trace.append(f"set_concat({show(c_concat)})")
+
+    @contextlib.contextmanager
+    def _enqueue(self, cur=None):
+        yield
+
+    _ops_stream = _enqueue
+
+    def _replay(self):
+        for step in self.steps:
+            step()
+
+    def close(self):
+        self.trace.append("close")
+
+
+@contextlib.contextmanager
+def engine_tracing(trace):
+    """`tracing()` with `BufferPlan` under the name the engines construct their plan through -> the module"""
+    from moca_video_amd import fifo_graph
+    saved, fifo_graph._Plan = fifo_graph._Plan, BufferPlan
+    try:
+        with tracing(trace):
+            yield fifo_graph
+    finally:
+        fifo_graph._Plan = saved
+
+
+def _dump(trace, eng, what):
+    """what a reset (or `what`) left behind: the device state as the host sees it"""
+    trace.append(f"after {what}: state={show(eng.state)} x_in={show(eng.plan.x_in)} fps_rows={show(eng.plan.fps_rows)} coef={show(eng.coef)} "
+                 f"t_table={show(eng.t_table)} n_iter={eng.n_iter} it0={getattr(eng, 'it0', '-')}")
+
+
+EB = 2                                                # latents per engine: "per sample" means something
+E_SHAPE = (EB, 4, 2, 2, 2)
+E_DDPM_STEPS = 4
+
+
+def _adapter_maps(seed):
+    return [grid((EB * 2, 2, 2, 2), seed)]
+
+
+def trace_base_engine(which):
+    """`BaseEngine`: construction, reset, a step with host-given noise and one without, a second reset with other operands; `which`
+    picks the constructor's options and, for "plain", the calls between the two resets"""
+    from moca_video_amd.sampler import DDIMSampler
+    trace = []
+    hybrid = which == "hybrid"
+    m = make_model(trace, key="hybrid" if hybrid else "crossattn")
+    s = DDIMSampler(m)
+    s.make_schedule(S, ddim_eta=1.0, verbose=False)
+    kw = {"rows": dict(n_rows=T_START), "pred_x0": dict(keep_pred_x0=True), "adapter": dict(features_adapter=_adapter_maps(50))}.get(which, {})
+    c, uc = _cond(EB, 3, 16, 1, hybrid), _cond(EB, 3, 16, 2, hybrid)
+    with engine_tracing(trace) as fg:
+        eng = fg.BaseEngine(m, s, grid(E_SHAPE, 3), c, uc, SCALE, seed=5, **kw)
+        _dump(trace, eng, "construction")
+        eng.step(noise=grid(E_SHAPE, 6))
+        eng.step()
+        trace.append(f"latents={show(eng.latents())} last_pred_x0={show(eng.last_pred_x0())}")
+        if which == "plain":
+            x0 = grid(E_SHAPE, 9)
+            for t_index in (3, torch.tensor([2, 4])):
+                eng.encode(x0, t_index)
+                eng.encode(x0, t_index, noise=grid(E_SHAPE, 11))
+                trace.append(f"encoded x_in={show(eng.plan.x_in)} noise={show(eng.noise)}")
+            shorter = DDIMSampler(m)
+            shorter.make_schedule(T_START, ddim_eta=1.0, verbose=False)
+            eng.set_schedule(shorter)
+            _dump(trace, eng, "set_schedule")
+            eng.step()
+            eng.encode(x0, 3)
+            init, lpf = grid(E_SHAPE, 12), grid((1, 1, 2, 2, 2), 13)
+            eng.reinit(init, lpf, seed=7)
+            _dump(trace, eng, "reinit")
+            init.add_(1)                              # the same objects again: no upload, so the launches still see the old values
+            lpf.add_(1)
+            eng.reinit(init, lpf, z_rand=grid(E_SHAPE, 14), seed=8)
+            eng.reinit(init.clone(), lpf.clone(), seed=8)
+        c2, uc2 = _cond(EB, 3, 8, 7), _cond(EB, 3, 8, 8)
+        if hybrid:
+            c2["c_concat"] = uc2["c_concat"] = [grid((EB, 2, 2, 2, 2), 41)]
+        eng.reset(grid(E_SHAPE, 4), c2, uc2, (1 << 40) + 9, **({"features_adapter": _adapter_maps(51)} if which == "adapter" else {}))
+        _dump(trace, eng, "reset")
+        if which == "plain":
+            eng.reinit(init, lpf, seed=3)             # a reset forgets what was uploaded
+        eng.step()
+        trace.append(f"n_iter={eng.n_iter} S={eng.S} shape={show(eng.shape)}")
+        eng.close()
+    return trace
+
+
+def trace_invert_engine(which):
+    from moca_video_amd.sampler import DDIMSampler
+    trace = []
+    m = make_model(trace)
+    s = DDIMSampler(m)
+    s.make_schedule(S, ddim_eta=0.0, verbose=False)
+    guided = which == "guided"
+    c, uc = _cond(EB, 3, 16, 1), _cond(EB, 6, 16, 2) if guided else None
+    with engine_tracing(trace) as fg:
+        eng = fg.InvertEngine(m, s, grid(E_SHAPE, 3), c, uc, SCALE if guided else 1.0, keep_pred_x0=which == "pred_x0")
+        _dump(trace, eng, "construction")
+        eng.step()
+        eng.step()
+        trace.append(f"latents={show(eng.latents())} last_pred_x0={show(eng.last_pred_x0())} t_rows={show(eng.t_rows())} guided={int(eng.guided)}")
+        eng.reset(grid(E_SHAPE, 4), _cond(EB, 3, 8, 7), _cond(EB, 6, 8, 8) if guided else None)
+        _dump(trace, eng, "reset")
+        if which == "unguided":
+            for _ in range(S):
+                eng.step()
+            _run(trace, eng.step)
+            trace.append(f"n_iter={eng.n_iter} S={eng.S} zeros={show(eng.zeros)}")
+        eng.close()
+    return trace
+
+
+def _mask(which, seed=7):
+    return None if which not in ("c0", "full") else (grid((EB, 1 if which == "c0" else 4, 2, 2, 2), seed) > 0).float()
+
+
+def trace_ddpm_engine(which):
+    trace = []
+    m = make_model(trace)
+    guided = which == "guided"
+    c, uc = _cond(EB, 3, 16, 1), _cond(EB, 6, 16, 2) if guided else None
+    masked = which in ("c0", "full")
+    with engine_tracing(trace) as fg:
+        eng = fg.DdpmEngine(m, grid(E_SHAPE, 3), c, uc, SCALE if guided else 1.0, E_DDPM_STEPS, mask=_mask(which), x0=grid(E_SHAPE, 9) if masked else None,
+                            seed=5, keep_x_recon=which == "x_recon")
+        _dump(trace, eng, "construction")
+        eng.step(noise=grid(E_SHAPE, 6), mask_noise=grid(E_SHAPE, 16) if masked else None)
+        eng.step()
+        trace.append(f"latents={show(eng.latents())} last_x_recon={show(eng.last_x_recon())} t_rows={show(eng.t_rows())} guided={int(eng.guided)} "
+                     f"masked={int(eng.masked)} noise={show(eng.noise)}")
+        eng.reset(grid(E_SHAPE, 4), _cond(EB, 3, 8, 7), _cond(EB, 6, 8, 8) if guided else None, (1 << 40) + 9, mask=_mask(which, 8),
+                  x0=grid(E_SHAPE, 10) if masked else None)
+        _dump(trace, eng, "reset")
+        eng.step()
+        trace.append(f"n_iter={eng.n_iter} S={eng.S} shape={show(eng.shape)}")
+        eng.close()
+    return trace
+
+
+def engine_errors():
+    """type and message of every refusal of the three engines' constructors, `reset`, `step`, `encode`, `set_schedule` and `reinit`"""
+    from moca_video_amd.sampler import DDIMSampler
+    trace, lines = [], []
+    m = make_model(trace)
+    s = DDIMSampler(m)
+    s.make_schedule(S, ddim_eta=1.0, verbose=False)
+    longer = DDIMSampler(m)
+    longer.make_schedule(S + 1, ddim_eta=1.0, verbose=False)
+    x, wide = grid(E_SHAPE, 3), grid((EB + 1,) + E_SHAPE[1:], 3)
+    c, uc, uc8 = _cond(EB, 3, 16, 1), _cond(EB, 3, 16, 2), _cond(EB, 3, 8, 2)
+
+    def case(name, fn):
+        try:
+            fn()
+            lines.append(f"{name}: no error")
+        except Exception as e:
+            lines.append(f"{name}: {type(e).__name__}: {e}")
+    with engine_tracing(trace) as fg:
+        base = fg.BaseEngine(m, s, x, c, uc, SCALE)
+        case("base.init.n_rows", lambda: fg.BaseEngine(m, s, x, c, uc, SCALE, n_rows=S + 1))
+        case("base.init.fps", lambda: fg.BaseEngine(m, s, x, c, uc8, SCALE))
+        case("base.reset.adapter", lambda: base.reset(x, c, uc, features_adapter=_adapter_maps(50)))
+        case("base.reset.fps", lambda: base.reset(x, c, uc8))
+        case("base.encode.shape", lambda: base.encode(wide, 3))
+        case("base.encode.t_shape", lambda: base.encode(x, torch.tensor([1, 2, 3])))
+        case("base.encode.t_range", lambda: base.encode(x, S))
+        case("base.set_schedule.longer", lambda: base.set_schedule(longer))
+        case("base.reinit.initial_noise", lambda: base.reinit(wide, grid((2, 2, 2), 13)))
+        case("base.reinit.lpf", lambda: base.reinit(x, grid((2, 2, 3), 13)))
+        case("base.reinit.z_rand", lambda: base.reinit(x, grid((2, 2, 2), 13), z_rand=wide))
+        inv = fg.InvertEngine(m, s, x, c, uc, SCALE)
+        case("invert.init.fps", lambda: fg.InvertEngine(m, s, x, c, uc8, SCALE))
+        case("invert.reset.shape", lambda: inv.reset(wide, c, uc))
+        case("invert.reset.fps", lambda: inv.reset(x, c, uc8))
+        inv.n_iter = S
+        case("invert.step.past_S", inv.step)
+        ddpm = fg.DdpmEngine(m, x, c, None, 1.0, E_DDPM_STEPS)
+        gd = fg.DdpmEngine(m, x, c, uc, SCALE, E_DDPM_STEPS, mask=_mask("c0"), x0=x)
+        case("ddpm.init.timesteps", lambda: fg.DdpmEngine(m, x, c, None, 1.0, 0))
+        case("ddpm.init.fps", lambda: fg.DdpmEngine(m, x, c, uc8, SCALE, E_DDPM_STEPS))
+        case("ddpm.reset.guidance", lambda: ddpm.reset(x, c, uc))
+        case("ddpm.reset.mask", lambda: ddpm.reset(x, c, mask=_mask("c0"), x0=x))
+        case("ddpm.reset.shape", lambda: ddpm.reset(wide, c))
+        case("ddpm.reset.fps", lambda: gd.reset(x, c, uc8, mask=_mask("c0"), x0=x))
+        case("ddpm.reset.mask_kind", lambda: gd.reset(x, c, uc, mask=_mask("full"), x0=x))
+        case("ddpm.reset.x0", lambda: gd.reset(x, c, uc, mask=_mask("c0"), x0=wide))
+        case("ddpm.step.one_draw", lambda: gd.step(noise=x))
+    return lines
+
+
+def _counting(cls, log):
+    """a stand-in engine that counts builds, resets and closes; `supported` (and whatever else the class says about a would-be
+    constructor call) stays the real class's"""
+    class Counting(cls):
+        def __init__(self, *a, **k):
+            log.append("build")
+            sampler = next((v for v in a if hasattr(v, "ddim_timesteps")), None)
+            self._shape = next(v for v in a if torch.is_tensor(v)).shape
+            self.S, self.it0 = k.get("n_rows") or (len(sampler.ddim_timesteps) if sampler is not None else 0), 0
+
+        def reset(self, *a, **k):
+            log.append("reset")
+            self.it0 = 0
+
+        def close(self):
+            log.append("close")
+
+        def set_schedule(self, sampler):
+            self.it0 = self.S - len(sampler.ddim_timesteps)
+
+        def step(self, *a, **k):
+            pass
+
+        reinit = step
+
+        def latents(self):
+            return torch.zeros(self._shape)
+    return Counting
+
+
+def cache_table():
+    """which calls reuse the cached step engine and which build another: `name: <the variant after the base call> <the variant again>`,
+    each "hit" (reset only) or "miss" (built; "+close": the cached engine was closed first).  One part of a call varies per line."""
+    from moca_video_amd import ddpm as DM
+    from moca_video_amd import sampler as SM
+    log, lines, trace = [], [], []
+    m, mh = make_model(trace), make_model(trace, key="hybrid")
+    s, sh = SM.DDIMSampler(m), SM.DDIMSampler(mh)
+
+    on_meta = torch.zeros((1, 4, 2, 2, 2), device="meta")         # (made out here: inside `tracing()` torch.empty is torch.zeros)
+
+    def latent(B=1, meta=False, seed=3):
+        return cuda_like(on_meta if meta else grid((B, 4, 2, 2, 2), seed))
+
+    def pair(B, Lc, Lu, pieces=None):
+        c, uc = _cond(B, Lc, 16, 1), _cond(B, Lu, 16, 2)
+        if pieces is not None:
+            c["c_concat"] = uc["c_concat"] = [grid((B, k, 2, 2, 2), 40) for k in pieces]
+        return c, uc
+
+    def sample(B=1, Lc=3, Lu=3, scale=SCALE, steps=S, eta=0., meta=False, fa=None, pieces=None, seed=3):
+        c, uc = pair(B, Lc, Lu, pieces)
+        (s if pieces is None else sh).sample(steps, B, (4, 2, 2, 2), c, eta=eta, x_T=latent(B, meta, seed), unconditional_guidance_scale=scale,
+                                             unconditional_conditioning=uc, features_adapter=fa)
+
+    def decode(t_start=T_START):
+        s.make_schedule(S, ddim_eta=0., verbose=False)
+        c, uc = pair(1, 3, 3)
+        s.decode(latent(), c, t_start, unconditional_guidance_scale=SCALE, unconditional_conditioning=uc)
+
+    def encode(B=1, Lc=3, Lu=3, scale=1.0, steps=S, eta=0., meta=False, t_enc=3):
+        s.make_schedule(steps, ddim_eta=eta, verbose=False)
+        c, uc = pair(B, Lc, Lu)
+        s.encode(latent(B, meta), c, t_enc, unconditional_guidance_scale=scale, unconditional_conditioning=uc)
+
+    def freeinit(steps=(2, 3)):
+        c, uc = pair(1, 3, 3)
+        s.sample_freeinit(list(steps), 1, (4, 2, 2, 2), grid((1, 1, 2, 2, 2), 13), c, x_T=latent(), unconditional_guidance_scale=SCALE,
+                          unconditional_conditioning=uc)
+
+    def loop(B=1, Lc=3, Lu=3, scale=1.0, timesteps=2, mask=None, meta=False, clip=False, param="eps"):
+        c, uc = pair(B, Lc, Lu)
+        m.clip_denoised, m.parameterization = clip, param
+        try:
+            mk = None if mask is None else (grid((B, 1 if mask == "c0" else 4, 2, 2, 2), 7) > 0).float()
+            m.p_sample_loop(c, (B, 4, 2, 2, 2), x_T=latent(B, meta), timesteps=timesteps, mask=mk, x0=None if mask is None else grid((B, 4, 2, 2, 2), 9),
+                            unconditional_guidance_scale=scale, unconditional_conditioning=uc, verbose=False)
+        finally:
+            m.clip_denoised, m.parameterization = False, "eps"
+
+    def without_scale(fn):
+        def call():
+            m.use_scale = False
+            try:
+                fn()
+            finally:
+                m.use_scale = True
+        return call
+
+    def probe(name, base, variant):
+        got = []
+        for call in (base, variant, variant):
+            del log[:]
+            call()
+            got.append(("miss" if "build" in log else "hit") + ("+close" if "close" in log else ""))
+        lines.append(f"{name}: {got[1]} {got[2]}")
+    adapter = lambda ch: [grid((2, ch, 2, 2), 50)]
+    saved = SM.BaseEngine, SM.InvertEngine, DM.DdpmEngine
+    SM.BaseEngine, SM.InvertEngine, DM.DdpmEngine = (_counting(cls, log) for cls in saved)
+    try:
+        with tracing(trace):
+            for name, variant in {"same": sample, "latent_values": lambda: sample(seed=4), "shape": lambda: sample(B=2), "cond_length": lambda: sample(Lc=6),
+                                  "uncond_length": lambda: sample(Lu=6), "scale": lambda: sample(scale=2.0), "schedule_length": lambda: sample(steps=S - 1),
+                                  "eta": lambda: sample(eta=1.0), "device": lambda: sample(meta=True), "use_scale": without_scale(sample),
+                                  "adapter": lambda: sample(fa=adapter(2)), "decode": decode, "decode_all_rows": lambda: decode(S),
+                                  "encode": encode, "freeinit": freeinit, "freeinit_same_rows": lambda: freeinit((2, S))}.items():
+                probe("sample." + name, sample, variant)
+            probe("sample.adapter_shapes", lambda: sample(fa=adapter(2)), lambda: sample(fa=adapter(3)))
+            probe("sample.hybrid", sample, lambda: sample(pieces=(2,)))
+            probe("sample.concat_widths", lambda: sample(pieces=(2,)), lambda: sample(pieces=(1, 1)))
+            probe("decode.n_rows", decode, lambda: decode(T_START - 1))
+            for name, variant in {"same": encode, "t_enc": lambda: encode(t_enc=4), "shape": lambda: encode(B=2), "cond_length": lambda: encode(Lc=6),
+                                  "guided": lambda: encode(scale=SCALE), "schedule_length": lambda: encode(steps=S - 1), "eta": lambda: encode(eta=1.0),
+                                  "device": lambda: encode(meta=True), "use_scale": without_scale(encode), "sample": sample}.items():
+                probe("encode." + name, encode, variant)
+            guided = lambda **k: encode(scale=SCALE, **k)
+            for name, variant in {"uncond_length": lambda: guided(Lu=6), "scale": lambda: encode(scale=2.0)}.items():
+                probe("encode.guided." + name, guided, variant)
+            for name, variant in {"same": loop, "shape": lambda: loop(B=2), "cond_length": lambda: loop(Lc=6), "guided": lambda: loop(scale=SCALE),
+                                  "timesteps": lambda: loop(timesteps=3), "mask_c0": lambda: loop(mask="c0"), "device": lambda: loop(meta=True),
+                                  "clip_denoised": lambda: loop(clip=True), "parameterization": lambda: loop(param="x0")}.items():
+                probe("p_sample_loop." + name, loop, variant)
+            probe("p_sample_loop.mask_kind", lambda: loop(mask="c0"), lambda: loop(mask="full"))
+            gloop = lambda **k: loop(scale=SCALE, **k)
+            for name, variant in {"uncond_length": lambda: gloop(Lu=6), "scale": lambda: loop(scale=2.0)}.items():
+                probe("p_sample_loop.guided." + name, gloop, variant)
+            del log[:]
+            s.release()
+            m.release()
+            lines.append("release: " + " ".join(log))
+    finally:
+        SM.BaseEngine, SM.InvertEngine, DM.DdpmEngine = saved
+    return lines
+
+
 def coefficient_tables():
     """`step_tables` and the `BaseEngine` coefficient table (its constructor run on the host over a plan that holds buffers only)"""
-    from moca_video_amd import fifo_graph
     from moca_video_amd.sampler import DDIMSampler
     out = {}
     for eta in (0.0, 1.0):
@@ -385,19 +764,10 @@ def coefficient_tables():
             out[f"step_tables.eta{eta:g}.quirk{int(quirk)}.coef"], out[f"step_tables.eta{eta:g}.quirk{int(quirk)}.enh"] = coef, enh
             out[f"step_tables.eta{eta:g}.quirk{int(quirk)}.midx"] = midx
 
-        class BufferPlan:
-            def __init__(self, unet, B, T, H, W, *a, **k):
-                self.steps, self.x_in, self.out = [], torch.zeros(B // 2, 4, T, H, W), torch.zeros(B, 4, T, H, W)
-                self.t_rows = torch.zeros(B * T, dtype=torch.int64)
-        saved = fifo_graph._Plan, fifo_graph.BaseEngine.reset
-        fifo_graph._Plan, fifo_graph.BaseEngine.reset = BufferPlan, lambda self, *a, **k: None
-        try:
-            with tracing(trace):
-                for rows in (None, T_START):
-                    eng = fifo_graph.BaseEngine(m, s, grid((1, 4, 2, 2, 2), 3), _cond(1, 3, 16, 1), _cond(1, 3, 16, 2), SCALE, n_rows=rows)
-                    out[f"base_engine.eta{eta:g}.rows{rows}.coef"] = eng.coef.numpy().copy()
-        finally:
-            fifo_graph._Plan, fifo_graph.BaseEngine.reset = saved
+        with engine_tracing(trace) as fifo_graph:
+            for rows in (None, T_START):
+                eng = fifo_graph.BaseEngine(m, s, grid((1, 4, 2, 2, 2), 3), _cond(1, 3, 16, 1), _cond(1, 3, 16, 2), SCALE, n_rows=rows)
+                out[f"base_engine.eta{eta:g}.rows{rows}.coef"] = eng.coef.numpy().copy()
     return out
 
 
@@ -425,5 +795,13 @@ def record():
     for lookahead in (False, True):
         for batch_windows in (False, True):
             out[f"fifo.lookahead{int(lookahead)}.batch_windows{int(batch_windows)}"] = trace_fifo(lookahead, batch_windows)
+    for which in ("plain", "rows", "pred_x0", "adapter", "hybrid"):
+        out[f"engine.base.{which}"] = trace_base_engine(which)
+    for which in ("unguided", "guided", "pred_x0"):
+        out[f"engine.invert.{which}"] = trace_invert_engine(which)
+    for which in ("unguided", "guided", "c0", "full", "x_recon"):
+        out[f"engine.ddpm.{which}"] = trace_ddpm_engine(which)
+    out["engine_errors"] = engine_errors()
+    out["cache"] = cache_table()
     out.update(coefficient_tables())
     return {k: np.asarray(v) for k, v in out.items()}

@@ -1,8 +1,10 @@
 """The sampling layer's routes against the parent commit's (tests/golden/sampler_routes.npz, recorded by
 tools/record_parent_fixtures.py --samplers): which UNet entry point every guidance case reaches through `_cfg_eps`, `unet_windows` and
 `_ddpm_step` and with which operands, every launch of the host-issued `sample` / `decode` loops with its coefficients, `ddim_step`,
-the two queue-noising calls, two iterations of the host-driven FIFO loop, the three `supported()` predicates and the coefficient
-tables.  A line that differs is a behaviour change."""
+the two queue-noising calls, two iterations of the host-driven FIFO loop, the three `supported()` predicates, the coefficient
+tables, and the three trajectory engines of fifo_graph.py on a plan that holds buffers only: every launch around the forward with its
+position, what each reset leaves in the state block, the plan's inputs and the tables, every refusal with its message, and which
+sampler calls reuse the cached engine.  A line that differs is a behaviour change."""
 import os
 
 import numpy as np
@@ -27,9 +29,11 @@ def parent():
 def test_every_recorded_trace_is_still_produced(now, parent):
     assert sorted(now) == sorted(parent)
     assert len([k for k in parent if k.startswith("guidance.")]) >= 60
+    assert len([k for k in parent if k.startswith("engine.")]) == 5 + 3 + 5
 
 
-@pytest.mark.parametrize("group", ["guidance.cfg_eps", "guidance.windows", "guidance.ddpm", "supported", "loop", "ddim_step", "queue", "fifo"])
+@pytest.mark.parametrize("group", ["guidance.cfg_eps", "guidance.windows", "guidance.ddpm", "supported", "loop", "ddim_step", "queue", "fifo", "engine.base",
+                                   "engine.invert", "engine.ddpm", "engine_errors", "cache"])
 def test_traces_equal_the_parents(now, parent, group):
     keys = [k for k in sorted(parent) if k.startswith(group)]
     assert keys

@@ -12,8 +12,9 @@ optimisation or a compiler bump legitimately changes them:
                                                  tests/temporal_variants_ref.py
   tests/golden/sampler_routes.npz                (--samplers, no GPU)  the traces of tests/sampler_routes_cpu.py::record: the UNet entry
                                                  points and launches of the sampling layer (guidance routing, host-issued loops,
-                                                 ddim_step, queue noising, the host-driven FIFO loop, `supported()` tables) as
-                                                 lines, the coefficient tables as arrays
+                                                 ddim_step, queue noising, the host-driven FIFO loop, `supported()` tables, the
+                                                 three trajectory engines' launches, resets, refusals and cache hits) as lines,
+                                                 the coefficient tables as arrays
 
     git worktree add ../base <commit> && make -C ../base/moca_video_amd/csrc
     python tools/record_parent_fixtures.py --tree ../base --plans          (any host)
