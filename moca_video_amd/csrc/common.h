@@ -21,6 +21,14 @@ typedef float    f32x16 __attribute__((ext_vector_type(16)));
 
 static inline hipStream_t moca_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// blocks of 256 threads for `total` work items of a grid-stride kernel: at most 4096, beyond that a thread loops
+static inline int grid_for(int64_t total) {
+    int64_t g = (total + 255) / 256;
+    if (g > 4096) g = 4096;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
 // current value of a MOCA_TUNE_* knob (runtime.hip; set through moca_set_tuning)
 int moca_tuning_get(int knob);
 

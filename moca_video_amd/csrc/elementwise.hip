@@ -158,13 +158,6 @@ __global__ __launch_bounds__(256) void silu_add_rows_kernel(const half_t* __rest
     }
 }
 
-inline int grid_for(int64_t total) {
-    int64_t g = (total + 255) / 256;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 // ---- VAE: z / scale_factor -> post_quant_conv (1x1, <= 8 channels) -> channels-last fp16 ---------------
 // out[(b*T+t)*HW + p][co] = bias[co] + sum_ci w[co][ci] * (z[b][ci][t][p] * inv_scale), co < Cout; 0 for Cout <= co < Cpad
 template <typename TIN>

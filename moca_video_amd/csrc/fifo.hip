@@ -2,9 +2,12 @@
 // latent queue is a RING in HBM whose head index, iteration counter and RNG seed live in a small device-resident state
 // block, so that an iteration -- window gather, batched UNet, classifier-free guidance + MoCA ddim_step of all 2n windows,
 // write-back, emission, FreeInit mix, queue shift -- is a fixed launch sequence the host captures ONCE into a hipGraph and
-// replays without reading anything back.  fp32 throughout, compiled with -ffp-contract=off like sampler.hip (the reference
-// evaluates these expressions as separate fp32 torch ops).
+// replays without reading anything back.  The MoCA `ddim_step` of one call's windows (moca_fifo_ddim_step_f32) lives here too: it
+// shares the per-frame recurrence with the all-windows kernel.  One trajectory's step arithmetic (DDIM, base sampling, DDPM,
+// q_sample) is sampler.hip.  fp32 throughout, no FMA contraction (step_math.h, and -ffp-contract=off in the Makefile): the reference
+// evaluates these expressions as separate fp32 torch ops.
 #include "common.h"
+#include "step_math.h"
 
 namespace {
 
@@ -82,6 +85,75 @@ __global__ __launch_bounds__(256) void fifo_gather_kernel(const moca_fifo_state*
     }
 }
 
+// sum of each mask frame over (batch, pixels): ddim.py:585 `if mask.sum() != 0`
+__global__ __launch_bounds__(256) void mask_sum_kernel(const float* __restrict__ mask, float* __restrict__ sums,
+                                                       int B, int Fm, int HW) {
+    __shared__ float red[4];
+    const int fm = blockIdx.x;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < B * HW; i += 256) {
+        const int b = i / HW, p = i - b * HW;
+        s += mask[((int64_t)b * Fm + fm) * HW + p];
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) sums[fm] = red[0] + red[1] + red[2] + red[3];
+}
+
+// Frame j of the MoCA `ddim_step` recurrence for one (b, c, pixel), ddim.py:415-430,557-562.  cf = {sqrt(a_t), sqrt(a_prev),
+// sigma_t, sqrt(1-a_t), sqrt(1-a_prev-sigma^2), 2(1 - ts/1000)} of this frame.  prev (the previous frame's pred_x0) and mom_prev
+// (its momentum) are carried along the frame axis; *mom is this frame's momentum element, written for j >= 1 only (:424).
+// Out: p0 = pred_x0 with the momentum term, before any mask; nz = sigma_t noise; xp = x_prev.
+__device__ __forceinline__ void moca_frame_step(float x, float et, float noise, const float* cf, int j, float beta,
+                                                float one_minus_beta, float* mom, float& prev, float& mom_prev,
+                                                float& p0, float& nz, float& xp) {
+    p0 = (x - cf[3] * et) / cf[0];                              // :415
+    const float dir = cf[4] * et;                               // :418
+    if (j >= 1) {
+        float g = p0 - prev;                                    // :422
+        g = g + 1.5f * dir;                                     // :423
+        const float m = beta * mom_prev + one_minus_beta * g;   // :424-427
+        *mom = m;
+        mom_prev = m;
+        p0 = p0 + cf[5] * m;                                    // :428-430,557
+    }
+    prev = p0;                                                  // :559
+    nz = cf[2] * noise;                                         // :561
+    xp = cf[1] * p0 + dir + nz;                                 // :562
+}
+
+// MoCA FIFO step of one call's windows, ddim.py:405-430,556-609: eps is already guided, coef[f] as above per frame.  One thread per
+// (b, c, pixel); the frame axis is walked sequentially (momentum EMA + previous-frame dependence).
+__global__ __launch_bounds__(256) void fifo_step_kernel(
+    const float* __restrict__ sample, const float* __restrict__ eps, const float* __restrict__ noise,
+    float* __restrict__ momentum, float* __restrict__ x_prev, float* __restrict__ pred_x0,
+    const float* __restrict__ coef, const float* __restrict__ mask, const float* __restrict__ mask_sums,
+    const float* __restrict__ cond, const int32_t* __restrict__ mask_index, const float* __restrict__ enh,
+    int B, int C, int F, int Fm, int HW, float beta, float one_minus_beta, float gamma, float one_minus_gamma) {
+    const int64_t total = (int64_t)B * C * HW;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int p = (int)(i % HW);
+        const int64_t bc = i / HW;
+        const int b = (int)(bc / C);
+        const int64_t base = bc * F * HW + p;   // element (b,c,frame 0,p); frame stride HW
+        float prev = 0.f, mom_prev = momentum[base];   // momentum[:, :, 0] is never written (stays at its initial value)
+        const float cnd = cond ? cond[bc * HW + p] : 0.f;
+        for (int f = 0; f < F; ++f) {
+            const int64_t o = base + (int64_t)f * HW;
+            float p0, nz, xp;
+            moca_frame_step(sample[o], eps[o], noise[o], coef + f * 6, f, beta, one_minus_beta, momentum + o, prev, mom_prev, p0, nz, xp);
+            x_prev[o] = xp;
+            const int mi = mask_index ? mask_index[f] : -1;
+            if (mi >= 0 && mask && mask_sums[mi] != 0.f) {      // :565-590
+                const float mk = mask[((int64_t)b * Fm + mi) * HW + p];
+                if (mk > 0.5f) p0 = cnd * enh[f];
+            }
+            pred_x0[o] = one_minus_gamma * p0 + gamma * nz;     // :609
+        }
+    }
+}
+
 // classifier-free guidance (ddim.py:372) + MoCA ddim_step (ddim.py:405-430,556-609) of every window of an iteration + the
 // write-back of funcs.py:351-354.  One thread per (window, channel, pixel); the frame axis is walked sequentially (momentum
 // EMA, previous-frame dependence).  x is the gathered PRE-iteration copy of the windows: window r+1 reads the frames window
@@ -100,26 +172,12 @@ __global__ __launch_bounds__(256) void fifo_step_windows_kernel(moca_fifo_step_p
         const float cnd = P.cond ? P.cond[(int64_t)c * HW + p] : 0.f;
         const int start = P.win_start[w];
         for (int j = 0; j < f; ++j) {
-            const float* cf = P.coef + ((int64_t)w * f + j) * 6;
             const int64_t o = base + (int64_t)j * HW;
             float et = P.eps_c[o];
-            if (P.eps_u) {
-                const float u = P.eps_u[o];
-                et = u + P.cfg_scale * (et - u);               // :372
-            }
-            float p0 = (P.x[o] - cf[3] * et) / cf[0];          // :415
-            const float dir = cf[4] * et;                      // :418
-            if (j >= 1) {
-                float g = p0 - prev;                           // :422
-                g = g + 1.5f * dir;                            // :423
-                const float m = P.beta * mom_prev + P.one_minus_beta * g;   // :424-427
-                P.momentum[o] = m;
-                mom_prev = m;
-                p0 = p0 + cf[5] * m;                           // :428-430,557
-            }
-            prev = p0;                                         // :559
-            const float nz = cf[2] * P.noise[o];               // :561
-            const float xp = cf[1] * p0 + dir + nz;            // :562
+            if (P.eps_u) et = cfg_guidance(et, P.eps_u[o], P.cfg_scale);   // :372
+            float p0, nz, xp;
+            moca_frame_step(P.x[o], et, P.noise[o], P.coef + ((int64_t)w * f + j) * 6, j, P.beta, P.one_minus_beta, P.momentum + o, prev,
+                            mom_prev, p0, nz, xp);
             if (P.x_prev) P.x_prev[o] = xp;
             if (P.queue && j >= P.wb_from) {                   // funcs.py:351-354
                 int fr = head + start + j;
@@ -162,61 +220,6 @@ __global__ void fifo_advance_bump_kernel(moca_fifo_state* st, int Q) {
     st->head = (st->head + 1) % Q;
     st->iter = st->iter + 1;
     st->ext_noise = 0;
-}
-
-// ---- base sampling (ddim.py:226-252): one DDIM step of `ddim_sampling` as device-side work.  Step i of the loop uses schedule
-// index S - 1 - i (ddim.py:238); i = state->iter mod S, so a captured step replays for every i.
-// rows[0:n] = table[S - 1 - i]: the timestep rows of the UNet plan (ddim.py:239 `ts = torch.full((b,), step)`)
-__global__ __launch_bounds__(256) void base_set_timestep_kernel(const moca_fifo_state* __restrict__ st, const int64_t* __restrict__ table,
-                                                                int S, int64_t* __restrict__ rows, int n) {
-    const int64_t t = table[S - 1 - st->iter % S];
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) rows[i] = t;
-}
-
-// guidance (ddim.py:304) + the tail of p_sample_ddim (ddim.py:328-357, as ddim_update_kernel) with the coefficients of schedule
-// index S - 1 - i: coef[idx] = {sqrt(a_t), sqrt(a_prev), sigma_t, sqrt(1 - a_t), sqrt(1 - a_prev - sigma_t^2), scale_t, scale_prev, -}.
-// x is updated IN PLACE (it is the UNet plan's input buffer: the next step reads it there).
-__global__ __launch_bounds__(256) void base_step_kernel(const moca_fifo_state* __restrict__ st, float* __restrict__ x,
-                                                        const float* __restrict__ eps_c, const float* __restrict__ eps_u,
-                                                        const float* __restrict__ noise, float* __restrict__ pred_x0,
-                                                        const float* __restrict__ coef, int S, float cfg_scale, int use_scale, int64_t n) {
-    const float* cf = coef + (int64_t)(S - 1 - st->iter % S) * 8;
-    const float sqrt_at = cf[0], sqrt_aprev = cf[1], sigma_t = cf[2], s1m = cf[3], dir_coef = cf[4], scale_t = cf[5], scale_prev = cf[6];
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float et = eps_c[i];
-        if (eps_u) {
-            const float u = eps_u[i];
-            et = u + cfg_scale * (et - u);                      // :304
-        }
-        float p0 = (x[i] - s1m * et) / sqrt_at;                 // :339
-        const float dir = dir_coef * et;                        // :343
-        const float nz = sigma_t * noise[i];                    // :345
-        float xp;
-        if (use_scale) {
-            p0 = p0 / scale_t;                                  // :353
-            xp = sqrt_aprev * scale_prev * p0 + dir + nz;       // :354
-        } else {
-            xp = sqrt_aprev * p0 + dir + nz;                    // :356
-        }
-        x[i] = xp;
-        if (pred_x0) pred_x0[i] = p0;
-    }
-}
-
-__global__ void state_bump_kernel(moca_fifo_state* st) {
-    st->iter = st->iter + 1;
-    st->ext_noise = 0;
-}
-
-__global__ __launch_bounds__(256) void mask_frame_sums_kernel(const float* __restrict__ mask, float* __restrict__ sums, int HW) {
-    __shared__ float red[4];
-    const int fm = blockIdx.x;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < HW; i += 256) s += mask[(int64_t)fm * HW + i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[fm] = red[0] + red[1] + red[2] + red[3];
 }
 
 // funcs.py:53-79: queue frame j = sqrt(a_j) z[frame_idx_j] + sqrt(1 - a_j) noise_j, all B videos; coefficients come from the host,
@@ -327,13 +330,6 @@ __global__ __launch_bounds__(256) void sam_select_kernel(const float* __restrict
     }
 }
 
-inline int grid_for(int64_t total) {
-    int64_t g = (total + 255) / 256;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
 
 extern "C" int moca_fifo_randn_f32(const moca_fifo_state* state, float* out, int64_t n, void* stream) {
@@ -398,29 +394,32 @@ extern "C" int moca_fifo_prepare_queue_f32(const float* z, const float* noise, f
     return MOCA_OK;
 }
 
-extern "C" int moca_base_set_timestep(const moca_fifo_state* state, const int64_t* table, int32_t S, int64_t* rows, int32_t n, void* stream) {
-    if (!state || !table || !rows || S <= 0 || n <= 0) return MOCA_E_BADARG;
-    hipLaunchKernelGGL(base_set_timestep_kernel, dim3(grid_for(n)), dim3(256), 0, moca_stream(stream), state, table, S, rows, n);
-    MOCA_CHECK_LAUNCH();
-    return MOCA_OK;
-}
-
-extern "C" int moca_base_ddim_step_f32(moca_fifo_state* state, float* x, const float* eps_c, const float* eps_u, const float* noise,
-                                       float* pred_x0, const float* coef, int32_t S, float cfg_scale, int32_t use_scale, int64_t n,
+extern "C" int moca_fifo_ddim_step_f32(const float* sample, const float* eps, const float* noise,
+                                       float* momentum, float* x_prev, float* pred_x0,
+                                       const float* coef, const float* mask, const float* cond,
+                                       const int32_t* mask_index, const float* enh, float* ws,
+                                       int32_t B, int32_t C, int32_t F, int32_t Fm, int32_t HW,
+                                       float beta, float one_minus_beta, float gamma, float one_minus_gamma,
                                        void* stream) {
-    if (!state || !x || !eps_c || !noise || !coef || S <= 0 || n <= 0) return MOCA_E_BADARG;
+    if (!sample || !eps || !noise || !momentum || !x_prev || !pred_x0 || !coef) return MOCA_E_BADARG;
+    if (B <= 0 || C <= 0 || F <= 0 || HW <= 0) return MOCA_E_BADARG;
+    if (mask && (Fm <= 0 || !mask_index || !enh || !ws)) return MOCA_E_BADARG;
     hipStream_t st = moca_stream(stream);
-    hipLaunchKernelGGL(base_step_kernel, dim3(grid_for(n)), dim3(256), 0, st, state, x, eps_c, eps_u, noise, pred_x0, coef, S, cfg_scale,
-                       use_scale, n);
-    MOCA_CHECK_LAUNCH();
-    hipLaunchKernelGGL(state_bump_kernel, dim3(1), dim3(1), 0, st, state);
+    if (mask) {
+        hipLaunchKernelGGL(mask_sum_kernel, dim3(Fm), dim3(256), 0, st, mask, ws, B, Fm, HW);
+        MOCA_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(fifo_step_kernel, dim3(grid_for((int64_t)B * C * HW)), dim3(256), 0, st, sample, eps, noise, momentum,
+                       x_prev, pred_x0, coef, mask, ws, cond, mask_index, enh, B, C, F, Fm, HW, beta, one_minus_beta,
+                       gamma, one_minus_gamma);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }
 
+// the mask queue's per-frame sums: mask_sum_kernel over one "batch" of `frames` frames
 extern "C" int moca_mask_frame_sums_f32(const float* mask, float* sums, int32_t frames, int32_t HW, void* stream) {
     if (!mask || !sums || frames <= 0 || HW <= 0) return MOCA_E_BADARG;
-    hipLaunchKernelGGL(mask_frame_sums_kernel, dim3(frames), dim3(256), 0, moca_stream(stream), mask, sums, HW);
+    hipLaunchKernelGGL(mask_sum_kernel, dim3(frames), dim3(256), 0, moca_stream(stream), mask, sums, 1, frames, HW);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }

@@ -93,13 +93,6 @@ __global__ __launch_bounds__(256) void filter_kernel(float* __restrict__ lpf, in
     }
 }
 
-inline int grid_for(int64_t total) {
-    int64_t g = (total + 255) / 256;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace
 
 extern "C" int64_t moca_freq_mix_ws_bytes(int32_t C, int32_t T, int32_t H, int32_t W) {

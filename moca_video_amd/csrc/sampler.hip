@@ -1,17 +1,36 @@
-// fp32 sampler arithmetic of the DDIM / FIFO / MoCA step (lvdm/models/samplers/ddim.py).
-// Compiled with -ffp-contract=off: the reference evaluates these expressions as separate
-// fp32 torch ops (mul, sub, div ...), so no FMA contraction here keeps results within
-// an ulp of the CPU path.  HBM-bound, one thread per latent element.
+// fp32 step arithmetic of ONE trajectory (lvdm/models/samplers/ddim.py, lvdm/models/ddpm3d.py): guidance, the DDIM update as a
+// host-parameterised call and as the device-resident base-sampling step, the encoder's Gaussian sample, q_sample and the DDPM step.
+// The MoCA FIFO (ring queue, windows, per-frame recurrence) is fifo.hip.  No FMA contraction (step_math.h, and -ffp-contract=off in
+// the Makefile): the reference evaluates these expressions as separate fp32 torch ops (mul, sub, div ...), and the results are
+// compared bit for bit.  HBM-bound, one thread per latent element or group of four.
 #include "common.h"
+#include "step_math.h"
 
 namespace {
 
 __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restrict__ ec, const float* __restrict__ eu,
                                                           float* __restrict__ out, float scale, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float u = eu[i];
-        out[i] = u + scale * (ec[i] - u);   // ddim.py:304,372
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        out[i] = cfg_guidance(ec[i], eu[i], scale);   // ddim.py:304,372
+}
+
+// the tail of p_sample_ddim (ddim.py:339-356) for one element
+struct ddim_coef {
+    float sqrt_at, sqrt_aprev, sigma_t, sqrt_one_minus_at, dir_coef, scale_t, scale_prev;
+};
+
+__device__ __forceinline__ void ddim_tail(float x, float et, float noise, const ddim_coef& k, int use_scale, float& x_prev,
+                                          float& pred_x0) {
+    float p0 = (x - k.sqrt_one_minus_at * et) / k.sqrt_at;     // ddim.py:339
+    const float dir = k.dir_coef * et;                          // :343
+    const float nz = k.sigma_t * noise;                         // :345
+    if (use_scale) {
+        p0 = p0 / k.scale_t;                                    // :353
+        x_prev = k.sqrt_aprev * k.scale_prev * p0 + dir + nz;   // :354
+    } else {
+        x_prev = k.sqrt_aprev * p0 + dir + nz;                  // :356
     }
+    pred_x0 = p0;
 }
 
 __global__ __launch_bounds__(256) void ddim_update_kernel(const float* __restrict__ x, const float* __restrict__ e,
@@ -19,88 +38,47 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(const float* __restric
                                                           float* __restrict__ pred_x0, float sqrt_at, float sqrt_aprev,
                                                           float sigma_t, float sqrt_one_minus_at, float dir_coef,
                                                           int use_scale, float scale_t, float scale_prev, int64_t n) {
+    const ddim_coef k = {sqrt_at, sqrt_aprev, sigma_t, sqrt_one_minus_at, dir_coef, scale_t, scale_prev};
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float et = e[i];
-        float p0 = (x[i] - sqrt_one_minus_at * et) / sqrt_at;   // ddim.py:339
-        const float dir = dir_coef * et;                        // :343
-        const float nz = sigma_t * noise[i];                    // :345
-        float xp;
-        if (use_scale) {
-            p0 = p0 / scale_t;                                  // :353
-            xp = sqrt_aprev * scale_prev * p0 + dir + nz;       // :354
-        } else {
-            xp = sqrt_aprev * p0 + dir + nz;                    // :356
-        }
+        float xp, p0;
+        ddim_tail(x[i], e[i], noise[i], k, use_scale, xp, p0);
         x_prev[i] = xp;
         pred_x0[i] = p0;
     }
 }
 
-// sum of each mask frame over (batch, pixels): ddim.py:585 `if mask.sum() != 0`
-__global__ __launch_bounds__(256) void mask_sum_kernel(const float* __restrict__ mask, float* __restrict__ sums,
-                                                       int B, int Fm, int HW) {
-    __shared__ float red[4];
-    const int fm = blockIdx.x;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < B * HW; i += 256) {
-        const int b = i / HW, p = i - b * HW;
-        s += mask[((int64_t)b * Fm + fm) * HW + p];
-    }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[fm] = red[0] + red[1] + red[2] + red[3];
+// ---- base sampling (ddim.py:226-252): one DDIM step of `ddim_sampling` as device-side work.  Step i of the loop uses schedule
+// index S - 1 - i (ddim.py:238); i = state->iter mod S, so a captured step replays for every i.
+// rows[0:n] = table[S - 1 - i]: the timestep rows of the UNet plan (ddim.py:239 `ts = torch.full((b,), step)`)
+__global__ __launch_bounds__(256) void base_set_timestep_kernel(const moca_fifo_state* __restrict__ st, const int64_t* __restrict__ table,
+                                                                int S, int64_t* __restrict__ rows, int n) {
+    const int64_t t = table[S - 1 - st->iter % S];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) rows[i] = t;
 }
 
-// MoCA FIFO step, ddim.py:405-430,556-609.  coef[i] = {sqrt(a_t), sqrt(a_prev), sigma_t,
-// sqrt(1-a_t), sqrt(1-a_prev-sigma^2), 2(1 - ts/1000)}.  One thread per (b, c, pixel);
-// the frame axis is walked sequentially (momentum EMA + previous-frame dependence).
-__global__ __launch_bounds__(256) void fifo_step_kernel(
-    const float* __restrict__ sample, const float* __restrict__ eps, const float* __restrict__ noise,
-    float* __restrict__ momentum, float* __restrict__ x_prev, float* __restrict__ pred_x0,
-    const float* __restrict__ coef, const float* __restrict__ mask, const float* __restrict__ mask_sums,
-    const float* __restrict__ cond, const int32_t* __restrict__ mask_index, const float* __restrict__ enh,
-    int B, int C, int F, int Fm, int HW, float beta, float one_minus_beta, float gamma, float one_minus_gamma) {
-    const int64_t total = (int64_t)B * C * HW;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int p = (int)(i % HW);
-        const int64_t bc = i / HW;
-        const int b = (int)(bc / C);
-        const int64_t base = bc * F * HW + p;   // element (b,c,frame 0,p); frame stride HW
-        float prev = 0.f, mom_prev = momentum[base];   // momentum[:, :, 0] is never written (stays at its initial value)
-        const float cnd = cond ? cond[bc * HW + p] : 0.f;
-        for (int f = 0; f < F; ++f) {
-            const float* cf = coef + f * 6;
-            const int64_t o = base + (int64_t)f * HW;
-            const float et = eps[o];
-            float p0 = (sample[o] - cf[3] * et) / cf[0];        // :415
-            const float dir = cf[4] * et;                       // :418
-            if (f >= 1) {
-                float g = p0 - prev;                            // :422
-                g = g + 1.5f * dir;                             // :423
-                const float m = beta * mom_prev + one_minus_beta * g;   // :424-427
-                momentum[o] = m;
-                mom_prev = m;
-                p0 = p0 + cf[5] * m;                            // :428-430,557
-            }
-            prev = p0;                                          // :559
-            const float nz = cf[2] * noise[o];                  // :561
-            x_prev[o] = cf[1] * p0 + dir + nz;                  // :562
-            const int mi = mask_index ? mask_index[f] : -1;
-            if (mi >= 0 && mask && mask_sums[mi] != 0.f) {      // :565-590
-                const float mk = mask[((int64_t)b * Fm + mi) * HW + p];
-                if (mk > 0.5f) p0 = cnd * enh[f];
-            }
-            pred_x0[o] = one_minus_gamma * p0 + gamma * nz;     // :609
-        }
+// guidance (ddim.py:304) + the tail of p_sample_ddim (ddim.py:328-357, as ddim_update_kernel) with the coefficients of schedule
+// index S - 1 - i: coef[idx] = {sqrt(a_t), sqrt(a_prev), sigma_t, sqrt(1 - a_t), sqrt(1 - a_prev - sigma_t^2), scale_t, scale_prev, -}.
+// x is updated IN PLACE (it is the UNet plan's input buffer: the next step reads it there).
+__global__ __launch_bounds__(256) void base_step_kernel(const moca_fifo_state* __restrict__ st, float* __restrict__ x,
+                                                        const float* __restrict__ eps_c, const float* __restrict__ eps_u,
+                                                        const float* __restrict__ noise, float* __restrict__ pred_x0,
+                                                        const float* __restrict__ coef, int S, float cfg_scale, int use_scale, int64_t n) {
+    const float* cf = coef + (int64_t)(S - 1 - st->iter % S) * 8;
+    const ddim_coef k = {cf[0], cf[1], cf[2], cf[3], cf[4], cf[5], cf[6]};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float et = eps_c[i];
+        if (eps_u) et = cfg_guidance(et, eps_u[i], cfg_scale);  // :304
+        float xp, p0;
+        ddim_tail(x[i], et, noise[i], k, use_scale, xp, p0);
+        x[i] = xp;
+        if (pred_x0) pred_x0[i] = p0;
     }
 }
 
-inline int grid_for(int64_t total) {
-    int64_t g = (total + 255) / 256;
-    if (g > 4096) g = 4096;
-    if (g < 1) g = 1;
-    return (int)g;
+// the end of a trajectory step (base sampling, DDPM): the next replay of the captured step sees the next schedule index
+__global__ void state_bump_kernel(moca_fifo_state* st) {
+    st->iter = st->iter + 1;
+    st->ext_noise = 0;
 }
 
 // ---- DiagonalGaussianDistribution.sample / .mode (lvdm/distributions.py:24-40) + get_first_stage_encoding's scale_factor
@@ -122,13 +100,49 @@ __global__ void gaussian_sample_kernel(const float* __restrict__ mom, const floa
     }
 }
 
+// ---- the walk of q_sample_kernel and ddpm_step_kernel: one thread per group of four consecutive elements of the FLAT [B * per]
+// range, each sample with its own coefficients.  A group that lies inside one sample (and every pointer being 16-byte aligned) moves
+// as float4; a group that straddles two samples (per % 4 != 0) or the end goes element by element -- nothing is read or written past
+// B * per.
+struct group4 {
+    int64_t e0, b0;   // first element, its sample
+    int cnt;          // elements inside [0, total)
+    bool vec;         // whole, inside sample b0, pointers aligned
+};
+
+__device__ __forceinline__ group4 group4_at(int64_t q, int64_t total, int64_t per, int vec_ok) {
+    group4 g;
+    g.e0 = q * 4;
+    g.b0 = g.e0 / per;
+    g.cnt = total - g.e0 < 4 ? (int)(total - g.e0) : 4;
+    g.vec = vec_ok && g.cnt == 4 && (g.e0 + 3) / per == g.b0;
+    return g;
+}
+
+// p NULL: v keeps what it holds / nothing is stored
+__device__ __forceinline__ void group4_ld(const float* p, int64_t e0, bool vec, int cnt, float (&v)[4]) {
+    if (!p) return;
+    if (vec) {
+        const float4 q = *reinterpret_cast<const float4*>(p + e0);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+        for (int j = 0; j < cnt; ++j) v[j] = p[e0 + j];
+    }
+}
+
+__device__ __forceinline__ void group4_st(float* p, int64_t e0, bool vec, int cnt, const float (&v)[4]) {
+    if (!p) return;
+    if (vec) {
+        *reinterpret_cast<float4*>(p + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int j = 0; j < cnt; ++j) p[e0 + j] = v[j];
+    }
+}
+
 // q_sample over per-sample schedule indices (ddim.py:652-671 `stochastic_encode`): out[b][p] = ca[t[b]] * x0[b][p] + cb[t[b]] * noise[b][p].
 // The gather of both tables runs here (t and the tables are device memory: nothing for the host to read, the launch can be captured).
-// mul, mul, add with no contraction = the torch expression bit for bit.  One thread per group of four consecutive elements of the FLAT
-// [B * per] range: a group that lies inside one sample (and the pointers being 16-byte aligned) moves as float4, a group that straddles
-// two samples (per % 4 != 0) or the end goes element by element, each with its own sample's coefficients -- nothing is read or written
-// past B * per.  out may alias x0 (every element is read before it is written, by the same thread).  An index outside [0, n_tab) reads
-// no table entry: that sample's output is NaN.
+// mul, mul, add with no contraction = the torch expression bit for bit.  out may alias x0 (every element is read before it is written,
+// by the same thread).  An index outside [0, n_tab) reads no table entry: that sample's output is NaN.
 __device__ __forceinline__ void q_coef(const float* __restrict__ ca, const float* __restrict__ cb, const int64_t* __restrict__ t, int64_t b,
                                        int n_tab, float& a, float& c, bool& bad) {
     const int64_t tb = t[b];
@@ -144,32 +158,26 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* x0, const fl
     const int64_t n4 = (total + 3) / 4;
     const float qnan = __builtin_nanf("");
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
-        const int64_t e0 = q * 4;
-        const int64_t b0 = e0 / per;
-        if (vec_ok && e0 + 3 < total && (e0 + 3) / per == b0) {
-            float a, c;
-            bool bad;
-            q_coef(ca, cb, t, b0, n_tab, a, c, bad);
-            const float4 xv = *reinterpret_cast<const float4*>(x0 + e0);
-            const float4 nv = *reinterpret_cast<const float4*>(noise + e0);
-            float4 o;
-            o.x = a * xv.x + c * nv.x;
-            o.y = a * xv.y + c * nv.y;
-            o.z = a * xv.z + c * nv.z;
-            o.w = a * xv.w + c * nv.w;
-            if (bad) o = make_float4(qnan, qnan, qnan, qnan);
-            *reinterpret_cast<float4*>(out + e0) = o;
-        } else {
-            for (int j = 0; j < 4; ++j) {
-                const int64_t e = e0 + j;
-                if (e >= total) break;
-                float a, c;
-                bool bad;
-                q_coef(ca, cb, t, e / per, n_tab, a, c, bad);
-                const float v = a * x0[e] + c * noise[e];
-                out[e] = bad ? qnan : v;
+        const group4 g = group4_at(q, total, per, vec_ok);
+        float xv[4] = {}, nv[4] = {}, o[4];
+        group4_ld(x0, g.e0, g.vec, g.cnt, xv);
+        group4_ld(noise, g.e0, g.vec, g.cnt, nv);
+        float a, c;
+        bool bad;
+        q_coef(ca, cb, t, g.b0, n_tab, a, c, bad);
+        int64_t b_cur = g.b0;
+        for (int j = 0; j < g.cnt; ++j) {
+            if (!g.vec) {
+                const int64_t b = (g.e0 + j) / per;
+                if (b != b_cur) {
+                    q_coef(ca, cb, t, b, n_tab, a, c, bad);
+                    b_cur = b;
+                }
             }
+            const float v = a * xv[j] + c * nv[j];
+            o[j] = bad ? qnan : v;
         }
+        group4_st(out, g.e0, g.vec, g.cnt, o);
     }
 }
 
@@ -182,9 +190,8 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* x0, const fl
 //   orig = sac x0 [scale] + s1mac noise_q                   :415-420
 //   out = orig mask + (1 - mask) out                        :648
 // mul / add / sub only and no contraction: bit-equal to the torch expression over the same tables.  coef[t] = {srac, srm1, c1, c2,
-// std, sac, s1mac, scale}.  eps_c NULL: no reverse step, out = orig (`q_sample`).  Groups of four consecutive elements of the flat
-// [B * per] range as in q_sample_kernel: float4 where the group lies inside one sample and every pointer is 16-byte aligned, element
-// by element otherwise; out may alias x (each thread reads all it needs before it writes).  t_b outside [0, n_tab): nothing is read
+// std, sac, s1mac, scale}.  eps_c NULL: no reverse step, out = orig (`q_sample`).  Groups of four as above (vec_ok: every pointer
+// is 16-byte aligned); out may alias x (each thread reads all it needs before it writes).  t_b outside [0, n_tab): nothing is read
 // from the table and every output of sample b is NaN.
 struct ddpm_args {
     const float* x; float* out; const float* eps_c; const float* eps_u; const float* noise; float* x_recon; float* mean;
@@ -212,25 +219,6 @@ __device__ __forceinline__ ddpm_coef ddpm_load_coef(const ddpm_args& a, int64_t 
     return k;
 }
 
-__device__ __forceinline__ void ddpm_ld(const float* p, int64_t e0, bool vec, int cnt, float (&v)[4]) {
-    if (!p) return;
-    if (vec) {
-        const float4 q = *reinterpret_cast<const float4*>(p + e0);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        for (int j = 0; j < cnt; ++j) v[j] = p[e0 + j];
-    }
-}
-
-__device__ __forceinline__ void ddpm_st(float* p, int64_t e0, bool vec, int cnt, const float (&v)[4]) {
-    if (!p) return;
-    if (vec) {
-        *reinterpret_cast<float4*>(p + e0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        for (int j = 0; j < cnt; ++j) p[e0 + j] = v[j];
-    }
-}
-
 __global__ __launch_bounds__(256) void ddpm_step_kernel(const ddpm_args a) {
     const int64_t per = a.per, total = (int64_t)a.B * per;
     const int64_t n4 = (total + 3) / 4;
@@ -238,22 +226,22 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const ddpm_args a) {
     const bool x0_param = a.flags & MOCA_DDPM_X0, clip = a.flags & MOCA_DDPM_CLIP, use_scale = a.flags & MOCA_DDPM_SCALE;
     const bool blend = a.eps_c && a.mask;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
-        const int64_t e0 = q * 4;
-        const int64_t b0 = e0 / per;
-        const int cnt = total - e0 < 4 ? (int)(total - e0) : 4;
-        const bool vec = a.vec_ok && cnt == 4 && (e0 + 3) / per == b0;
+        const group4 g = group4_at(q, total, per, a.vec_ok);
+        const int64_t e0 = g.e0, b0 = g.b0;
+        const int cnt = g.cnt;
+        const bool vec = g.vec;
         float x[4] = {}, ec[4] = {}, eu[4] = {}, nz[4] = {}, mk[4] = {}, x0[4] = {}, nq[4] = {}, o[4], rc[4], mn[4];
-        ddpm_ld(a.x, e0, vec, cnt, x);
-        ddpm_ld(a.eps_c, e0, vec, cnt, ec);
-        ddpm_ld(a.eps_u, e0, vec, cnt, eu);
-        if (a.out) ddpm_ld(a.noise, e0, vec, cnt, nz);
-        ddpm_ld(a.x0, e0, vec, cnt, x0);
-        ddpm_ld(a.noise_q, e0, vec, cnt, nq);
+        group4_ld(a.x, e0, vec, cnt, x);
+        group4_ld(a.eps_c, e0, vec, cnt, ec);
+        group4_ld(a.eps_u, e0, vec, cnt, eu);
+        if (a.out) group4_ld(a.noise, e0, vec, cnt, nz);
+        group4_ld(a.x0, e0, vec, cnt, x0);
+        group4_ld(a.noise_q, e0, vec, cnt, nq);
         if (blend) {
             if (!(a.flags & MOCA_DDPM_MASK_C0)) {
-                ddpm_ld(a.mask, e0, vec, cnt, mk);
+                group4_ld(a.mask, e0, vec, cnt, mk);
             } else if (vec && a.mask_vec) {                     // per % 4 == 0 and inner % 4 == 0: the group stays inside one channel
-                ddpm_ld(a.mask, b0 * a.mask_inner + (e0 - b0 * per) % a.mask_inner, true, 4, mk);
+                group4_ld(a.mask, b0 * a.mask_inner + (e0 - b0 * per) % a.mask_inner, true, 4, mk);
             } else {
                 for (int j = 0; j < cnt; ++j) {
                     const int64_t b = (e0 + j) / per;
@@ -281,7 +269,7 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const ddpm_args a) {
             rc[j] = mn[j] = qnan;
             if (a.eps_c) {
                 float e = ec[j];
-                if (a.eps_u) e = eu[j] + a.cfg_scale * (e - eu[j]);            // ddim.py:304
+                if (a.eps_u) e = cfg_guidance(e, eu[j], a.cfg_scale);         // ddim.py:304
                 float r = x0_param ? e : k.srac * x[j] - k.srm1 * e;          // :573-576
                 if (clip) r = r < -1.f ? -1.f : (r > 1.f ? 1.f : r);          // :581 (NaN stays NaN, as clamp_)
                 const float m = k.c1 * r + k.c2 * x[j];                       // :219-222
@@ -294,15 +282,10 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const ddpm_args a) {
             }
             o[j] = k.bad ? qnan : v;
         }
-        ddpm_st(a.out, e0, vec, cnt, o);
-        ddpm_st(a.x_recon, e0, vec, cnt, rc);
-        ddpm_st(a.mean, e0, vec, cnt, mn);
+        group4_st(a.out, e0, vec, cnt, o);
+        group4_st(a.x_recon, e0, vec, cnt, rc);
+        group4_st(a.mean, e0, vec, cnt, mn);
     }
-}
-
-__global__ void ddpm_state_bump_kernel(moca_fifo_state* st) {
-    st->iter = st->iter + 1;
-    st->ext_noise = 0;
 }
 
 }  // namespace
@@ -329,24 +312,22 @@ extern "C" int moca_ddim_update_f32(const float* x, const float* e, const float*
     return MOCA_OK;
 }
 
-extern "C" int moca_fifo_ddim_step_f32(const float* sample, const float* eps, const float* noise,
-                                       float* momentum, float* x_prev, float* pred_x0,
-                                       const float* coef, const float* mask, const float* cond,
-                                       const int32_t* mask_index, const float* enh, float* ws,
-                                       int32_t B, int32_t C, int32_t F, int32_t Fm, int32_t HW,
-                                       float beta, float one_minus_beta, float gamma, float one_minus_gamma,
+extern "C" int moca_base_set_timestep(const moca_fifo_state* state, const int64_t* table, int32_t S, int64_t* rows, int32_t n, void* stream) {
+    if (!state || !table || !rows || S <= 0 || n <= 0) return MOCA_E_BADARG;
+    hipLaunchKernelGGL(base_set_timestep_kernel, dim3(grid_for(n)), dim3(256), 0, moca_stream(stream), state, table, S, rows, n);
+    MOCA_CHECK_LAUNCH();
+    return MOCA_OK;
+}
+
+extern "C" int moca_base_ddim_step_f32(moca_fifo_state* state, float* x, const float* eps_c, const float* eps_u, const float* noise,
+                                       float* pred_x0, const float* coef, int32_t S, float cfg_scale, int32_t use_scale, int64_t n,
                                        void* stream) {
-    if (!sample || !eps || !noise || !momentum || !x_prev || !pred_x0 || !coef) return MOCA_E_BADARG;
-    if (B <= 0 || C <= 0 || F <= 0 || HW <= 0) return MOCA_E_BADARG;
-    if (mask && (Fm <= 0 || !mask_index || !enh || !ws)) return MOCA_E_BADARG;
+    if (!state || !x || !eps_c || !noise || !coef || S <= 0 || n <= 0) return MOCA_E_BADARG;
     hipStream_t st = moca_stream(stream);
-    if (mask) {
-        hipLaunchKernelGGL(mask_sum_kernel, dim3(Fm), dim3(256), 0, st, mask, ws, B, Fm, HW);
-        MOCA_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(fifo_step_kernel, dim3(grid_for((int64_t)B * C * HW)), dim3(256), 0, st, sample, eps, noise, momentum,
-                       x_prev, pred_x0, coef, mask, ws, cond, mask_index, enh, B, C, F, Fm, HW, beta, one_minus_beta,
-                       gamma, one_minus_gamma);
+    hipLaunchKernelGGL(base_step_kernel, dim3(grid_for(n)), dim3(256), 0, st, state, x, eps_c, eps_u, noise, pred_x0, coef, S, cfg_scale,
+                       use_scale, n);
+    MOCA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(state_bump_kernel, dim3(1), dim3(1), 0, st, state);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }
@@ -354,10 +335,8 @@ extern "C" int moca_fifo_ddim_step_f32(const float* sample, const float* eps, co
 extern "C" int moca_gaussian_sample_f32(const float* moments, const float* noise, float* out, int32_t n, int32_t z, int32_t hw,
                                         float scale, void* stream) {
     if (!moments || !out || n <= 0 || z <= 0 || hw <= 0) return MOCA_E_BADARG;
-    const int64_t total = (int64_t)n * z * hw;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(gaussian_sample_kernel, dim3(blocks), dim3(256), 0, moca_stream(stream), moments, noise, out, n, z, hw, scale);
+    hipLaunchKernelGGL(gaussian_sample_kernel, dim3(grid_for((int64_t)n * z * hw)), dim3(256), 0, moca_stream(stream), moments, noise, out,
+                       n, z, hw, scale);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }
@@ -404,7 +383,7 @@ extern "C" int moca_ddpm_step_f32(moca_fifo_state* state, const float* x, float*
     hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for(n4)), dim3(256), 0, st, a);
     MOCA_CHECK_LAUNCH();
     if (state) {
-        hipLaunchKernelGGL(ddpm_state_bump_kernel, dim3(1), dim3(1), 0, st, state);
+        hipLaunchKernelGGL(state_bump_kernel, dim3(1), dim3(1), 0, st, state);
         MOCA_CHECK_LAUNCH();
     }
     return MOCA_OK;

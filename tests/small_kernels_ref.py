@@ -34,8 +34,8 @@ import math
 
 import torch
 
-# csrc/elementwise.hip grid_for(): `if (g > 4096) g = 4096;` blocks of 256 threads (the same function in csrc/sampler.hip and
-# csrc/freeinit.hip; moca_gaussian_sample_f32 spells it `if (blocks > 4096) blocks = 4096;`): more work items than this and a thread loops
+# csrc/common.h grid_for(): `if (g > 4096) g = 4096;` blocks of 256 threads, the one definition that csrc/elementwise.hip, sampler.hip,
+# fifo.hip and freeinit.hip launch with (moca_gaussian_sample_f32 included): more work items than this and a thread loops
 GRID_CAP = 4096 * 256
 # csrc/runtime.hip moca_memset_zero(): `if (blocks > 1024) blocks = 1024;` blocks of 256 threads, one 16-byte chunk per trip
 ZERO_CAP = 1024 * 256

@@ -1,6 +1,7 @@
 """References, case tables and comparison standards of tests/test_step_kernels_cpu.py and tests/test_step_kernels_gpu.py: the device-side
-sampling step -- all of csrc/fifo.hip, the MoCA recurrence (fifo_step_kernel / mask_sum_kernel) of csrc/sampler.hip and the frequency
-filters (filter_kernel) of csrc/freeinit.hip.
+sampling step -- all of csrc/fifo.hip (the MoCA recurrence of one call's windows, fifo_step_kernel / mask_sum_kernel, included), the
+base-sampling step (base_set_timestep_kernel / base_step_kernel / state_bump_kernel) of csrc/sampler.hip and the frequency filters
+(filter_kernel) of csrc/freeinit.hip.
 
 Every operation is restated in plain torch from the reference's formula (the ddim.py / funcs.py / freeinit_utils.py lines the kernel
 comments cite), op by op in the reference's order, with the dtype as a parameter.  These translation units are built with

@@ -530,7 +530,10 @@ def test_fifo_randn_kernel_is_philox_box_muller():
 
 def test_fifo_step_windows_equals_per_window_kernel():
     """moca_fifo_step_windows_f32 (guidance + step of all windows + ring write-back, head != 0) == moca_cfg_combine_f32 +
-    moca_fifo_ddim_step_f32 per window + the reference's slice assignment, bit for bit; then the advance"""
+    moca_fifo_ddim_step_f32 per window + the reference's slice assignment, bit for bit; then the advance.  Both kernels call the one
+    per-frame recurrence of csrc/fifo.hip (`moca_frame_step`), so this comparison checks what differs between them -- indexing,
+    guidance, ring write-back, masks; the independent reference of the recurrence itself is the torch restatement of
+    test_step_kernels_gpu.py (`test_moca_step`, `test_step_windows`)"""
     import ctypes as C
     from moca_video_amd import lib as L
     from moca_video_amd.sampler import DDIMSampler

@@ -178,8 +178,11 @@ def test_fp32_kernels_reference():
     # the caps are what the sources say
     import os
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "moca_video_amd", "csrc")
-    for f in ("elementwise.hip", "sampler.hip", "freeinit.hip"):
-        assert "if (g > 4096) g = 4096;" in open(os.path.join(csrc, f)).read(), f
+    common = open(os.path.join(csrc, "common.h")).read()
+    assert common.count("if (g > 4096) g = 4096;") == 1 and common.count("int grid_for(") == 1
+    for f in ("elementwise.hip", "sampler.hip", "fifo.hip", "freeinit.hip"):          # ... once: every launch goes through common.h's
+        s = open(os.path.join(csrc, f)).read()
+        assert "grid_for(" in s and "int grid_for" not in s and "4096" not in s, f
     assert "if (blocks > 1024) blocks = 1024;" in open(os.path.join(csrc, "runtime.hip")).read()
 
 

@@ -1,4 +1,5 @@
-"""GPU: the device-side sampling step -- all of csrc/fifo.hip, the MoCA recurrence (fifo_step_kernel / mask_sum_kernel) of
+"""GPU: the device-side sampling step -- all of csrc/fifo.hip (the MoCA recurrence of one call's windows, fifo_step_kernel /
+mask_sum_kernel, included), the base-sampling step (base_set_timestep_kernel / base_step_kernel / state_bump_kernel) of
 csrc/sampler.hip, filter_kernel of csrc/freeinit.hip -- element by element against the restatements of tests/step_kernels_ref.py: at
 HW below, at and above a wave and a block, at the ring's wrap (head = Q - 1, windows that straddle the ring end), at iter >= S and
 iter >= n_slots, with every optional pointer NULL once, and past the grid cap (4096 blocks of 256 work items: a thread makes a
