@@ -557,7 +557,18 @@ int moca_fifo_prepare_queue_f32(const float* z, const float* noise, float* queue
  * moca_base_set_timestep: rows[0:n] = table[S - 1 - i] (`ts = torch.full((b,), step)`, :239; table = ddim_timesteps as int64).
  * moca_base_ddim_step_f32: guidance e_u + s (e_c - e_u) (:304; eps_u NULL: none) + the tail of p_sample_ddim (:328-357) with
  *   coef[idx][8] = {sqrt(a_t), sqrt(a_prev), sigma_t, sqrt(1-a_t), sqrt(1-a_prev-sigma_t^2), scale_t, scale_prev, -} (host,
- *   fp32 like the reference's tensors); x [n] is updated IN PLACE to x_prev, pred_x0 optional; then iter += 1, ext_noise = 0. */
+ *   fp32 like the reference's tensors); x [n] is updated IN PLACE to x_prev, pred_x0 optional; then iter += 1, ext_noise = 0.
+ *   `use_scale` is a flag word.  MOCA_BASE_SCALE (bit 0, what the parameter always was): pred_x0 is divided by scale_t and x_prev
+ *   multiplied by scale_prev (:353-354).  MOCA_BASE_MULTISTEP (bit 1): the step is one DPM-Solver++(2M) update (Lu et al., 2022) in
+ *   place of the DDIM tail, on a second row layout
+ *     coef[idx][8] = {sqrt(a_t), c_0, c_1, sqrt(1-a_t), c_x, scale_t, -, -}      (built by the host in float64, rounded to fp32 once)
+ *     p0 = (x - sqrt(1-a_t) eps) / sqrt(a_t) [/ scale_t]                         (the DDIM tail's pred_x0, bit for bit)
+ *     x  = (c_x x + c_0 p0) + c_1 (p0 - hist)                                    (fp32, in this order, no contraction)
+ *   where `pred_x0` is the HISTORY operand and therefore required (NULL: MOCA_E_BADARG): on entry the previous step's p0, on exit this
+ *   step's.  A row with c_1 == 0 -- the first step of a trajectory, a first-order last step, an identity row -- does not read the
+ *   history: it may hold anything, NaN included.  `noise` must be non-NULL as always and is not read.  Other bits are ignored. */
+#define MOCA_BASE_SCALE 1
+#define MOCA_BASE_MULTISTEP 2
 int moca_base_set_timestep(const moca_fifo_state* state, const int64_t* table, int32_t S, int64_t* rows, int32_t n, void* stream);
 int moca_base_ddim_step_f32(moca_fifo_state* state, float* x, const float* eps_c, const float* eps_u, const float* noise,
                             float* pred_x0, const float* coef, int32_t S, float cfg_scale, int32_t use_scale, int64_t n, void* stream);

@@ -14,6 +14,8 @@ Public surface mirrors the reference interfaces for this path only:
   v2v_ddim_sampling    DDIMSampler.stochastic_encode + decode (ddim.py:652-692): noise a clip's latents, denoise under a new prompt
   v2v_invert_sampling  DDIMSampler.encode + decode: the clip's own DDIM inversion in place of the noising, then denoise under a new prompt
   freeinit_ddim_sampling   FreeInit (Wu et al., 2023) over base_ddim_sampling: re-noise with the initial noise, freq_mix_3d, sample again
+  DPMSolverSampler     DPM-Solver++(2M) (Lu et al., 2022) on DDIMSampler's timestep grid and one-graph step; no counterpart in the reference
+  dpm_solver_sampling, v2v_dpm_solver_sampling   base_ddim_sampling / v2v_ddim_sampling with that solver (20 steps where DDIM takes 50)
   load_multiprompts, run_multiprompts  its prompt file and driver (moca_video_amd.io)
   instantiate_from_config       utils/utils.py:27-42
   AutoencoderKL                 lvdm/models/autoencoder.py:13-107 + lvdm/modules/networks/ae_modules.py:364-579
@@ -37,8 +39,11 @@ from .image_proj import ImageProjModel, Resampler  # noqa: E402
 from .clip_vision import FrozenOpenCLIPImageEmbedder, FrozenOpenCLIPImageEmbedderV2  # noqa: E402
 from .wrapper import LatentVisualDiffusion  # noqa: E402
 from .fifo import fifo_ddim_sampling_multiprompts, freeinit_ddim_sampling, v2v_ddim_sampling, v2v_invert_sampling  # noqa: E402
+from .fifo import dpm_solver_sampling, v2v_dpm_solver_sampling  # noqa: E402
+from .sampler import DPMSolverSampler  # noqa: E402
 from .io import load_multiprompts, run_multiprompts  # noqa: E402
 
 __all__ = ["UNetModel", "DiffusionWrapper", "DenoiseModel", "AutoencoderKL", "FrozenOpenCLIPEmbedder", "SimpleTokenizer", "ImageProjModel", "Resampler",
            "FrozenOpenCLIPImageEmbedder", "FrozenOpenCLIPImageEmbedderV2", "LatentVisualDiffusion", "instantiate_from_config",
-           "load_unet_config", "fifo_ddim_sampling_multiprompts", "v2v_ddim_sampling", "v2v_invert_sampling", "freeinit_ddim_sampling", "load_multiprompts", "run_multiprompts"]
+           "load_unet_config", "fifo_ddim_sampling_multiprompts", "v2v_ddim_sampling", "v2v_invert_sampling", "freeinit_ddim_sampling", "load_multiprompts", "run_multiprompts",
+           "DPMSolverSampler", "dpm_solver_sampling", "v2v_dpm_solver_sampling"]

@@ -75,6 +75,43 @@ __global__ __launch_bounds__(256) void base_step_kernel(const moca_fifo_state* _
     }
 }
 
+// ---- DPM-Solver++(2M) (Lu et al., 2022) on the same table walk: one multistep update in the data-prediction form for one element.
+// p0 is ddim_tail's pred_x0, operation for operation (ddim.py:339,353), so both samplers see the same bits of it.
+struct multistep_coef {
+    float sqrt_at, c0, c1, sqrt_one_minus_at, cx, scale_t;
+};
+
+// x' = (c_x x + c_0 p0) + c_1 (p0 - *hist); a first-order row (c_1 == 0) leaves the history term out and never looks at *hist
+__device__ __forceinline__ void multistep_tail(float x, float et, const float* hist, const multistep_coef& k, int use_scale, float& x_next,
+                                               float& pred_x0) {
+    float p0 = (x - k.sqrt_one_minus_at * et) / k.sqrt_at;     // ddim.py:339
+    if (use_scale) p0 = p0 / k.scale_t;                        // :353
+    float xn = k.cx * x + k.c0 * p0;
+    if (k.c1 != 0.f) xn = xn + k.c1 * (p0 - *hist);
+    x_next = xn;
+    pred_x0 = p0;
+}
+
+// coef[idx] = {sqrt(a_t), c_0, c_1, sqrt(1 - a_t), c_x, scale_t, -, -} (the host's float64 table, rounded once).  `hist` is the history
+// operand: the previous step's pred_x0 on entry, this step's on exit, each element read and written by the same thread.  A row whose
+// c_1 is 0 (the first step of a trajectory, the last one with lower_order_final, order 1) does NOT read it -- the branch is uniform, on
+// the table value -- so that what an earlier trajectory or nobody left there, NaN included, never reaches x.  x is updated IN PLACE.
+__global__ __launch_bounds__(256) void multistep_step_kernel(const moca_fifo_state* __restrict__ st, float* __restrict__ x,
+                                                             const float* __restrict__ eps_c, const float* __restrict__ eps_u,
+                                                             float* hist, const float* __restrict__ coef, int S, float cfg_scale,
+                                                             int use_scale, int64_t n) {
+    const float* cf = coef + (int64_t)(S - 1 - st->iter % S) * 8;
+    const multistep_coef k = {cf[0], cf[1], cf[2], cf[3], cf[4], cf[5]};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float et = eps_c[i];
+        if (eps_u) et = cfg_guidance(et, eps_u[i], cfg_scale);  // :304
+        float xn, p0;
+        multistep_tail(x[i], et, hist + i, k, use_scale, xn, p0);
+        x[i] = xn;
+        hist[i] = p0;
+    }
+}
+
 // the end of a trajectory step (base sampling, DDPM): the next replay of the captured step sees the next schedule index
 __global__ void state_bump_kernel(moca_fifo_state* st) {
     st->iter = st->iter + 1;
@@ -323,9 +360,16 @@ extern "C" int moca_base_ddim_step_f32(moca_fifo_state* state, float* x, const f
                                        float* pred_x0, const float* coef, int32_t S, float cfg_scale, int32_t use_scale, int64_t n,
                                        void* stream) {
     if (!state || !x || !eps_c || !noise || !coef || S <= 0 || n <= 0) return MOCA_E_BADARG;
+    if ((use_scale & MOCA_BASE_MULTISTEP) && !pred_x0) return MOCA_E_BADARG;   // the history operand
     hipStream_t st = moca_stream(stream);
-    hipLaunchKernelGGL(base_step_kernel, dim3(grid_for(n)), dim3(256), 0, st, state, x, eps_c, eps_u, noise, pred_x0, coef, S, cfg_scale,
-                       use_scale, n);
+    const int scale_bit = use_scale & MOCA_BASE_SCALE;
+    if (use_scale & MOCA_BASE_MULTISTEP) {
+        hipLaunchKernelGGL(multistep_step_kernel, dim3(grid_for(n)), dim3(256), 0, st, state, x, eps_c, eps_u, pred_x0, coef, S, cfg_scale,
+                           scale_bit, n);
+    } else {
+        hipLaunchKernelGGL(base_step_kernel, dim3(grid_for(n)), dim3(256), 0, st, state, x, eps_c, eps_u, noise, pred_x0, coef, S, cfg_scale,
+                           scale_bit, n);
+    }
     MOCA_CHECK_LAUNCH();
     hipLaunchKernelGGL(state_bump_kernel, dim3(1), dim3(1), 0, st, state);
     MOCA_CHECK_LAUNCH();

@@ -11,7 +11,7 @@ import torch
 from .conditioning import refuse_concat, refuse_image_attention, refuse_long_window
 from .fifo_graph import FifoEngine, fifo_windows, lookahead_schedule
 from .freeinit import freeinit_steps, freq_mix_3d, get_freq_filter
-from .sampler import DDIMSampler, noise_queue
+from .sampler import DDIMSampler, DPMSolverSampler, noise_queue
 
 
 def prepare_latents(args, input_path, sampler, model=None, data=None, initial_latents=None, noises=None):
@@ -173,6 +173,54 @@ def v2v_ddim_sampling(model, cond, latents=None, frames=None, ddim_steps=50, t_s
     return images, sampler, samples
 
 
+def dpm_solver_sampling(model, cond, noise_shape, steps=20, order=2, cfg_scale=1.0, uc_emb=None, x_T=None, use_graph=True,
+                        lower_order_final=True):
+    """`base_ddim_sampling` with DPM-Solver++(2M) (`DPMSolverSampler`) in place of DDIM: `steps` schedule rows on the same `uniform`
+    grid, steps - 1 UNet forwards (the row at timestep 0 is an identity), deterministic -- `x_T` is the only draw.  Returns
+    (images, sampler, samples) like `base_ddim_sampling`."""
+    sampler = DPMSolverSampler(model, order=order, lower_order_final=lower_order_final)
+    sampler.use_graph = use_graph
+    uc = base_uncond(model, cond, noise_shape[0], cfg_scale, uc_emb)
+    samples, _ = sampler.sample(S=steps, conditioning=cond, batch_size=noise_shape[0], shape=noise_shape[1:], verbose=False,
+                                unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc, x_T=x_T)
+    sampler.release()
+    images = model.decode_first_stage_2DAE(samples) if getattr(model, "first_stage_model", None) is not None else None
+    return images, sampler, samples
+
+
+def v2v_dpm_solver_sampling(model, cond, latents=None, frames=None, steps=20, t_start=10, order=2, cfg_scale=1.0, uc_emb=None, noise=None,
+                            use_graph=True, lower_order_final=True):
+    """`v2v_ddim_sampling` with DPM-Solver++(2M): the clip's latents noised to schedule index `t_start` (`stochastic_encode`; `noise`
+    fixes that draw, the only one), then the multistep `decode` over the first t_start schedule rows.  1 <= t_start <= steps - 1.
+    Returns (images, sampler, samples) like `base_ddim_sampling`."""
+    if (latents is None) == (frames is None):
+        raise ValueError("v2v_dpm_solver_sampling wants exactly one of latents= and frames=")
+    if not 1 <= int(t_start) <= int(steps) - 1:
+        raise ValueError(f"t_start = {t_start}: the clip is encoded at schedule index t_start and decoded over t_start rows, "
+                         f"so 1 <= t_start <= steps - 1 = {int(steps) - 1}")
+    t_start = int(t_start)
+    if frames is not None:
+        latents = model.encode_first_stage_2DAE(frames.to(model.device))
+    x0 = latents.to(model.device)
+    sampler = DPMSolverSampler(model, order=order, lower_order_final=lower_order_final)
+    sampler.use_graph = use_graph
+    sampler.make_schedule(ddim_num_steps=steps, verbose=False)
+    uc = base_uncond(model, cond, x0.shape[0], cfg_scale, uc_emb)
+    x_enc = sampler.stochastic_encode(x0, torch.full((x0.shape[0],), t_start, dtype=torch.long), noise=noise)
+    samples = sampler.decode(x_enc, cond, t_start, unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc)
+    sampler.release()
+    images = model.decode_first_stage_2DAE(samples) if getattr(model, "first_stage_model", None) is not None else None
+    return images, sampler, samples
+
+
+def refuse_multistep(sampler):
+    """the FIFO loops take `DDIMSampler`'s first-order step only"""
+    if getattr(sampler, "multistep", False):
+        raise NotImplementedError(f"{type(sampler).__name__} cannot drive FIFO / MoCA sampling: diagonal denoising holds one queue frame per "
+                                  "schedule level and moves every frame by one level per iteration, which ties the queue length to "
+                                  "first-order steps; a multistep solver would need a history per frame and another queue")
+
+
 def v2v_invert_sampling(model, cond, latents=None, frames=None, ddim_steps=50, t_start=25, ddim_eta=0.0, cfg_scale=1.0, uc_emb=None,
                         src_cond=None, src_cfg_scale=1.0, noises=None, use_graph=True):
     """`v2v_ddim_sampling` with the clip taken to schedule index `t_start` by its own deterministic DDIM inversion
@@ -235,6 +283,7 @@ def fifo_ddim_sampling(args, model, conditioning, noise_shape, ddim_sampler, cfg
     conditional context, a tensor [1,L,D] replaces it from this iteration on (same L; on the graph path `FifoEngine.set_context`)."""
     context_at = kwargs.pop("context_at", None)
     kwargs.update({"clean_cond": True})
+    refuse_multistep(ddim_sampler)
     refuse_long_window(args)
     refuse_image_attention(model)
     refuse_concat(model, conditioning)
@@ -401,6 +450,7 @@ def fifo_ddim_sampling_multiprompts(args, model, conditioning, noise_shape, ddim
     for k in ("davis_data", "davis_masks"):
         if kwargs.pop(k, None) is not None:
             raise NotImplementedError(f"fifo_ddim_sampling_multiprompts has no DAVIS-video mode: {k} is not supported")
+    refuse_multistep(ddim_sampler)
     refuse_long_window(args)
     refuse_image_attention(model)
     refuse_concat(model, conditioning)

@@ -23,7 +23,8 @@ accessors) under all four engines; `FifoEngine`, the loop above; `_TrajectoryEng
 plan's input buffer by one schedule-table row per replay -- `BaseEngine` (DDIM sampling), `InvertEngine` (DDIM inversion), `DdpmEngine`
 (`p_sample_loop`) -- which owns the one- or two-branch plan, the reset core, the launches around the forward and the shared clauses
 of `supported()`.  Each of the three says beside `supported()` what a built engine is good for (`key`), which is what `EngineCache`
-compares."""
+compares.  `DpmEngine` is `BaseEngine` with the tables and the step of DPM-Solver++(2M) (`dpmpp_tables`): same launches around the
+forward, the multistep bit in the step's flag word, no draw."""
 from __future__ import annotations
 
 import contextlib
@@ -86,6 +87,60 @@ def invert_coef(sampler, i):
     else:
         s_cur = s_next = f32(1)
     return np.sqrt(a_cur), np.sqrt(a_next), f32(0), s1m_cur, np.sqrt(f32(1.) - a_next), s_cur, s_next
+
+
+def dpmpp_tables(sampler, n_rows, order=2, lower_order_final=True):
+    """The step tables of DPM-Solver++(2M) (Lu et al., 2022; data prediction, midpoint form) over the first `n_rows` rows of the
+    sampler's eta-0 schedule -> (coef [n_rows][8] fp32 = {sqrt(a_t), c_0, c_1, sqrt(1 - a_t), c_x, scale_t, 0, 0}, the int64 timesteps):
+    the second row layout of `moca_base_ddim_step_f32` (MOCA_BASE_MULTISTEP).  Row i takes the latents from level (a, s) =
+    (ddim_alphas[i], ddim_scale_arr[i]) to (ddim_alphas_prev[i], ddim_scale_arr_prev[i]), s = 1 without `use_scale`; with
+    alpha = sqrt(a) s, sigma = sqrt(1 - a), lam = log(alpha / sigma) and h = lam_prev - lam, in float64 rounded to fp32 once:
+
+        c_x = sigma_prev / sigma      c_0 = -alpha_prev expm1(-h)      c_1 = 0.5 c_0 h / h_prev      x' = c_x x + c_0 p0 + c_1 (p0 - p0_prev)
+
+    Columns 0, 3 and 5 are `ddim_coef`'s and `BaseEngine`'s, so pred_x0 has DDIM's bits.  A trajectory walks the rows from n_rows - 1
+    down.  A row with h == 0 is an identity row (c_x = 1, c_0 = c_1 = 0): every `uniform` schedule has one at i = 0, and the identity
+    rows at the clean end are not stepped at all (`dpm_stepped_rows`).  c_1 is 0 -- first order, the history is not read -- on the
+    first stepped row, on every row with `order` 1 and, with `lower_order_final`, on the last stepped row; h_prev is the h of the row
+    above.  An identity row ABOVE a stepped one (repeated timesteps, as 'quad' discretisation makes them) would put its own p0 into
+    the history at a distance h_prev = 0: refused."""
+    if order not in (1, 2):
+        raise ValueError(f"order = {order}: DPM-Solver++ multistep is built for orders 1 and 2")
+    n_rows = int(n_rows)
+    if not 1 <= n_rows <= len(sampler.ddim_timesteps):
+        raise ValueError(f"n_rows = {n_rows}: the schedule has {len(sampler.ddim_timesteps)} rows")
+    if np.any(np.asarray(sampler.ddim_sigmas, dtype=np.float64) != 0):
+        raise ValueError("dpmpp_tables: the solver is deterministic, its schedule is made with eta 0")
+    f64 = lambda v: np.asarray(v, dtype=np.float64)[:n_rows]
+    a, ap = f64(sampler.ddim_alphas), f64(sampler.ddim_alphas_prev)
+    use_scale = bool(sampler.use_scale)
+    sc, scp = (f64(sampler.ddim_scale_arr), f64(sampler.ddim_scale_arr_prev)) if use_scale else (np.ones(n_rows), np.ones(n_rows))
+    alpha_p, sigma, sigma_p = np.sqrt(ap) * scp, np.sqrt(1. - a), np.sqrt(1. - ap)
+    h = np.log(alpha_p / sigma_p) - np.log(np.sqrt(a) * sc / sigma)
+    stepped = np.flatnonzero(h != 0)
+    first = int(stepped[0]) if stepped.size else n_rows          # the identity rows at the clean end: 0 .. first - 1
+    if np.any(h[first:] == 0):
+        raise ValueError("dpmpp_tables: schedule rows with equal levels (repeated timesteps) above the clean end")
+    coef = np.zeros((n_rows, 8), np.float32)
+    for i in range(n_rows):
+        coef[i, 0], _, _, coef[i, 3], _ = ddim_coef(sampler, i)
+        coef[i, 5] = sampler.ddim_scale_arr[i] if use_scale else 1.0
+        coef[i, 4] = 1.0
+        if i < first:
+            continue
+        c_0 = -alpha_p[i] * np.expm1(-h[i])
+        coef[i, 1], coef[i, 4] = c_0, sigma_p[i] / sigma[i]
+        if order == 2 and i < n_rows - 1 and not (lower_order_final and i == first):
+            coef[i, 2] = 0.5 * c_0 * h[i] / h[i + 1]
+    t_table = np.ascontiguousarray(np.asarray(sampler.ddim_timesteps, dtype=np.int64)[:n_rows])
+    return torch.from_numpy(coef), torch.from_numpy(t_table)
+
+
+def dpm_stepped_rows(coef):
+    """how many rows of a `dpmpp_tables` table a trajectory steps: all but the identity rows at the clean end (one forward saved each)"""
+    c = np.asarray(coef)
+    identity = (c[:, 1] == 0) & (c[:, 2] == 0) & (c[:, 4] == 1)
+    return int(c.shape[0] - (np.argmin(identity) if not identity.all() else c.shape[0]))
 
 
 def n_ctx(cond):
@@ -734,6 +789,87 @@ class BaseEngine(_TrajectoryEngine):
         with self._step():
             if noise is not None:
                 self._fix_noise((self.noise, noise))
+
+
+class DpmEngine(BaseEngine):
+    """One step of DPM-Solver++(2M) sampling (`DPMSolverSampler`) as ONE hipGraph: `BaseEngine`'s two launches around the forward,
+    `moca_base_set_timestep` and `moca_base_ddim_step_f32`, the latter with MOCA_BASE_MULTISTEP in its flag word and on the tables of
+    `dpmpp_tables`.  `reset`, `encode`, `reinit`, `set_schedule`, `n_rows`, `c_concat` and `features_adapter` are `BaseEngine`'s.  What
+    differs:
+
+      * nothing is drawn in a step: no `moca_fifo_randn_f32` launch, `step()` takes no noise.  The step kernel's noise operand (not
+        read) is the buffer `encode` and `reinit` draw into;
+      * `pred_x0` is always allocated: it is the solver's history, read and rewritten by the step kernel.  Nothing resets it: the first
+        stepped row of every table has c_1 = 0 and does not read it, and every trajectory (after `reset`, `encode`, `reinit`,
+        `set_schedule`) starts on the first row of its table;
+      * the identity rows at the clean end of the table are not stepped (`n_stepped` replays make a trajectory; one more is refused);
+      * without guidance (`uc` None or scale 1) the plan holds the B latents and ONE context segment and the step kernel's eps_u is
+        NULL, as in `InvertEngine` ('crossattn' models only)."""
+
+    @staticmethod
+    def supported(model, x, cond, uc, scale, features_adapter=None):
+        """`BaseEngine.supported`, and the unguided call (`uc` None or scale 1.0) under `InvertEngine.supported`'s conditions"""
+        if uc is not None and scale != 1.0:
+            return BaseEngine.supported(model, x, cond, uc, scale, features_adapter=features_adapter)
+        return (_TrajectoryEngine._supports(model, x, [cond]) and "c_crossattn" in cond
+                and _TrajectoryEngine._supports_crossattn(model, [cond]))
+
+    @staticmethod
+    def key(sampler, x, cond, uc, cfg_scale, features_adapter=None, n_rows=None):
+        """what an engine built by `DpmEngine(model, sampler, x, cond, uc, cfg_scale, ...)` is good for: `BaseEngine.key`'s entries behind a
+        leading "dpmpp" (both share a cache), with the solver's order and `lower_order_final` and the scale bit of the flag word where
+        that key holds the sigmas, and no unconditional entries without guidance"""
+        guided = uc is not None and cfg_scale != 1.0
+        return ("dpmpp", tuple(x.shape), n_ctx(cond), n_ctx(uc) if guided else None, float(cfg_scale) if guided else 1.0,
+                sampler.ddim_timesteps.tobytes(), (int(sampler.order), bool(sampler.lower_order_final), bool(sampler.use_scale)),
+                str(x.device), tuple(int(c.shape[1]) for c in cond.get("c_concat") or ()),
+                None if features_adapter is None else tuple(tuple(f.shape) for f in features_adapter),
+                len(sampler.ddim_timesteps) if n_rows is None else int(n_rows))
+
+    def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, features_adapter=None, n_rows=None):
+        S = len(sampler.ddim_timesteps) if n_rows is None else int(n_rows)
+        if not 1 <= S <= len(sampler.ddim_timesteps):
+            raise ValueError(f"n_rows = {n_rows}: the schedule has {len(sampler.ddim_timesteps)} rows")
+        guided = uc is not None and cfg_scale != 1.0
+        self.order, self.lower_order_final = int(sampler.order), bool(sampler.lower_order_final)
+        self.hybrid = conditioning_key(model) != "crossattn"
+        concat = cond.get("c_concat") if self.hybrid else None
+        dev, n = self._open(model, x, [cond, uc] if guided else [cond], S, None if concat is None else tuple(int(c.shape[1]) for c in concat),
+                            features_adapter)
+        self._built = self._schedule_tables(sampler, S)
+        self.coef, self.t_table = (t.to(dev) for t in self._built)
+        self.it0, self._schedule_set = 0, False
+        self.end_iter = dpm_stepped_rows(self._built[0])     # the iteration counter after the last stepped row (`_write_schedule`)
+        self.enc_coef = self._built_enc = tuple(c.to(dev) for c in sampler.encode_tables())
+        self.enc_state = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.model = model
+        self._reinit_bufs = None
+        self._reinit_src = (None, None)
+        self.noise = torch.zeros(n, dtype=torch.float32, device=dev)           # the draws of `encode` / `reinit`; no step reads it
+        self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev)         # the history
+        self.reset(x, cond, uc if guided else None, seed, features_adapter=features_adapter)
+        plan = self.plan
+        flags = _l.MOCA_BASE_MULTISTEP | (_l.MOCA_BASE_SCALE if sampler.use_scale else 0)
+        self._wrap_step(None, lambda lib, st_, eps_c, eps_u, stream: _l.check(lib.moca_base_ddim_step_f32(
+            st_, _l.ptr(plan.x_in), eps_c, eps_u, _l.ptr(self.noise), _l.ptr(self.pred_x0), _l.ptr(self.coef), self.S, float(cfg_scale),
+            flags, n, stream), "moca_base_ddim_step_f32"))
+
+    def _schedule_tables(self, sampler, n_rows):
+        """`dpmpp_tables` with the order and `lower_order_final` the engine was built with (whatever `sampler` says: `set_schedule`)"""
+        return dpmpp_tables(sampler, n_rows, self.order, self.lower_order_final)
+
+    def _write_schedule(self, coef, t_table):
+        super()._write_schedule(coef, t_table)
+        self.end_iter = self.it0 + dpm_stepped_rows(coef)
+
+    n_stepped = property(lambda self: self.end_iter - self.it0, doc="the steps of a trajectory over the current schedule")
+
+    def step(self):
+        """one solver step (enqueued, not synchronised)"""
+        if self.n_iter >= self.end_iter:
+            raise ValueError(f"the schedule has {self.n_stepped} stepped rows: step {self.n_iter - self.it0} would run past the clean end")
+        with self._step():
+            pass
 
 class InvertEngine(_TrajectoryEngine):
     """One step of deterministic DDIM inversion (`DDIMSampler.encode`) as ONE hipGraph: [timestep rows of step i] + the UNet forward +

@@ -27,6 +27,7 @@ MOCA_TUNE_SLAB_F16 = 9
 MOCA_TUNE_GEMM_WS = 10
 MOCA_TUNE_CONV_HALO = 11
 MOCA_DDPM_X0, MOCA_DDPM_CLIP, MOCA_DDPM_SCALE, MOCA_DDPM_MASK_C0 = 1, 2, 4, 8
+MOCA_BASE_SCALE, MOCA_BASE_MULTISTEP = 1, 2              # the `use_scale` flag word of moca_base_ddim_step_f32
 (MOCA_ROUTE_SMALL64, MOCA_ROUTE_SMALL128, MOCA_ROUTE_GLDS128, MOCA_ROUTE_GLDS160, MOCA_ROUTE_G4, MOCA_ROUTE_W80, MOCA_ROUTE_W80W,
  MOCA_ROUTE_SQ256, MOCA_ROUTE_G4P, MOCA_ROUTE_SQP, MOCA_ROUTE_TATTN, MOCA_ROUTE_WS, MOCA_ROUTE_W80H) = range(1, 14)
 (MOCA_GN_ROUTE_STREAM, MOCA_GN_ROUTE_SLAB2, MOCA_GN_ROUTE_SLAB4, MOCA_GN_ROUTE_SLAB8, MOCA_GN_ROUTE_SLABREG1, MOCA_GN_ROUTE_SLABREG2,

@@ -25,7 +25,8 @@ import torch
 from . import lib as _l
 from . import ops
 from .conditioning import _f32c, check_schedule_index, cond_image_rows, guidance_eps
-from .fifo_graph import BaseEngine, EngineCache, InvertEngine, ddim_coef, invert_coef
+from .fifo_graph import (BaseEngine, DpmEngine, EngineCache, InvertEngine, ddim_coef, dpm_stepped_rows, dpmpp_tables, invert_coef,
+                         state_block)
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
@@ -622,3 +623,139 @@ class DDIMSampler(object):
             b, Cc, f, Fm, H * W, f32(self.beta), f32(1 - self.beta), f32(gamma), f32(1 - gamma), _st()),
             "moca_fifo_ddim_step_f32")
         return x_prev, pred_x0
+
+
+class DPMSolverSampler(DDIMSampler):
+    """DPM-Solver++(2M) (Lu et al., 2022: data prediction, multistep, midpoint form) on `DDIMSampler`'s integer timestep grid and its
+    one-graph step: `sample`, `decode` and `sample_freeinit` with the parent's signatures and return shapes, every step
+    `moca_base_ddim_step_f32` with MOCA_BASE_MULTISTEP over the tables of `fifo_graph.dpmpp_tables` -- replayed by `fifo_graph.DpmEngine`
+    where `DpmEngine.supported` allows it, else host-issued through the same entry point (`_steps_host`): one kernel serves both.
+    A trajectory over n schedule rows steps all but the identity rows at the clean end (`uniform` schedules have one, at timestep 0:
+    one forward fewer than DDIM), first order on its first step and -- `lower_order_final` -- on its last, second order between them
+    (`order` 1: first order throughout, which is DDIM at eta 0).  The solver is deterministic: `eta` other than 0, `noises=` and a
+    temperature other than 1 are refused, nothing is drawn.  `p_sample_ddim`, `ddim_step`, `fifo_onestep`, `encode`,
+    `stochastic_encode` are the parent's; FIFO / MoCA sampling refuses this sampler (`multistep`): diagonal denoising holds one frame
+    per schedule level and moves each by one level per iteration, which ties the queue length to first-order steps."""
+    multistep = True
+
+    def __init__(self, model, order=2, lower_order_final=True, **kw):
+        if isinstance(order, bool) or order not in (1, 2):
+            raise ValueError(f"order = {order!r}: DPM-Solver++ multistep is built for orders 1 and 2")
+        super().__init__(model, **kw)
+        self.order, self.lower_order_final = int(order), bool(lower_order_final)
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=True):
+        if ddim_eta != 0.:
+            raise ValueError(f"eta = {ddim_eta}: DPM-Solver++ is a deterministic solver, its schedule has eta 0")
+        super().make_schedule(ddim_num_steps, ddim_discretize=ddim_discretize, ddim_eta=0., verbose=verbose)
+
+    @staticmethod
+    def _refuse_draws(noises, temperature=1.):
+        if noises is not None:
+            raise ValueError("noises=: DPM-Solver++ draws nothing, there is no step noise to fix")
+        if temperature != 1.:
+            raise ValueError(f"temperature = {temperature}: DPM-Solver++ draws nothing, there is no step noise to scale")
+
+    def _dpm_engine_for(self, img, cond, uc, scale, seed, n_rows, features_adapter=None):
+        """the cached step graph (fifo_graph.DpmEngine) for this call, reset to a new trajectory; built when `DpmEngine.key` changes.  It
+        shares the one-entry cache of the parent's engines."""
+        return self._engines.get(DpmEngine.key(self, img, cond, uc, scale, features_adapter, n_rows),
+                                 lambda: DpmEngine(self.model, self, img, cond, uc, scale, seed=seed, features_adapter=features_adapter,
+                                                   n_rows=n_rows),
+                                 lambda eng: eng.reset(img, cond, uc, seed, features_adapter=features_adapter))
+
+    def _on_graph(self, x, cond, uc, scale, use_graph, features_adapter):
+        """-> (whether the call runs on `DpmEngine`, its unconditional branch: None without guidance)"""
+        guided = uc is not None and scale != 1.0
+        uc = uc if guided else None
+        return bool(use_graph and (self.share_prefix or not guided)
+                    and DpmEngine.supported(self.model, x, cond, uc, scale, features_adapter=features_adapter)), uc
+
+    def _steps_host(self, x, cond, uc, scale, n_rows, features_adapter=None):
+        """the host-issued trajectory over the first `n_rows` schedule rows: per stepped row `guidance_eps` + `cfg_combine`, then the
+        engine's step launch on a private 32-byte state block, the device table and a history buffer (eps_u NULL: eps is combined)"""
+        coef, t_table = dpmpp_tables(self, n_rows, self.order, self.lower_order_final)
+        x = _f32c(x).clone()                                  # (the step kernel updates in place: the caller keeps x_T)
+        dev = x.device
+        state, coef_d, hist = state_block(0).to(dev), coef.to(dev), torch.empty_like(x)
+        flags = _l.MOCA_BASE_MULTISTEP | (_l.MOCA_BASE_SCALE if self.use_scale else 0)
+        unet_kwargs = {} if features_adapter is None else {"features_adapter": list(features_adapter)}
+        for k in range(dpm_stepped_rows(coef)):
+            ts = torch.full((x.shape[0],), int(t_table[n_rows - 1 - k]), device=dev, dtype=torch.long)
+            e_t = _f32c(self._cfg_eps(x, ts, cond, uc, scale, **unet_kwargs))
+            # (noise: required, not read)
+            _l.check(_l.load().moca_base_ddim_step_f32(_l.ptr(state), _l.ptr(x), _l.ptr(e_t), None, _l.ptr(x), _l.ptr(hist), _l.ptr(coef_d),
+                                                       n_rows, 1.0, flags, x.numel(), _st()), "moca_base_ddim_step_f32")
+        return x
+
+    def _run_steps(self, x, cond, uc, scale, n_steps, noises, use_graph, features_adapter=None):
+        """the loop of `sample` and `decode`: the stepped rows among `ddim_timesteps[:n_steps]`, flipped, on `DpmEngine` where `use_graph`
+        and `DpmEngine.supported` allow it, else host-issued"""
+        self._refuse_draws(noises)
+        if n_steps <= 0:
+            return x
+        graph, uc_g = self._on_graph(x, cond, uc, scale, use_graph, features_adapter)
+        if graph:
+            eng = self._dpm_engine_for(x, cond, uc_g, scale, 0, n_steps, features_adapter=features_adapter)
+            for _ in range(eng.n_stepped):
+                eng.step()
+            return eng.latents().to(x.dtype)
+        return self._steps_host(x, cond, uc, scale, n_steps, features_adapter=features_adapter).to(x.dtype)
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, eta=0., x_T=None, verbose=False,
+               unconditional_guidance_scale=1., unconditional_conditioning=None, latents_dir=None, noises=None,
+               features_adapter=None, **kwargs):
+        """`DDIMSampler.sample` with the solver's steps: S schedule rows, S - 1 forwards on a `uniform` schedule"""
+        self._refuse_draws(noises, kwargs.get("temperature", 1.))
+        return super().sample(S, batch_size, shape, conditioning=conditioning, eta=eta, x_T=x_T, verbose=verbose,
+                              unconditional_guidance_scale=unconditional_guidance_scale,
+                              unconditional_conditioning=unconditional_conditioning, latents_dir=latents_dir, noises=None,
+                              features_adapter=features_adapter, **kwargs)
+
+    @torch.no_grad()
+    def sample_freeinit(self, steps, batch_size, shape, LPF, conditioning=None, eta=0., x_T=None, z_rands=None, noises=None,
+                        unconditional_guidance_scale=1., unconditional_conditioning=None, features_adapter=None, return_all=False,
+                        verbose=False):
+        """`DDIMSampler.sample_freeinit` with the solver's trajectories: on the step graph the whole run stays on ONE cached `DpmEngine`
+        captured for steps[-1] rows (`set_schedule` where the step count changes, `reinit` between trajectories -- each starts on the
+        first row of its table, so first order, whatever the history holds); elsewhere composed on the host from `freeinit_reinit`
+        and `_steps_host`.  Only the fresh noise of a re-initialisation is drawn (`z_rands[k-1]` fixes it)."""
+        from .freeinit import freeinit_reinit
+        self._refuse_draws(noises)
+        steps = [int(s) for s in steps]
+        if not steps or max(steps) != steps[-1] or min(steps) < 1:
+            raise ValueError(f"steps = {steps}: at least one trajectory, every one of 1 .. steps[-1] steps")
+        if z_rands is not None and len(z_rands) != len(steps) - 1:
+            raise ValueError(f"z_rands holds {len(z_rands)} tensors for {len(steps) - 1} re-initialisations")
+        cond, uc, scale = conditioning, unconditional_conditioning, unconditional_guidance_scale
+        self.make_schedule(ddim_num_steps=steps[-1], ddim_eta=eta, verbose=verbose)
+        device = self.model.betas.device
+        initial_noise = torch.randn((batch_size,) + tuple(shape), device=device) if x_T is None else x_T
+        z_rand = lambda k: None if z_rands is None else z_rands[k - 1]
+        every = []
+        graph, uc_g = self._on_graph(initial_noise, cond, uc, scale, self.use_graph, features_adapter)
+        if graph:
+            eng = self._dpm_engine_for(initial_noise, cond, uc_g, scale, 0, steps[-1], features_adapter=features_adapter)
+            for k, S in enumerate(steps):
+                if S != eng.S - eng.it0:
+                    self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+                    eng.set_schedule(self)
+                if k > 0:
+                    seed = 0 if z_rand(k) is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+                    eng.reinit(initial_noise, LPF, z_rand=z_rand(k), seed=seed)
+                for _ in range(eng.n_stepped):
+                    eng.step()
+                if return_all:
+                    every.append(eng.latents().to(initial_noise.dtype))
+            x = every[-1] if return_all else eng.latents().to(initial_noise.dtype)
+            return x, (every if return_all else None)
+        x = initial_noise
+        for k, S in enumerate(steps):
+            if k > 0:
+                zr = z_rand(k)
+                x = freeinit_reinit(self.model, x, initial_noise, torch.randn_like(initial_noise, dtype=torch.float32) if zr is None else zr, LPF)
+            self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+            x = self._run_steps(x, cond, uc, scale, S, None, False, features_adapter=features_adapter)
+            every.append(x)
+        return x, (every if return_all else None)
