@@ -23,6 +23,12 @@
 // moca_temporal_attention_long_f16: the same over 17 <= T <= 32 frames: one wavefront per
 //   problem, the 32 x 32 score tile of v_mfma_f32_32x32x16_f16 whose accumulator registers
 //   are the B operand of P.V (tattn_long_kernel).
+//
+// Layout of this file: the LDS images and MFMA fragment maps that attention_kernel, attention_short_kernel, attention_v4_kernel and
+// tattn_long_kernel share are written ONCE, in the first section below (k_img / v_img, score_key, load_q_frags, put_kv, pv_step,
+// store_o_frags / put_o_tile, the temporal problem decode); the kernels only call them.  A change of an image or a map is a change there.
+// temporal_attention_kernel (16 x 16 MFMAs, padded V rows) shares the problem decode only.  The entry points at the end share one
+// argument check (attn_args_ok) and one launch list (launch_qkvo).
 #include "common.h"
 #include <stdlib.h>
 
@@ -34,15 +40,112 @@ constexpr int QB = 128;      // queries per block
 constexpr int ROWB = 128;    // bytes per LDS row (64 halves)
 
 template <int V> struct int_c { static constexpr int value = V; };
-typedef short short4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) char* lds_c_ptr;
-typedef __attribute__((address_space(3))) short4v* lds_s4_ptr;
 
-// ds_read_b64_tr_b16: a 16-lane group reads a 4-row x 16-column block of 16-bit elements and receives it
-// column-major (lane i gets column i of the 4 rows).  Lane i = 4q+p supplies the address of row q, columns 4p..4p+3.
-__device__ __forceinline__ half4v tr_read(const char* addr) {
-    const short4v v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)addr);
-    return __builtin_bit_cast(half4v, v);
+// ---- LDS images and fragment maps of the 32 x 32 kernels -----------------------------------------------------------------
+// A lane is (fr = lane & 31, fh = lane >> 5).  In S^T = K.Q^T (v_mfma_f32_32x32x16_f16, A = K, B = Q) it supplies K[key fr][16 ks +
+// 8 fh + j] and Q[query fr][16 ks + 8 fh + j] and receives S^T[key = score_key(r, fh)][query fr] in accumulator register r.
+
+// Byte offset of 16-byte chunk `ch` of row `row` in an image of 128-byte rows: the K image (and the per-wave Q / O tile) is swizzled
+// for ds_read_b128 fragment reads down a column of chunks, the V image for the transposed reads (rows r and r + 8 keep their chunk).
+__device__ __forceinline__ int k_chunk(int row, int ch) { return ch ^ ((row >> 1) & 7); }
+__device__ __forceinline__ int v_chunk(int row, int ch) { return ch ^ (((row >> 1) & 1) << 2); }
+__device__ __forceinline__ int k_img(int row, int ch) { return row * ROWB + (k_chunk(row, ch) << 4); }
+__device__ __forceinline__ int v_img(int row, int ch) { return row * ROWB + (v_chunk(row, ch) << 4); }
+
+// key, inside its 32-key sub-tile, of score register r of lane half fh
+__device__ __forceinline__ int score_key(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }
+
+// Q fragments (B operand of S^T = K.Q^T) of query row `qrow` from global memory: zero when the row does not exist
+__device__ __forceinline__ void load_q_frags(half8v (&qf)[4], const half_t* qb, int qrow, int ldq, int fh, bool q_ok) {
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        half8v t = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (q_ok) t = *reinterpret_cast<const half8v*>(qb + (int64_t)qrow * ldq + ks * 16 + fh * 8);
+        qf[ks] = t;
+    }
+}
+
+// staging store of chunk `ch` of key row `row` into both images
+__device__ __forceinline__ void put_kv(char* sK, char* sV, int row, int ch, half8v a, half8v b) {
+    *reinterpret_cast<half8v*>(sK + k_img(row, ch)) = a;
+    *reinterpret_cast<half8v*>(sV + v_img(row, ch)) = b;
+}
+
+// O^T += V^T . P^T over the 16 keys [key0, key0 + 16) of a V image (key0 a multiple of 16); pf = the 8 score registers of those keys,
+// rounded to fp16.  The transposed read of a 16-lane group (lane i = 4 tq + tp) delivers to lane i the column d = 32 dt + 16 tcol16 + i
+// of the 4 keys key0 + 4 fh + (0 .. 3); the second read is 8 keys further: together the key order of the accumulator-as-operand trick.
+// pv_lane_offsets: the lane's two read addresses inside the first 16-key group, per-lane constants; a group further on, and the second
+// read, only add whole rows (16 and 8 of them: v_chunk does not change), so the kernels' unrolled steps add immediates.
+__device__ __forceinline__ void pv_lane_offsets(int (&v_off)[2], int lane) {
+    const int fh = lane >> 5, tq = (lane & 15) >> 2, tp = lane & 3, tcol16 = (lane >> 4) & 1;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+        const int dcol = dt * 32 + tcol16 * 16 + 4 * tp;     // first of this lane's 4 address columns
+        v_off[dt] = v_img(4 * fh + tq, dcol >> 3) + (dcol & 7) * 2;
+    }
+}
+__device__ __forceinline__ void pv_step(f32x16 (&o)[2], const char* vbuf, const int (&v_off)[2], int key0, half8v pf) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt) {
+        const char* a0 = vbuf + v_off[dt] + key0 * ROWB;
+        const half4v lo = lds_tr_read_b64(a0);
+        const half4v hi = lds_tr_read_b64(a0 + 8 * ROWB);
+        const half8v vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o[dt], 0, 0, 0);
+    }
+}
+
+// The lane holds O^T[d = 32 dt + 8 g + 4 fh + j][query fr] in o[dt][4 g + j]; o_frag: those four d, normalised and rounded.
+__device__ __forceinline__ half4v o_frag(const f32x16 (&o)[2], float inv, int dt, int g) {
+    half4v h4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h4[j] = (half_t)(o[dt][g * 4 + j] * inv);
+    return h4;
+}
+// 8-byte stores straight to the lane's output row (`orow` = its first element of this head)
+__device__ __forceinline__ void store_o_frags(half_t* orow, const f32x16 (&o)[2], float inv, int fh) {
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *reinterpret_cast<half4v*>(orow + dt * 32 + 8 * g + 4 * fh) = o_frag(o, inv, dt, g);
+}
+// Into the wave's own 32-row LDS tile `wq` (K image), from which whole 128-byte rows leave (8 lanes x 16 B) instead of one 8-byte piece
+// of 32 different rows per instruction.  Each wave touches only its own tile: no block barrier.  (The copy-out loop stays in the two
+// kernels: as a function it moves attention_short_kernel from 154 to 127 VGPRs with 16 instructions more per query group.)
+__device__ __forceinline__ void put_o_tile(char* wq, const f32x16 (&o)[2], float inv, int lane) {
+    const int fr = lane & 31, fh = lane >> 5;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int d0 = dt * 32 + 8 * g + 4 * fh;
+            *reinterpret_cast<half4v*>(wq + k_img(fr, d0 >> 3) + (d0 & 7) * 2) = o_frag(o, inv, dt, g);
+        }
+}
+
+// The problem of a wave of the temporal kernels: (video, pixel, head) = blockIdx.x * 4 + wave.  Token row of frame t:
+// (b T + t) HW + pix = row0 + t HW.  The waves past the last problem redo it and store nothing (`active`).
+struct TemporalProblem {
+    int head;
+    int64_t row0;        // token row of frame 0
+    int64_t rstride;     // elements between the q / k / v rows of consecutive frames
+    int64_t base;        // element offset of frame 0's q / k / v row of this head
+    bool active;
+};
+__device__ __forceinline__ TemporalProblem temporal_problem(int B, int T, int HW, int heads, int ld, int wave) {
+    TemporalProblem p;
+    const int64_t total = (int64_t)B * HW * heads;
+    int64_t prob = (int64_t)blockIdx.x * 4 + wave;
+    p.active = prob < total;
+    if (!p.active) prob = total - 1;
+    p.head = (int)(prob % heads);
+    const int64_t bp = prob / heads;
+    const int pix = (int)(bp % HW), b = (int)(bp / HW);
+    p.row0 = (int64_t)b * T * HW + pix;
+    p.rstride = (int64_t)HW * ld;
+    p.base = p.row0 * ld + p.head * D;
+    return p;
 }
 
 // XCD-aware block order: the hardware deals consecutive workgroup ids round-robin to the 8 XCDs (each with its own L2).  With
@@ -65,8 +168,7 @@ template <bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void attention_kernel(
     const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v, half_t* __restrict__ out,
     int heads, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, int kv_div, float scale_log2e) {
-    // double-buffered K / V tiles: K row-major [key][d] swizzled for ds_read_b128 (chunk ^ ((row>>1)&7)),
-    // V row-major [key][d] swizzled for the transposed reads (chunk ^ (((row>>1)&1)<<2))
+    // double-buffered K / V tiles, row-major [key][d]: the K image and the V image
     __shared__ __attribute__((aligned(16))) char sK[2][KT * ROWB];
     __shared__ __attribute__((aligned(16))) char sV[2][KT * ROWB];
 
@@ -82,16 +184,10 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
     const half_t* kb = k + (int64_t)bkv * Nk * ldk + head * D;
     const half_t* vb = v + (int64_t)bkv * Nk * ldv + head * D;
 
-    // Q fragments (B operand of S^T = K.Q^T): lane (q=fr, h=fh) holds Q[q][16ks + 8h + j]
     half8v qf[4];
     const int qrow = q0 + fr;
     const bool q_ok = qrow < Nq;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        half8v t = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (q_ok) t = *reinterpret_cast<const half8v*>(qb + (int64_t)qrow * ldq + ks * 16 + fh * 8);
-        qf[ks] = t;
-    }
+    load_q_frags(qf, qb, qrow, ldq, fh, q_ok);
 
     f32x16 o[2];
 #pragma unroll
@@ -117,16 +213,11 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
     };
     auto store_kv = [&](int buf) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = r0 + 32 * i;
-            *reinterpret_cast<half8v*>(sK[buf] + row * ROWB + ((cc ^ ((row >> 1) & 7)) << 4)) = rk[i];
-            *reinterpret_cast<half8v*>(sV[buf] + row * ROWB + ((cc ^ (((row >> 1) & 1) << 2)) << 4)) = rv[i];
-        }
+        for (int i = 0; i < 2; ++i) put_kv(sK[buf], sV[buf], r0 + 32 * i, cc, rk[i], rv[i]);
     };
-    // per-lane constants of the transposed V reads: lane i = lane&15 = 4q+p of its 16-lane group
-    const int tq = (lane & 15) >> 2, tp = lane & 3;
-    const int tcol16 = (lane >> 4) & 1;          // which 16-column half of the 32-wide d tile
-    const int tkey4 = 4 * fh;                     // lane half h selects keys +4
+
+    int v_off[2];
+    pv_lane_offsets(v_off, lane);
 
     const int nkt = (Nk + KT - 1) / KT;
     load_kv(0);
@@ -150,11 +241,9 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
         for (int sub = 0; sub < 2; ++sub) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[sub][r] = 0.f;
-            const int row = sub * 32 + fr;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                const int ch = ks * 2 + fh;
-                const half8v kf = *reinterpret_cast<const half8v*>(kbuf + row * ROWB + ((ch ^ ((row >> 1) & 7)) << 4));
+                const half8v kf = *reinterpret_cast<const half8v*>(kbuf + k_img(sub * 32 + fr, ks * 2 + fh));
                 s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[sub], 0, 0, 0);
             }
         }
@@ -164,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
             for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = kt * KT + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    const int key = kt * KT + sub * 32 + score_key(r, fh);
                     if (key >= Nk || (CAUSAL && key > qrow)) s[sub][r] = -INFINITY;
                 }
         }
@@ -202,53 +291,27 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
-            for (int ss = 0; ss < 2; ++ss) {
-                const int krow0 = sub * 32 + ss * 16 + tkey4 + tq;     // row of the first 4-key block; second is +8
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const int dcol = dt * 32 + tcol16 * 16 + 4 * tp;     // first of this lane's 4 address columns
-                    const int ch = dcol >> 3, within = (dcol & 7) * 2;
-                    const int ra = krow0, rb = krow0 + 8;
-                    const half4v lo = tr_read(vbuf + ra * ROWB + ((ch ^ (((ra >> 1) & 1) << 2)) << 4) + within);
-                    const half4v hi = tr_read(vbuf + rb * ROWB + ((ch ^ (((rb >> 1) & 1) << 2)) << 4) + within);
-                    half8v vf;
-                    vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3];
-                    vf[4] = hi[0]; vf[5] = hi[1]; vf[6] = hi[2]; vf[7] = hi[3];
-                    o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[sub][ss], o[dt], 0, 0, 0);
-                }
-            }
+            for (int ss = 0; ss < 2; ++ss) pv_step(o, vbuf, v_off, sub * 32 + ss * 16, pf[sub][ss]);
         __syncthreads();   // everyone is done with buffers [cur]; the other buffers' stores are visible
     }
 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
-    if (q_ok) {
-        half_t* ob = out + ((int64_t)bq * Nq + qrow) * ldo + head * D;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                half4v h4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h4[j] = (half_t)(o[dt][g * 4 + j] * inv);
-                *reinterpret_cast<half4v*>(ob + dt * 32 + 8 * g + 4 * fh) = h4;
-            }
-    }
+    if (q_ok) store_o_frags(out + ((int64_t)bq * Nq + qrow) * ldo + head * D, o, inv, fh);
 }
 
 // ---- cross-attention against a SHORT context (N_k <= 96: the 77 CLIP tokens): ONE key tile of 96 (three 32-key sub-tiles; the
 // general kernel runs two 64-key tiles of which the second is 80 % padding, with an online-softmax step and a barrier in
 // between), plain softmax (no running maximum), and K / V staged ONCE per block for `q_iters` consecutive 128-query groups
-// (the general kernel re-stages them per 128 queries: 20 times per (frame, head) at 2560 tokens).  Fragment maps and LDS images
-// are those of attention_kernel.
+// (the general kernel re-stages them per 128 queries: 20 times per (frame, head) at 2560 tokens).
 //
 // IP (moca_attention_ip_f16, the img_cross_attention of attention.py:82-87,117-124): the tile holds TWO contexts, text keys from k / v
 // in rows [0, Nt) and image keys from k_ip / v_ip in rows [IP_ROW0, IP_ROW0 + Ni) = [80, 96), and the block computes
 //   softmax(q k^T s) v + ip_scale * softmax(q k_ip^T s) v_ip
 // with two separate softmaxes: row maximum and row sum are taken per segment, and the image segment's P is multiplied by
 // ip_scale * l_text / l_img before its fp16 conversion, so that the one P.V MFMA chain and the 1 / l_text epilogue finish both.
-// The image rows start at a fixed multiple of 8: a lane's score register r of sub-tile `sub` holds key 32 sub + 8 (r >> 2) + 4 fh +
-// (r & 3), so with the segment boundary on an 8-key group every register belongs to one segment at COMPILE time, the same for all
+// The image rows start at a fixed multiple of 8: a lane's score register r of sub-tile `sub` holds key 32 sub + score_key(r, fh),
+// so with the segment boundary on an 8-key group every register belongs to one segment at COMPILE time, the same for all
 // lanes (a boundary at a runtime Nt costs a lane mask per register, 48 of them live across the softmax: SGPR spills).  Hence
 // Nt <= 80 and Ni <= 16, which covers the reference's 77 text tokens + 16 (Resampler) or 4 (ImageProjModel) image tokens.
 // (The IP = false instance ignores k_ip, v_ip, ldk_ip, ldv_ip, Nt and ip_scale; for IP = true, Nk = IP_ROW0 + Ni.)
@@ -261,9 +324,9 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
     const half_t* __restrict__ k_ip, const half_t* __restrict__ v_ip, int ldk_ip, int ldv_ip, int Nt, float ip_scale) {
     __shared__ __attribute__((aligned(16))) char sK[KS96 * ROWB];
     __shared__ __attribute__((aligned(16))) char sV[KS96 * ROWB];
-    // Q rows in / O rows out pass through a per-wave LDS tile (32 rows x 128 B, chunk ^ ((row >> 1) & 7)): the global accesses are
-    // whole 128-byte rows (8 lanes x 16 B) instead of one 16-byte / 8-byte piece of 32 different rows per instruction.  Each wave
-    // touches only its own 32 rows, so no block barrier is needed inside the query loop.
+    // Q rows in / O rows out pass through a per-wave LDS tile (32 rows x 128 B, the K image): the global accesses are whole 128-byte
+    // rows (8 lanes x 16 B) instead of one 16-byte / 8-byte piece of 32 different rows per instruction.  Each wave touches only its
+    // own 32 rows, so no block barrier is needed inside the query loop.
     __shared__ __attribute__((aligned(16))) char sQ[QB * ROWB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int bx, by;
@@ -289,14 +352,12 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
                 a = *reinterpret_cast<const half8v*>(k_ip + ((int64_t)bkv * Ni + ri) * ldk_ip + head * D + cc * 8);
                 b = *reinterpret_cast<const half8v*>(v_ip + ((int64_t)bkv * Ni + ri) * ldv_ip + head * D + cc * 8);
             }
-            *reinterpret_cast<half8v*>(sK + row * ROWB + ((cc ^ ((row >> 1) & 7)) << 4)) = a;
-            *reinterpret_cast<half8v*>(sV + row * ROWB + ((cc ^ (((row >> 1) & 1) << 2)) << 4)) = b;
+            put_kv(sK, sV, row, cc, a, b);
         }
     }
     __syncthreads();
-    const int tq = (lane & 15) >> 2, tp = lane & 3;
-    const int tcol16 = (lane >> 4) & 1;
-    const int tkey4 = 4 * fh;
+    int v_off[2];
+    pv_lane_offsets(v_off, lane);
     char* wq = sQ + wave * 32 * ROWB;
     half8v nq[4];                                          // the NEXT query group's rows travel while the current one is computed
     auto load_q = [&](int q0n) {
@@ -315,23 +376,20 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = lane + 64 * i, row = c >> 3, ch = c & 7;
-            *reinterpret_cast<half8v*>(wq + row * ROWB + ((ch ^ ((row >> 1) & 7)) << 4)) = nq[i];
+            *reinterpret_cast<half8v*>(wq + k_img(row, ch)) = nq[i];
         }
         if (it + 1 < q_iters) load_q(q0 + QB);
         half8v qf[4];
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            qf[ks] = *reinterpret_cast<const half8v*>(wq + fr * ROWB + (((ks * 2 + fh) ^ ((fr >> 1) & 7)) << 4));
+        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const half8v*>(wq + k_img(fr, ks * 2 + fh));
         f32x16 s[3];
 #pragma unroll
         for (int sub = 0; sub < 3; ++sub) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[sub][r] = 0.f;
-            const int row = sub * 32 + fr;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                const int ch = ks * 2 + fh;
-                const half8v kf = *reinterpret_cast<const half8v*>(sK + row * ROWB + ((ch ^ ((row >> 1) & 7)) << 4));
+                const half8v kf = *reinterpret_cast<const half8v*>(sK + k_img(sub * 32 + fr, ks * 2 + fh));
                 s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[sub], 0, 0, 0);
             }
         }
@@ -343,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
             for (int sub = 0; sub < 3; ++sub)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    const int key = sub * 32 + score_key(r, fh);
                     if (key >= Nk) s[sub][r] = -INFINITY;
                     tmax = fmaxf(tmax, s[sub][r]);
                 }
@@ -366,7 +424,7 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
             for (int sub = 0; sub < 3; ++sub)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    const int key = sub * 32 + score_key(r, fh);
                     const bool txt = sub < 2 || r < 8;                       // compile time
                     if (txt ? key >= Nt : key >= Nk) s[sub][r] = -INFINITY;
                     if (txt) tmax = fmaxf(tmax, s[sub][r]);
@@ -405,36 +463,15 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
 #pragma unroll
         for (int sub = 0; sub < 3; ++sub)
 #pragma unroll
-            for (int ss = 0; ss < 2; ++ss) {
-                const int krow0 = sub * 32 + ss * 16 + tkey4 + tq;
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const int dcol = dt * 32 + tcol16 * 16 + 4 * tp;
-                    const int ch = dcol >> 3, within = (dcol & 7) * 2;
-                    const int ra = krow0, rb = krow0 + 8;
-                    const half4v lo = tr_read(sV + ra * ROWB + ((ch ^ (((ra >> 1) & 1) << 2)) << 4) + within);
-                    const half4v hi = tr_read(sV + rb * ROWB + ((ch ^ (((rb >> 1) & 1) << 2)) << 4) + within);
-                    const half8v vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                    o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[sub][ss], o[dt], 0, 0, 0);
-                }
-            }
-        // O^T[d = 32 dt + 8 g + 4 fh + j][query fr] -> row fr of the wave's LDS tile (the Q fragments are in registers), then whole rows out
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                half4v h4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h4[j] = (half_t)(o[dt][g * 4 + j] * inv);
-                const int d0 = dt * 32 + 8 * g + 4 * fh;
-                *reinterpret_cast<half4v*>(wq + fr * ROWB + (((d0 >> 3) ^ ((fr >> 1) & 7)) << 4) + (d0 & 7) * 2) = h4;
-            }
+            for (int ss = 0; ss < 2; ++ss) pv_step(o, sV, v_off, sub * 32 + ss * 16, pf[sub][ss]);
+        // O rows leave through the wave's Q tile (the Q fragments are in registers), whole rows as they came in
+        put_o_tile(wq, o, inv, lane);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = lane + 64 * i, row = c >> 3, ch = c & 7;
             if (q0 + row < Nq)
                 *reinterpret_cast<half8v*>(out + ((int64_t)bq * Nq + q0 + row) * ldo + head * D + ch * 8) =
-                    *reinterpret_cast<const half8v*>(wq + row * ROWB + ((ch ^ ((row >> 1) & 7)) << 4));
+                    *reinterpret_cast<const half8v*>(wq + k_img(row, ch));
         }
     }
 }
@@ -451,12 +488,16 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(
 //   * the reference maximum is lazy (cdna_hip_programming.md T13): it is moved (O, l rescaled) only when a tile maximum
 //     exceeds it by more than THR = 8, i.e. P <= 2^8 in fp16, whose relative precision does not depend on magnitude; the
 //     first tile always sets it;
-//   * the row sums are v_dot2_f32_f16 of the PACKED P against (1, 1): 16 instructions per tile instead of 32 adds (a variant
-//     that takes them from the matrix pipe -- l^T += 1^T.P^T, one more MFMA per 16 keys -- is 5 % slower: the matrix pipe is
-//     the longer pole once the VALU work is cut; -DMOCA_ATTN_SUM_MFMA);
+//   * the row sums are v_dot2_f32_f16 of the PACKED P against (1, 1): 16 instructions per tile instead of 32 adds;
 //   * P is packed with v_cvt_pk_f16_f32 only; LDS fragment addresses are per-lane constants + immediates (key loop
 //     unrolled over the two buffers); the staging pointers advance by one 64-bit add per tile.
-// What is left per element: 0.5 max3 + exp + 0.5 cvt_pk + 0.5 dot2.  121 VGPRs: four waves per SIMD.  Tiles, LDS images and fragment maps are those of attention_kernel.
+// What is left per element: 0.5 max3 + exp + 0.5 cvt_pk + 0.5 dot2.  121 VGPRs: four waves per SIMD.  Tiles, LDS images and fragment
+// maps are those of attention_kernel (k_img / v_img, hoisted into per-lane constants here).
+// Measured and not kept (the variants are no longer in the source):
+//   * row sums from the matrix pipe (l^T += 1^T.P^T, one more MFMA per 16 keys): 5 % slower, the matrix pipe is the longer pole once the VALU work is cut;
+//   * -m_ref living across the tile instead of 16 v_mov per tile: 141 instead of 121 VGPRs (three waves per SIMD), 3.5 % slower;
+//   * without the zero-reference inline constant below: the 16 v_mov cost 64 of the tile's 960 issue-port cycles;
+//   * 8 wavefronts (256 queries) per block: -2.8 % at 2560 tokens in isolation, -0.1 % on the whole step.
 [[maybe_unused]] constexpr float LAZY_THR = 8.0f;
 [[maybe_unused]] constexpr float REF0_BAND = 6.0f;     // first-tile maxima inside [-6, 6] (in log2 units) leave the reference at 0
 __device__ __forceinline__ float vmax3(float a, float b, float c) {
@@ -465,12 +506,12 @@ __device__ __forceinline__ float vmax3(float a, float b, float c) {
     return r;
 }
 
-// NW wavefronts (32 queries each) share every K/V tile: 4 (128 queries per block), or 8 (256 queries: half the LDS-DMA and L2 -> LDS
-// traffic per query, one piece of K and one of V per wave and tile; the barrier spans 8 waves)
+// NW = 4 wavefronts (32 queries each) share every K/V tile (the template parameter is part of the kernel's name in profiles and tools)
 template <int NW>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 2) void attention_v4_kernel(
+__global__ __launch_bounds__(64 * NW, 2) void attention_v4_kernel(
     const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v, half_t* __restrict__ out,
     int heads, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, int kv_div, float scale_log2e) {
+    static_assert(NW == 4 && 32 * NW == QB, "the DMA pieces and the per-wave output tiles below are laid out for four waves");
 #if defined(__HIP_DEVICE_COMPILE__)   // (__amdgpu_buffer_rsrc_t is a device-only type; the host pass only needs the launch stub)
     __shared__ __attribute__((aligned(16))) char smem[4 * KT * ROWB];      // sK[0], sK[1], sV[0], sV[1]
     constexpr int TILE = KT * ROWB;                                       // 8 KiB
@@ -482,32 +523,24 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 2) void attention_v4_kernel(
     attn_block_coords(bx, by);
     const int bq = by / heads, head = by % heads;
     const int bkv = bq / kv_div;
-    const int q0 = bx * (32 * NW) + wave * 32;
+    const int q0 = bx * QB + wave * 32;
     const int fr = lane & 31, fh = lane >> 5;
 
     const half_t* qb = q + (int64_t)bq * Nq * ldq + head * D;
-    // Q' = Q * scale * log2(e), B operand of S^T = K.Q'^T: lane (q = fr, h = fh) holds Q'[q][16 ks + 8 h + j]
+    // Q' = Q * scale * log2(e)
     half8v qf[4];
-    const int qrow = q0 + fr;
-    const bool q_ok = qrow < Nq;
+    load_q_frags(qf, qb, q0 + fr, ldq, fh, q0 + fr < Nq);
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        half8v t = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (q_ok) t = *reinterpret_cast<const half8v*>(qb + (int64_t)qrow * ldq + ks * 16 + fh * 8);
+    for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = (half_t)((float)t[j] * scale_log2e);
-        qf[ks] = t;
-    }
+        for (int j = 0; j < 8; ++j) qf[ks][j] = (half_t)((float)qf[ks][j] * scale_log2e);
 
-    f32x16 o[2], osum, negm;          // O^T accumulators, row-sum accumulator (all rows equal), -m_ref replicated
+    f32x16 o[2];               // O^T accumulators
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; osum[r] = 0.f; negm[r] = 0.f; }
+    for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
     float m_ref = 0.f;
     bool ref_zero = true;      // (wave-uniform) no query of this wave has moved its reference off 0
     float lsum = 0.f;          // this lane's share of the row sum (its 32 of the 64 keys of every tile)
-    half8v ones;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = (half_t)1.0f;
 
     // staging by LDS-DMA (buffer_load_dwordx4 ... lds: no staging registers, no ds_write): a 1 KiB piece = 8 key rows x 128 B,
     // lane -> row (lane >> 3), PHYSICAL chunk lane & 7; the swizzles of the two LDS images go on the per-lane SOURCE address
@@ -516,8 +549,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 2) void attention_v4_kernel(
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     const int lr = lane >> 3, pc = lane & 7;
     const int srow = wv * 8 + lr;                                          // + 32 for the second piece (same swizzles)
-    const unsigned k_voff = (unsigned)(srow * ldk * 2 + ((pc ^ ((srow >> 1) & 7)) << 4));
-    const unsigned v_voff = (unsigned)(srow * ldv * 2 + ((pc ^ (((srow >> 1) & 1) << 2)) << 4));
+    const unsigned k_voff = (unsigned)(srow * ldk * 2 + (k_chunk(srow, pc) << 4));
+    const unsigned v_voff = (unsigned)(srow * ldv * 2 + (v_chunk(srow, pc) << 4));
     const half_t* kbase = k + (int64_t)bkv * Nk * ldk + head * D;
     const half_t* vbase = v + (int64_t)bkv * Nk * ldv + head * D;
     const __amdgpu_buffer_rsrc_t rsrc_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(kbase), 0, (unsigned)(Nk * ldk * 2), 0x00020000);
@@ -526,67 +559,55 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 2) void attention_v4_kernel(
         const lds_c_ptr dk = (lds_c_ptr)sK + buf * TILE + wv * 1024;
         const unsigned ks0 = (unsigned)(kt * KT * ldk * 2);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_k, dk, 16, k_voff, ks0, 0, 0);
-        if constexpr (NW == 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_k, dk + 4096, 16, k_voff, ks0 + (unsigned)(32 * ldk * 2), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_k, dk + 4096, 16, k_voff, ks0 + (unsigned)(32 * ldk * 2), 0, 0);
     };
     auto dma_v = [&](int kt, int buf) {
         const lds_c_ptr dv = (lds_c_ptr)sV + buf * TILE + wv * 1024;
         const unsigned vs0 = (unsigned)(kt * KT * ldv * 2);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_v, dv, 16, v_voff, vs0, 0, 0);
-        if constexpr (NW == 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_v, dv + 4096, 16, v_voff, vs0 + (unsigned)(32 * ldv * 2), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_v, dv + 4096, 16, v_voff, vs0 + (unsigned)(32 * ldv * 2), 0, 0);
     };
     // fragment read offsets inside a tile: per-lane constants; (sub, ss, buffer) only add immediates
     int k_off[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) k_off[ks] = fr * ROWB + (((ks * 2 + fh) ^ ((fr >> 1) & 7)) << 4);       // + sub * 32 * ROWB
-    const int tq = (lane & 15) >> 2, tp = lane & 3, tcol16 = (lane >> 4) & 1;
+    for (int ks = 0; ks < 4; ++ks) k_off[ks] = k_img(fr, ks * 2 + fh);       // + sub * 32 * ROWB
     int v_off[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
-        const int dcol = dt * 32 + tcol16 * 16 + 4 * tp;
-        const int row = 4 * fh + tq;                                      // + sub*32 + ss*16 (+8): leaves ((row >> 1) & 1) unchanged
-        v_off[dt] = row * ROWB + (((dcol >> 3) ^ (((row >> 1) & 1) << 2)) << 4) + (dcol & 7) * 2;
-    }
+    pv_lane_offsets(v_off, lane);
     const int nkt = (Nk + KT - 1) / KT;
 
-    // scores of one key tile: S'' = K.Q'^T - m_ref (the accumulator input of the first MFMA of each chain is -m_ref)
-    auto qk = [&](const char* kbuf, f32x16 (&s)[2], auto zero_tag) {
-        constexpr bool ZERO_REF = decltype(zero_tag)::value != 0;    // the reference of every query of this wave is 0: the accumulator input is the inline constant
-        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // scores of one key tile: S'' = K.Q'^T - m_ref (`acc0`, the accumulator input of the first MFMA of each chain, is -m_ref)
+    auto qk = [&](const char* kbuf, f32x16 (&s)[2], const f32x16& acc0) {
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const half8v kf = *reinterpret_cast<const half8v*>(kbuf + k_off[ks] + sub * 32 * ROWB);
-                s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? (ZERO_REF ? zero16 : negm) : s[sub], 0, 0, 0);
+                s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? acc0 : s[sub], 0, 0, 0);
             }
     };
-    // one key tile (K and V in slot B): scores, lazy reference, exp2/pack in four 16-key groups each followed by its 3 MFMAs
-    // (row sum + two O tiles), so a group's MFMAs run under the next group's exp2
+    // one key tile (K and V in slot B): scores, lazy reference, exp2/pack in four 16-key groups each followed by its 2 MFMAs
+    // (two O tiles), so a group's MFMAs run under the next group's exp2
     auto tile = [&](auto b_tag, f32x16 (&sc)[2], int kt) {
         constexpr int VB = decltype(b_tag)::value;
-        // Round 5: while the reference of every query of the wave is still 0 (`ref_zero`, wave-uniform) the score MFMAs take the inline
-        // constant 0 as their accumulator input and the 16 v_mov that rebuild the -m_ref operand per tile (64 of the tile's 960 issue-port
-        // cycles) are not executed.  The reference starts at 0 unless the first tile's maximum lies outside [-REF0_BAND, REF0_BAND] (then
-        // it is that maximum, as before) and moves, as before, when a tile maximum exceeds it by more than LAZY_THR: P <= 2^8 and the
-        // row's largest P >= 2^-REF0_BAND either way.
-#ifndef MOCA_ATTN_NO_ZERO_REF
+        // While the reference of every query of the wave is still 0 (`ref_zero`, wave-uniform) the score MFMAs take the inline constant 0
+        // as their accumulator input and the 16 v_mov that rebuild the -m_ref operand per tile are not executed.  The reference starts
+        // at 0 unless the first tile's maximum lies outside [-REF0_BAND, REF0_BAND] (then it is that maximum) and moves when a tile
+        // maximum exceeds it by more than LAZY_THR: P <= 2^8 and the row's largest P >= 2^-REF0_BAND either way.
         if (ref_zero) {
-            qk(sK + VB * TILE, sc, int_c<1>{});
-        } else
-#endif
-        {
-#ifndef MOCA_ATTN_NEGM_PERSISTENT   // -m_ref rebuilt per tile (16 v_mov) instead of living across it: 141 -> 121 VGPRs = 4 waves per SIMD, +3.5 %
+            const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            qk(sK + VB * TILE, sc, zero16);
+        } else {
+            f32x16 negm;                              // -m_ref replicated, rebuilt per tile
 #pragma unroll
             for (int r = 0; r < 16; ++r) negm[r] = -m_ref;
-#endif
-            qk(sK + VB * TILE, sc, int_c<0>{});
+            qk(sK + VB * TILE, sc, negm);
         }
         if ((kt + 1) * KT > Nk) {                     // keys beyond Nk (last tile only)
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = kt * KT + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+                    const int key = kt * KT + sub * 32 + score_key(r, fh);
                     if (key >= Nk) sc[sub][r] = -INFINITY;
                 }
         }
@@ -604,21 +625,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 2) void attention_v4_kernel(
         float tmax = vmax3(vmax3(t4[0], t4[1], t4[2]), t4[3], t4[3]);
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));      // both key halves of this query: the two lanes agree from here on
         if (kt == 0 || __any(tmax > LAZY_THR)) {      // move the reference (first tile: to its maximum unless that lies in the zero band)
-#ifndef MOCA_ATTN_NO_ZERO_REF
             const float delta = kt == 0 ? (fabsf(tmax) > REF0_BAND ? tmax : 0.f) : fmaxf(tmax, 0.f);
-#else
-            const float delta = kt == 0 ? tmax : fmaxf(tmax, 0.f);
-#endif
             const float alpha = __builtin_amdgcn_exp2f(-delta);          // (kt == 0: O and l are still zero)
             m_ref += delta;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                o[0][r] *= alpha; o[1][r] *= alpha; osum[r] *= alpha;
+                o[0][r] *= alpha; o[1][r] *= alpha;
                 if (r == 0) lsum *= alpha;
                 sc[0][r] -= delta; sc[1][r] -= delta;
-#ifdef MOCA_ATTN_NEGM_PERSISTENT
-                negm[r] = -m_ref;
-#endif
             }
             ref_zero = !__any(m_ref != 0.f);
         }
@@ -637,20 +651,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 2) void attention_v4_kernel(
                 const half4v plo = __builtin_shufflevector(h[0], h[1], 0, 1, 2, 3);
                 const half4v phi = __builtin_shufflevector(h[2], h[3], 0, 1, 2, 3);
                 const half8v pf = __builtin_shufflevector(plo, phi, 0, 1, 2, 3, 4, 5, 6, 7);
-#ifndef MOCA_ATTN_SUM_MFMA      // row sums by v_dot2_f32_f16 on the packed P (+5 % over a 4th "ones" MFMA per 16 keys, and 16 registers fewer)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) lsum = __builtin_amdgcn_fdot2(h[j], half2v{(half_t)1.0f, (half_t)1.0f}, lsum, false);
-#else
-                osum = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, pf, osum, 0, 0, 0);
-#endif
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const char* a0 = vbuf + v_off[dt] + (sub * 32 + ss * 16) * ROWB;
-                    const half4v lo = tr_read(a0);
-                    const half4v hi = tr_read(a0 + 8 * ROWB);
-                    const half8v vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                    o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o[dt], 0, 0, 0);
-                }
+                pv_step(o, vbuf, v_off, sub * 32 + ss * 16, pf);
             }
     };
 
@@ -675,34 +678,20 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 2) void attention_v4_kernel(
         }
     }
 
-#ifndef MOCA_ATTN_SUM_MFMA
     const float inv = 1.0f / (lsum + __shfl_xor(lsum, 32, 64));
-#else
-    const float inv = 1.0f / osum[0];
-#endif
     // O rows leave as whole 128-byte rows through the (now free) K/V buffers: wave w owns 4 KiB at smem + 4096 w (the last
     // barrier of the key loop retired every fragment read; each wave touches only its own 32 rows, so no further barrier)
     {
         char* wq = smem + wave * 32 * ROWB;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                half4v h4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h4[j] = (half_t)(o[dt][g * 4 + j] * inv);
-                const int d0 = dt * 32 + 8 * g + 4 * fh;
-                *reinterpret_cast<half4v*>(wq + fr * ROWB + (((d0 >> 3) ^ ((fr >> 1) & 7)) << 4) + (d0 & 7) * 2) = h4;
-            }
+        put_o_tile(wq, o, inv, lane);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = lane + 64 * i, row = c >> 3, ch = c & 7;
             if (q0 + row < Nq)
                 *reinterpret_cast<half8v*>(out + ((int64_t)bq * Nq + q0 + row) * ldo + head * D + ch * 8) =
-                    *reinterpret_cast<const half8v*>(wq + row * ROWB + ((ch ^ ((row >> 1) & 7)) << 4));
+                    *reinterpret_cast<const half8v*>(wq + k_img(row, ch));
         }
     }
-    (void)q_ok;
 #endif
 }
 
@@ -718,17 +707,8 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(
     int B, int T, int HW, int heads, int ld, int ldo, float scale_log2e) {
     __shared__ __attribute__((aligned(16))) char sV[4][16 * TV_ROWB];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t total = (int64_t)B * HW * heads;
-    int64_t prob = (int64_t)blockIdx.x * 4 + wave;
-    const bool active = prob < total;
-    if (!active) prob = total - 1;
-    const int head = (int)(prob % heads);
-    const int64_t bp = prob / heads;
-    const int pix = (int)(bp % HW), b = (int)(bp / HW);
-    // token row of frame t: (b*T + t)*HW + pix
-    const int64_t row0 = (int64_t)b * T * HW + pix;
-    const int64_t rstride = (int64_t)HW * ld;
-    const int64_t base = row0 * ld + head * D;
+    const TemporalProblem p = temporal_problem(B, T, HW, heads, ld, wave);
+    const int64_t rstride = p.rstride, base = p.base;
 
     const int fr = lane & 15, fg = lane >> 4;
     // K (A operand) and Q (B operand) fragments of S^T = K.Q^T: row fr, d = 32 ks + 8 fg + j
@@ -742,7 +722,7 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(
         }
         kf[ks] = a; qf[ks] = c;
     }
-    // V -> LDS row-major [key][d]
+    // V -> LDS row-major [key][d], padded rows (no swizzle: the 16 x 16 P.V reads single halves)
     char* sv = sV[wave];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -779,8 +759,8 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(
     const float inv = 1.0f / sum;
 
     // O^T[d][q] = V^T[d][key] . P^T[key][q]; A: lane (d = fr, k = 4 fg + j) = V[4fg+j][16dt + fr]
-    const bool st_ok = active && fr < T;
-    half_t* ob = out + (row0 + (int64_t)fr * HW) * ldo + head * D;
+    const bool st_ok = p.active && fr < T;
+    half_t* ob = out + (p.row0 + (int64_t)fr * HW) * ldo + p.head * D;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
         half4v vf;
@@ -801,10 +781,10 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(
 
 // ---- temporal attention over 17 .. 32 frames: one wavefront per (video, pixel, head) -------
 // The 32 frames of a pixel are one 32 x 32 score tile.  S^T = K.Q^T by four v_mfma_f32_32x32x16_f16 over d = 64: the lane
-// (r = lane & 31, h = lane >> 5) then holds S^T[key = (reg & 3) + 8 (reg >> 2) + 4 h][query = r], i.e. the key index lies in its 16
+// (r = lane & 31, h = lane >> 5) then holds S^T[key = score_key(reg, h)][query = r], i.e. the key index lies in its 16
 // registers and the query on the lane -- the softmax over keys is 15 in-lane max / adds and one exchange with lane ^ 32.  Registers
 // 8s .. 8s+7, rounded to fp16 once, ARE the B operand of k-step s of O^T = V^T.P^T (element j = key 16s + 8(j>>2) + 4h + (j&3)); the A
-// operand takes V in that same key order by two transposing 4-key LDS reads of the row-major V tile (as attention_kernel does).
+// operand takes V in that same key order by two transposing 4-key LDS reads of the row-major V image (pv_step).
 // Keys >= T get -inf before the row maximum, with CAUSAL keys above the query too (attention.py:101-105); the diagonal is never
 // masked and T >= 17 > 4h + 3, so every lane's maximum is finite.  Rows t >= T are neither loaded (zero fragments) nor stored.
 // No atomics, fixed order of every sum: replays are bit-identical.
@@ -813,20 +793,10 @@ template <bool CAUSAL>
 __global__ __launch_bounds__(256) void tattn_long_kernel(
     const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v, half_t* __restrict__ out,
     int B, int T, int HW, int heads, int ld, int ldo, float scale_log2e) {
-    // V row-major [key][d], 128-byte rows, chunk ^ (((row >> 1) & 1) << 2): the swizzle of attention_kernel's transposed reads
-    __shared__ __attribute__((aligned(16))) char sV[4][TL_T * ROWB];
+    __shared__ __attribute__((aligned(16))) char sV[4][TL_T * ROWB];          // one V image per wave
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t total = (int64_t)B * HW * heads;
-    int64_t prob = (int64_t)blockIdx.x * 4 + wave;
-    const bool active = prob < total;
-    if (!active) prob = total - 1;
-    const int head = (int)(prob % heads);
-    const int64_t bp = prob / heads;
-    const int pix = (int)(bp % HW), b = (int)(bp / HW);
-    // token row of frame t: (b*T + t)*HW + pix
-    const int64_t row0 = (int64_t)b * T * HW + pix;
-    const int64_t rstride = (int64_t)HW * ld;
-    const int64_t base = row0 * ld + head * D;
+    const TemporalProblem p = temporal_problem(B, T, HW, heads, ld, wave);
+    const int64_t rstride = p.rstride, base = p.base;
 
     const int fr = lane & 31, fh = lane >> 5;
     // K (A operand) and Q (B operand) fragments of S^T = K.Q^T: row fr, d = 16 ks + 8 fh + j
@@ -847,7 +817,7 @@ __global__ __launch_bounds__(256) void tattn_long_kernel(
         const int row = (lane >> 3) + 8 * i, ch = lane & 7;
         half8v a = {0, 0, 0, 0, 0, 0, 0, 0};
         if (row < T) a = *reinterpret_cast<const half8v*>(v + base + row * rstride + ch * 8);
-        *reinterpret_cast<half8v*>(sv + row * ROWB + ((ch ^ (((row >> 1) & 1) << 2)) << 4)) = a;
+        *reinterpret_cast<half8v*>(sv + v_img(row, ch)) = a;
     }
     __syncthreads();
 
@@ -856,13 +826,13 @@ __global__ __launch_bounds__(256) void tattn_long_kernel(
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[ks], s, 0, 0, 0);
-    // register r holds key (r & 3) + 8 (r >> 2) + 4 fh; the last key this lane's query sees is T - 1, with CAUSAL min(T - 1, fr):
-    // ONE comparison per register in both instantiations
-    const int last = (CAUSAL ? min(T - 1, fr) : T - 1) - 4 * fh;
+    // the last key this lane's query sees is T - 1, with CAUSAL min(T - 1, fr); taken relative to the lane half's first key, so that
+    // the mask is ONE comparison per register in both instantiations
+    const int last = (CAUSAL ? min(T - 1, fr) : T - 1) - score_key(0, fh);
     float mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        if ((r & 3) + 8 * (r >> 2) > last) s[r] = -INFINITY;
+        if (score_key(r, 0) > last) s[r] = -INFINITY;
         mx = fmaxf(mx, s[r]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -871,50 +841,49 @@ __global__ __launch_bounds__(256) void tattn_long_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         // (a masked key is zero whatever the sign of the scale: the tail keys are masked in the non-causal form too)
-        const float pv = (r & 3) + 8 * (r >> 2) > last ? 0.f : exp2f((s[r] - mx) * scale_log2e);
+        const float pv = score_key(r, 0) > last ? 0.f : exp2f((s[r] - mx) * scale_log2e);
         sum += pv;
         pf[r >> 3][r & 7] = (half_t)pv;
     }
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.0f / sum;
 
-    // O^T[d][q] = V^T[d][key] . P^T[key][q]: the transposed read of a 16-lane group (lane i = 4 tq + tp) delivers to lane i the column
-    // d = 32 dt + 16 tcol16 + i of the 4 keys 16 ss + 4 fh + (0 .. 3); the second read is 8 keys further
-    const int tq = (lane & 15) >> 2, tp = lane & 3, tcol16 = (lane >> 4) & 1;
+    int v_off[2];
+    pv_lane_offsets(v_off, lane);
     f32x16 o[2];
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
+    for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
 #pragma unroll
-        for (int ss = 0; ss < 2; ++ss) {
-            const int ra = ss * 16 + 4 * fh + tq, rb = ra + 8;
-            const int dcol = dt * 32 + tcol16 * 16 + 4 * tp;
-            const int ch = dcol >> 3, within = (dcol & 7) * 2;
-            const half4v lo = tr_read(sv + ra * ROWB + ((ch ^ (((ra >> 1) & 1) << 2)) << 4) + within);
-            const half4v hi = tr_read(sv + rb * ROWB + ((ch ^ (((rb >> 1) & 1) << 2)) << 4) + within);
-            const half8v vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[ss], o[dt], 0, 0, 0);
-        }
-    }
-    // lane holds O^T[d = 32 dt + 8 g + 4 fh + j][q = fr]: 8-byte stores
-    if (active && fr < T) {
-        half_t* ob = out + (row0 + (int64_t)fr * HW) * ldo + head * D;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                half4v h4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h4[j] = (half_t)(o[dt][g * 4 + j] * inv);
-                *reinterpret_cast<half4v*>(ob + dt * 32 + 8 * g + 4 * fh) = h4;
-            }
-    }
+    for (int ss = 0; ss < 2; ++ss) pv_step(o, sv, v_off, ss * 16, pf[ss]);
+    if (p.active && fr < T) store_o_frags(out + (p.row0 + (int64_t)fr * HW) * ldo + p.head * D, o, inv, fh);
 }
 
-// Entry checks follow the widest access a kernel makes on an operand: 16-byte loads / LDS-DMA on q, k, v everywhere; 16-byte row
-// stores of `out` in the short and long-key kernels, 8-byte stores in attention_kernel and the temporal kernels.
+// ---- host side -----------------------------------------------------------------------------------------------------------
+constexpr float LOG2E = 1.4426950408889634f;      // the kernels take scale * log2(e): their exponentials are exp2
+
 inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+
+// The checks every entry shares, following the widest access a kernel makes on an operand.  `in`: q, k, v (and k_ip, v_ip) with
+// their leading dimensions, read by 16-byte loads / LDS-DMA everywhere: 16-byte aligned, ld % 8.  `out` is stored in pieces of
+// `store_bytes`: 16 (whole 16-byte pieces of a row: the short and the long-key kernel, so every route of moca_attention_f16) or 8 (one
+// lane's four halves: attention_kernel alone, the temporal kernels), i.e. ldo % 8 or ldo % 4.  `grid_y`: blocks along y (65535 at most).
+struct AttnOperand { const void* p; int ld; };
+template <size_t N>
+bool attn_args_ok(const AttnOperand (&in)[N], const void* out, int ldo, int store_bytes, int heads, int64_t grid_y) {
+    if (heads <= 0 || !out || misaligned(out, store_bytes) || ldo % (store_bytes / 2) || ldo < heads * D) return false;
+    for (const AttnOperand& a : in)
+        if (!a.p || misaligned(a.p, 16) || a.ld % 8 || a.ld < heads * D) return false;
+    return grid_y <= 65535;
+}
+
+// the launch list every kernel starts with: 256 threads, q, k, v, out as halves, then the kernel's own arguments
+template <class Kernel, class... Args>
+void launch_qkvo(Kernel kernel, dim3 grid, void* stream, const void* q, const void* k, const void* v, void* out, Args... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, moca_stream(stream), reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
+                       reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out), args...);
+}
 
 template <bool IP>
 void launch_short(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* out, int Bq, int heads, int Nq,
@@ -926,12 +895,23 @@ void launch_short(const void* q, const void* k, const void* v, const void* k_ip,
     if (q_iters < 1) q_iters = 1;
     if (q_iters > 8) q_iters = 8;
     if (q_iters > qgroups) q_iters = qgroups;
-    const dim3 grid_s((qgroups + q_iters - 1) / q_iters, Bq * heads), block(256);
-    hipLaunchKernelGGL(attention_short_kernel<IP>, grid_s, block, 0, moca_stream(stream),
-                       reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
-                       reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
-                       heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale * 1.4426950408889634f, q_iters,
-                       reinterpret_cast<const half_t*>(k_ip), reinterpret_cast<const half_t*>(v_ip), ldk_ip, ldv_ip, Nt, ip_scale);
+    launch_qkvo(attention_short_kernel<IP>, dim3((qgroups + q_iters - 1) / q_iters, Bq * heads), stream, q, k, v, out,
+                heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale * LOG2E, q_iters,
+                reinterpret_cast<const half_t*>(k_ip), reinterpret_cast<const half_t*>(v_ip), ldk_ip, ldv_ip, Nt, ip_scale);
+}
+
+// The three temporal entries: frame counts [t_min, t_max] go to `kernel` (one wave per problem, four per block).  `grid_check`:
+// refuse a launch of more than INT32_MAX blocks (the long entry; the T <= 16 entries never have).
+typedef void (*temporal_kernel_t)(const half_t*, const half_t*, const half_t*, half_t*, int, int, int, int, int, int, float);
+int launch_temporal(temporal_kernel_t kernel, int t_min, int t_max, bool grid_check, const void* q, const void* k, const void* v, void* out,
+                    int32_t B, int32_t T, int32_t HW, int32_t heads, int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
+    if (B <= 0 || T < t_min || T > t_max || HW <= 0) return MOCA_E_BADARG;
+    if (!attn_args_ok({{q, ld_qkv}, {k, ld_qkv}, {v, ld_qkv}}, out, ldo, 8, heads, 1)) return MOCA_E_BADARG;
+    const int64_t total = (int64_t)B * HW * heads;
+    if (grid_check && (total + 3) / 4 > INT32_MAX) return MOCA_E_BADARG;
+    launch_qkvo(kernel, dim3((unsigned)((total + 3) / 4)), stream, q, k, v, out, B, T, HW, heads, ld_qkv, ldo, scale * LOG2E);
+    MOCA_CHECK_LAUNCH();
+    return MOCA_OK;
 }
 
 }  // namespace
@@ -940,35 +920,17 @@ extern "C" int moca_attention_f16(const void* q, const void* k, const void* v, v
                                   int32_t Bq, int32_t heads, int32_t Nq, int32_t Nk,
                                   int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
                                   int32_t kv_div, float scale, void* stream) {
-    if (!q || !k || !v || !out) return MOCA_E_BADARG;
     if (Bq <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0 || kv_div <= 0 || Bq % kv_div) return MOCA_E_BADARG;
-    // the short and the long-key kernel store whole 16-byte pieces of an output row: ldo % 8 and a 16-byte aligned `out` on every route
-    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(out, 16)) return MOCA_E_BADARG;
-    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) return MOCA_E_BADARG;
-    if (ldq < heads * D || ldk < heads * D || ldv < heads * D || ldo < heads * D) return MOCA_E_BADARG;
-    if ((int64_t)Bq * heads > 65535) return MOCA_E_BADARG;
+    if (!attn_args_ok({{q, ldq}, {k, ldk}, {v, ldv}}, out, ldo, 16, heads, (int64_t)Bq * heads)) return MOCA_E_BADARG;
     // the long-key kernel addresses K and V of one video by 32-bit byte offsets (buffer descriptor, whole 64-key tiles)
     if (((int64_t)Nk + KT - 1) / KT * KT * (ldk > ldv ? ldk : ldv) * 2 > INT32_MAX) return MOCA_E_BADARG;
-    const dim3 grid((Nq + QB - 1) / QB, Bq * heads), block(256);
-    if (Nk >= 2 * KT) {
-        // (an 8-wave form, 256 queries per block, measured -2.8 % at 2560 tokens in isolation and -0.1 % on the whole step in round 2:
-        //  not kept)
-        hipLaunchKernelGGL(attention_v4_kernel<4>, grid, block, 0, moca_stream(stream),
-                           reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
-                           reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
-                           heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale * 1.4426950408889634f);
-        MOCA_CHECK_LAUNCH();
-        return MOCA_OK;
-    }
-    if (Nk <= KS96) {
+    const dim3 grid((Nq + QB - 1) / QB, Bq * heads);
+    if (Nk >= 2 * KT)
+        launch_qkvo(attention_v4_kernel<4>, grid, stream, q, k, v, out, heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale * LOG2E);
+    else if (Nk <= KS96)
         launch_short<false>(q, k, v, nullptr, nullptr, out, Bq, heads, Nq, Nk, Nk, ldq, ldk, ldv, 0, 0, ldo, kv_div, scale, 0.f, stream);
-        MOCA_CHECK_LAUNCH();
-        return MOCA_OK;
-    }
-    hipLaunchKernelGGL(attention_kernel<false>, grid, block, 0, moca_stream(stream),
-                       reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
-                       reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
-                       heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale * 1.4426950408889634f);
+    else
+        launch_qkvo(attention_kernel<false>, grid, stream, q, k, v, out, heads, Nq, Nk, ldq, ldk, ldv, ldo, kv_div, scale * LOG2E);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }
@@ -977,16 +939,12 @@ extern "C" int moca_attention_ip_f16(const void* q, const void* k, const void* v
                                      int32_t Bq, int32_t heads, int32_t Nq, int32_t Nt, int32_t Ni,
                                      int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldk_ip, int32_t ldv_ip, int32_t ldo,
                                      int32_t kv_div, float scale, float ip_scale, void* stream) {
-    if (!q || !k || !v || !k_ip || !v_ip || !out) return MOCA_E_BADARG;
-    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(k_ip, 16) || misaligned(v_ip, 16) || misaligned(out, 16))
-        return MOCA_E_BADARG;
     if (Bq <= 0 || heads <= 0 || Nq <= 0 || Nt < 1 || Ni < 0 || Nt + Ni > KS96 || kv_div <= 0 || Bq % kv_div) return MOCA_E_BADARG;
     if (Ni > 0 && (Nt > IP_ROW0 || Ni > KS96 - IP_ROW0)) return MOCA_E_BADARG;     // the fixed text / image rows of the tile
-    if (ldq % 8 || ldk % 8 || ldv % 8 || ldk_ip % 8 || ldv_ip % 8 || ldo % 8) return MOCA_E_BADARG;
-    if (ldq < heads * D || ldk < heads * D || ldv < heads * D || ldk_ip < heads * D || ldv_ip < heads * D || ldo < heads * D)
+    if (!attn_args_ok({{q, ldq}, {k, ldk}, {v, ldv}, {k_ip, ldk_ip}, {v_ip, ldv_ip}}, out, ldo, 16, heads, (int64_t)Bq * heads))
         return MOCA_E_BADARG;
     // |ip_scale| <= 64: the scaled image P (<= ip_scale * l_text <= 64 * 80) stays far inside the fp16 range; rejects inf and NaN too
-    if ((int64_t)Bq * heads > 65535 || !(fabsf(ip_scale) <= 64.f)) return MOCA_E_BADARG;
+    if (!(fabsf(ip_scale) <= 64.f)) return MOCA_E_BADARG;
     if (Ni == 0)   // no image tokens (a 77-token context): exactly moca_attention_f16's launch, bit for bit
         launch_short<false>(q, k, v, nullptr, nullptr, out, Bq, heads, Nq, Nt, Nt, ldq, ldk, ldv, 0, 0, ldo, kv_div, scale, 0.f, stream);
     else
@@ -999,32 +957,10 @@ extern "C" int moca_attention_ip_f16(const void* q, const void* k, const void* v
 extern "C" int moca_attention_causal_f16(const void* q, const void* k, const void* v, void* out,
                                          int32_t B, int32_t heads, int32_t N, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
                                          float scale, void* stream) {
-    if (!q || !k || !v || !out || B <= 0 || heads <= 0 || N <= 0) return MOCA_E_BADARG;
-    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(out, 8)) return MOCA_E_BADARG;   // attention_kernel: 8-byte stores
-    if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4) return MOCA_E_BADARG;
-    if (ldq < heads * D || ldk < heads * D || ldv < heads * D || ldo < heads * D) return MOCA_E_BADARG;
-    if ((int64_t)B * heads > 65535) return MOCA_E_BADARG;
-    const dim3 grid((N + QB - 1) / QB, B * heads), block(256);
-    hipLaunchKernelGGL(attention_kernel<true>, grid, block, 0, moca_stream(stream),
-                       reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
-                       reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
-                       heads, N, N, ldq, ldk, ldv, ldo, 1, scale * 1.4426950408889634f);
-    MOCA_CHECK_LAUNCH();
-    return MOCA_OK;
-}
-
-static int launch_temporal_attention(bool causal, const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T, int32_t HW,
-                                     int32_t heads, int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
-    if (!q || !k || !v || !out) return MOCA_E_BADARG;
-    if (B <= 0 || T <= 0 || T > 16 || HW <= 0 || heads <= 0) return MOCA_E_BADARG;
-    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(out, 8)) return MOCA_E_BADARG;   // 16-byte loads, 8-byte stores
-    if (ld_qkv % 8 || ldo % 4 || ld_qkv < heads * D || ldo < heads * D) return MOCA_E_BADARG;
-    const int64_t total = (int64_t)B * HW * heads;
-    const dim3 grid((unsigned)((total + 3) / 4)), block(256);
-    hipLaunchKernelGGL(causal ? temporal_attention_kernel<true> : temporal_attention_kernel<false>, grid, block, 0, moca_stream(stream),
-                       reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
-                       reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
-                       B, T, HW, heads, ld_qkv, ldo, scale * 1.4426950408889634f);
+    if (B <= 0 || heads <= 0 || N <= 0) return MOCA_E_BADARG;
+    if (!attn_args_ok({{q, ldq}, {k, ldk}, {v, ldv}}, out, ldo, 8, heads, (int64_t)B * heads)) return MOCA_E_BADARG;
+    launch_qkvo(attention_kernel<true>, dim3((N + QB - 1) / QB, B * heads), stream, q, k, v, out, heads, N, N, ldq, ldk, ldv, ldo, 1,
+                scale * LOG2E);
     MOCA_CHECK_LAUNCH();
     return MOCA_OK;
 }
@@ -1032,32 +968,22 @@ static int launch_temporal_attention(bool causal, const void* q, const void* k, 
 extern "C" int moca_temporal_attention_f16(const void* q, const void* k, const void* v, void* out,
                                            int32_t B, int32_t T, int32_t HW, int32_t heads,
                                            int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
-    return launch_temporal_attention(false, q, k, v, out, B, T, HW, heads, ld_qkv, ldo, scale, stream);
+    return launch_temporal(temporal_attention_kernel<false>, 1, 16, false, q, k, v, out, B, T, HW, heads, ld_qkv, ldo, scale, stream);
 }
 
 extern "C" int moca_temporal_attention_causal_f16(const void* q, const void* k, const void* v, void* out,
                                                   int32_t B, int32_t T, int32_t HW, int32_t heads,
                                                   int32_t ld_qkv, int32_t ldo, float scale, void* stream) {
     if (!(scale > 0.f)) return MOCA_E_BADARG;          // (the mask is applied before the scale: -inf must stay -inf)
-    return launch_temporal_attention(true, q, k, v, out, B, T, HW, heads, ld_qkv, ldo, scale, stream);
+    return launch_temporal(temporal_attention_kernel<true>, 1, 16, false, q, k, v, out, B, T, HW, heads, ld_qkv, ldo, scale, stream);
 }
 
 // 17 <= T <= 32 (T <= 16 stays with the two entries above: one kernel per frame count, and their bits do not move)
 extern "C" int moca_temporal_attention_long_f16(const void* q, const void* k, const void* v, void* out,
                                                 int32_t B, int32_t T, int32_t HW, int32_t heads,
                                                 int32_t ld_qkv, int32_t ldo, float scale, int32_t causal, void* stream) {
-    if (!q || !k || !v || !out) return MOCA_E_BADARG;
-    if (B <= 0 || T <= 16 || T > TL_T || HW <= 0 || heads <= 0 || (causal != 0 && causal != 1)) return MOCA_E_BADARG;
+    if (causal != 0 && causal != 1) return MOCA_E_BADARG;
     if (causal && !(scale > 0.f)) return MOCA_E_BADARG;          // (the mask is applied before the scale: -inf must stay -inf)
-    if (misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(out, 8)) return MOCA_E_BADARG;   // 16-byte loads, 8-byte stores
-    if (ld_qkv % 8 || ldo % 4 || ld_qkv < heads * D || ldo < heads * D) return MOCA_E_BADARG;
-    const int64_t total = (int64_t)B * HW * heads;
-    if ((total + 3) / 4 > INT32_MAX) return MOCA_E_BADARG;
-    const dim3 grid((unsigned)((total + 3) / 4)), block(256);
-    hipLaunchKernelGGL(causal ? tattn_long_kernel<true> : tattn_long_kernel<false>, grid, block, 0, moca_stream(stream),
-                       reinterpret_cast<const half_t*>(q), reinterpret_cast<const half_t*>(k),
-                       reinterpret_cast<const half_t*>(v), reinterpret_cast<half_t*>(out),
-                       B, T, HW, heads, ld_qkv, ldo, scale * 1.4426950408889634f);
-    MOCA_CHECK_LAUNCH();
-    return MOCA_OK;
+    return launch_temporal(causal ? tattn_long_kernel<true> : tattn_long_kernel<false>, 17, TL_T, true, q, k, v, out, B, T, HW, heads, ld_qkv,
+                           ldo, scale, stream);
 }

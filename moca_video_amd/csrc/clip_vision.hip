@@ -28,16 +28,6 @@ constexpr int A80_ROWB = 176;      // bytes per LDS row: 160 B of data + 16 B pa
 constexpr int A80_CH = D80 / 8;    // 16-byte chunks per row
 constexpr int A80_PIECES = 2 * A80_KT * A80_CH / 256;   // 16-byte K and V pieces per thread and tile (5)
 
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) short4v* lds_s4_ptr;
-
-// ds_read_b64_tr_b16: a 16-lane group reads a 4-row x 16-column block of 16-bit elements and receives it column-major (lane i gets
-// column i of the 4 rows, element j from row j).  Lane i = 4q+p supplies the address of row q, columns 4p..4p+3.
-__device__ __forceinline__ half4v tr_read80(const char* addr) {
-    const short4v v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)addr);
-    return __builtin_bit_cast(half4v, v);
-}
-
 __global__ __launch_bounds__(256, 4) void clip_attention_d80_kernel(
     const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v, half_t* __restrict__ out,
     int heads, int N, int ldq, int ldk, int ldv, int ldo, float scale_log2e) {
@@ -150,7 +140,7 @@ __global__ __launch_bounds__(256, 4) void clip_attention_d80_kernel(
         for (int dt = 0; dt < 5; ++dt)
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const half4v vf = tr_read80(sV + (16 * t + 4 * fg + (fr >> 2)) * A80_ROWB + (16 * dt + 4 * (fr & 3)) * 2);
+                const half4v vf = lds_tr_read_b64(sV + (16 * t + 4 * fg + (fr >> 2)) * A80_ROWB + (16 * dt + 4 * (fr & 3)) * 2);
                 o[dt] = __builtin_amdgcn_mfma_f32_16x16x16f16(vf, pf[t], o[dt], 0, 0, 0);
             }
     }

@@ -13,6 +13,20 @@ typedef float    f32x16 __attribute__((ext_vector_type(16)));
 
 #define MOCA_WAVE 64
 
+// ds_read_b64_tr_b16, the CDNA4 transposing LDS read: a 16-lane group reads a 4-row x 16-column block of 16-bit elements and receives
+// it column-major (lane i gets column i of the 4 rows, element j from row j).  Lane i = 4q+p supplies the address of row q, columns
+// 4p..4p+3.  (The host pass only needs a body: the builtin belongs to the device target.)
+typedef short lds_short4v __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) lds_short4v* lds_short4v_ptr;
+__device__ __forceinline__ half4v lds_tr_read_b64(const char* addr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const lds_short4v v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4v_ptr)addr);
+    return __builtin_bit_cast(half4v, v);
+#else
+    return half4v{0, 0, 0, 0};
+#endif
+}
+
 #define MOCA_CHECK_LAUNCH()                                  \
     do {                                                     \
         hipError_t e__ = hipGetLastError();                  \

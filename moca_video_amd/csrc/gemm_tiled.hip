@@ -729,17 +729,7 @@ __global__ __launch_bounds__(256, 2) void gemm_g4_kernel(const moca_gemm_params 
 
 // cross-lane steps of the in-epilogue temporal attention as VALU lane swaps (v_permlane16_swap / v_permlane32_swap: with both operands
 // equal to x, the two results hold x and its partner 16 / 32 lanes away in every lane -- cdna_hip_programming.md T12 / T21) instead of
-// ds_bpermute round trips through the LDS pipe; and the V^T operand by the transposing LDS read (attention.hip: tr_read)
-typedef short tq_short4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) tq_short4v* tq_lds_s4_ptr;
-__device__ __forceinline__ half4v tattn_tr_read(const char* addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const tq_short4v v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tq_lds_s4_ptr)addr);
-    return __builtin_bit_cast(half4v, v);
-#else
-    return half4v{0, 0, 0, 0};
-#endif
-}
+// ds_bpermute round trips through the LDS pipe; and the V^T operand by the transposing LDS read (common.h: lds_tr_read_b64)
 #if defined(__HIP_DEVICE_COMPILE__)
 #define MOCA_XLANE(NAME, SWAP, OP)                                                                         \
     __device__ __forceinline__ float NAME(float x) {                                                       \

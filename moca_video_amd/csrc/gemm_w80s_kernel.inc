@@ -414,7 +414,7 @@ __global__ __launch_bounds__(512, 2) void MOCA_W80S_NAME(const moca_gemm_params 
             const char* base = smem + (pixs[i] * 16) * pitch;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
-                vfr[i][dt] = tattn_tr_read(base + (4 * fg + (fr >> 2)) * pitch + (128 + dt * 16 + 4 * (fr & 3)) * 2);
+                vfr[i][dt] = lds_tr_read_b64(base + (4 * fg + (fr >> 2)) * pitch + (128 + dt * 16 + 4 * (fr & 3)) * 2);
         }
         f32x4 sc[NPX];
 #pragma unroll

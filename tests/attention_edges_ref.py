@@ -1,4 +1,5 @@
-"""Operands, layouts and float64 torch restatements for tests/test_attention_edges_gpu.py.
+"""Operands, layouts and float64 torch restatements for tests/test_attention_edges_gpu.py; at the end, the cases whose outputs
+tests/test_attention_parent_gpu.py pins by hash against the parent commit.
 
 Every reference works on the fp16-rounded operands it is handed (any strides, any device) and returns float64; the metric is taken
 per (batch, head) slice so that a wrong slice cannot hide under another slice's maximum.  Nothing here touches a GPU by itself:
@@ -164,3 +165,85 @@ def onehot_gap(q, k, heads, kv_div, scale, hot, D=64, causal=False):
     top = torch.gather(s, 3, idx)
     rest = s.scatter(3, idx, float("-inf")).amax(-1, keepdim=True)
     return (top - rest).min().item()
+
+
+# ---------------------------------------------------------------- outputs pinned by hash against the parent commit
+# tests/golden/attention_parent_sha.npz (tools/record_parent_fixtures.py --attention-sha; tests/test_attention_parent_gpu.py): the smallest
+# shapes that reach every instantiation and branch of csrc/attention.hip, plus one head-dim-80 launch.  (route, name, kind, parameters);
+# the operands of a case come from gen(crc32(name)), so recorder and test build the same bits in any order.
+def _parent_cases():
+    out = []
+    add = lambda route, kind, **p: out.append((route, ".".join([kind] + [f"{k}{v}" for k, v in p.items()]), kind, p))
+    two = [dict(Bq=4, heads=2, kv_div=2, Nq=130), dict(Bq=64, heads=8, kv_div=16, Nq=300)]          # the second: q_iters = 2
+    add("short", "attn", Nk=77, **two[0]), add("short", "attn", Nk=96, **two[0]), add("short", "attn", Nk=77, **two[1])
+    for shape in two:
+        for Ni in (16, 4):
+            add("short_ip", "ip", Nt=77, Ni=Ni, **shape)
+    for Nk in (97, 127):
+        for Nq in (1, 33, 130):
+            add("generic", "attn", Nk=Nk, Bq=4, heads=2, kv_div=2, Nq=Nq)
+    for N in (77, 200):
+        for B, heads in ((4, 2), (3, 3)):                         # grid.y = 8: remapped block order; 9: plain
+            add("causal", "causal", N=N, B=B, heads=heads)
+    for Nk in (128, 129, 191, 193, 320):
+        for Nq in (130, 300):
+            add("v4", "attn", Nk=Nk, Bq=4, heads=2, kv_div=2, Nq=Nq), add("v4", "attn", Nk=Nk, Bq=3, heads=3, kv_div=1, Nq=Nq)
+    for regime in ("high", "late_peak", "band_edge"):             # the reference moves off 0 / moves late / stays in the zero band
+        add("v4_regimes", "regime", regime=regime, Nk=320, Bq=2, heads=2, Nq=256)
+    for B, T, HW, heads in ((2, 16, 50, 5), (1, 8, 64, 8), (1, 16, 2560, 5), (3, 5, 7, 2)):          # temporal_variants_ref.STANDALONE
+        add("temporal_causal", "temporal", causal=1, B=B, T=T, HW=HW, heads=heads)
+    for T in (17, 24, 32):
+        for causal in (0, 1):
+            for B, HW, heads in ((2, 7, 2), (1, 64, 5)):
+                add("temporal_long", "temporal", causal=causal, B=B, T=T, HW=HW, heads=heads)
+    add("d80", "d80", B=1, heads=16, N=257)
+    return out
+
+
+PARENT_CASES = _parent_cases()
+PARENT_ROUTES = sorted({c[0] for c in PARENT_CASES})
+
+
+def sha(t):
+    import hashlib
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def run_parent_case(ops, name, kind, p, dev="cuda"):
+    """one launch of a PARENT_CASES entry on freshly generated operands; returns the output, which was pre-filled with NaN"""
+    import zlib
+    g = gen(zlib.crc32(name.encode()))
+    nan_out = lambda *shape: torch.full(shape, NAN, dtype=torch.float16, device=dev)
+    scale = 0.125
+    if kind in ("attn", "ip", "regime"):
+        Bq, heads, Nq, kv_div = p["Bq"], p["heads"], p["Nq"], p.get("kv_div", 1)
+        C, Bk, Nk = heads * 64, Bq // kv_div, p.get("Nk", p.get("Nt"))
+        q, k, v = randh(g, Bq, Nq, C), randh(g, Bk, Nk, C), randh(g, Bk, Nk, C)
+        if kind == "regime":
+            apply_regime(p["regime"], q, [(k, 1.0)], scale, 64, [(0, 300, 7, 6.0), (0, 30, 7, 1.5)])
+        q, k, v = q.to(dev), k.to(dev), v.to(dev)
+        out = nan_out(Bq, Nq, C)
+        if kind == "ip":
+            ki, vi = randh(g, Bk, p["Ni"], C).to(dev), randh(g, Bk, p["Ni"], C).to(dev)
+            ops.attention_ip(q, k, v, ki, vi, out, Bq=Bq, heads=heads, Nq=Nq, Nt=Nk, Ni=p["Ni"], ldq=C, ldk=C, ldv=C, ldk_ip=C, ldv_ip=C,
+                             ldo=C, kv_div=kv_div, scale=scale, ip_scale=0.7)
+        else:
+            ops.attention(q, k, v, out, Bq=Bq, heads=heads, Nq=Nq, Nk=Nk, ldq=C, ldk=C, ldv=C, ldo=C, kv_div=kv_div, scale=scale)
+    elif kind in ("causal", "d80"):
+        B, heads, N = p["B"], p["heads"], p["N"]
+        C = heads * (80 if kind == "d80" else 64)
+        q, k, v = (randh(g, B, N, C).to(dev) for _ in range(3))
+        out = nan_out(B, N, C)
+        fn, scale = (ops.attention_d80, 80 ** -0.5) if kind == "d80" else (ops.attention_causal, scale)
+        fn(q, k, v, out, B=B, heads=heads, N=N, ldq=C, ldk=C, ldv=C, ldo=C, scale=scale)
+    else:
+        B, T, HW, heads, causal = p["B"], p["T"], p["HW"], p["heads"], bool(p["causal"])
+        C = heads * 64
+        qkv = randh(g, B * T * HW, 3 * C).to(dev)                  # q | k | v side by side, as the projection leaves them
+        out = nan_out(B * T * HW, C)
+        kw = dict(B=B, T=T, HW=HW, heads=heads, ld_qkv=3 * C, ldo=C, scale=scale)
+        if T > 16:
+            ops.temporal_attention_long(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], out, causal=causal, **kw)
+        else:
+            (ops.temporal_attention_causal if causal else ops.temporal_attention)(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], out, **kw)
+    return out

@@ -10,6 +10,9 @@ optimisation or a compiler bump legitimately changes them:
   tests/golden/temporal_attention_parent_sha.npz (--sha, on the GPU)  sha256 of the outputs of moca_temporal_attention_f16 and of the
                                                  non-causal MOCA_EP_TATTN launch on the host-generated operands of
                                                  tests/temporal_variants_ref.py
+  tests/golden/attention_parent_sha.npz          (--attention-sha, on the GPU)  sha256 of the outputs of every kernel of csrc/attention.hip
+                                                 (and of moca_attention_d80_f16) on the cases and host-generated operands of
+                                                 tests/attention_edges_ref.py::PARENT_CASES
   tests/golden/sampler_routes.npz                (--samplers, no GPU)  the traces of tests/sampler_routes_cpu.py::record: the UNet entry
                                                  points and launches of the sampling layer (guidance routing, host-issued loops,
                                                  ddim_step, queue noising, the host-driven FIFO loop, `supported()` tables, the
@@ -19,9 +22,10 @@ optimisation or a compiler bump legitimately changes them:
     git worktree add ../base <commit> && make -C ../base/moca_video_amd/csrc
     python tools/record_parent_fixtures.py --tree ../base --plans          (any host)
     python tools/record_parent_fixtures.py --tree ../base --sha            (on the MI355X)
+    python tools/record_parent_fixtures.py --tree ../base --attention-sha  (on the MI355X)
     python tools/record_parent_fixtures.py --tree ../base --samplers       (any host)
 
-The package is imported from --tree, the helpers (tests/plan_cpu.py, tests/temporal_variants_ref.py) and the output directory are this
+The package is imported from --tree, the helpers (tests/plan_cpu.py, tests/temporal_variants_ref.py, tests/attention_edges_ref.py) and the output directory are this
 checkout's.  A tree older than the host-recordable plan (no `UNetModel._pack(dev)`, a stream created unconditionally) is recorded
 through two stand-ins defined here; nothing of it is modified."""
 import argparse
@@ -92,6 +96,20 @@ def record_sha():
     np.savez_compressed(os.path.join(GOLD, "temporal_attention_parent_sha.npz"), names=np.asarray(names), sha256=np.asarray(shas))
 
 
+def record_attention_sha():
+    from moca_video_amd import ops
+    import attention_edges_ref as R
+    names, shas = [], []
+    for route, name, kind, p in R.PARENT_CASES:
+        out = R.run_parent_case(ops, name, kind, p)
+        torch.cuda.synchronize()
+        assert not torch.isnan(out).any(), f"{name}: an output row was not written"
+        names.append(name)
+        shas.append(R.sha(out))
+        print(route, name, shas[-1])
+    np.savez_compressed(os.path.join(GOLD, "attention_parent_sha.npz"), names=np.asarray(names), sha256=np.asarray(shas))
+
+
 def record_samplers():
     import sampler_routes_cpu
     out = sampler_routes_cpu.record()
@@ -104,6 +122,7 @@ def main():
     ap.add_argument("--tree", required=True, help="checkout (with its built library) to record from")
     ap.add_argument("--plans", action="store_true")
     ap.add_argument("--sha", action="store_true")
+    ap.add_argument("--attention-sha", action="store_true")
     ap.add_argument("--samplers", action="store_true")
     a = ap.parse_args()
     tree = os.path.abspath(a.tree)
@@ -115,6 +134,8 @@ def main():
         record_plans()
     if a.sha:
         record_sha()
+    if a.attention_sha:
+        record_attention_sha()
     if a.samplers:
         record_samplers()
 
