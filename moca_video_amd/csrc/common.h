@@ -206,6 +206,15 @@ __device__ __forceinline__ double moca_gstat_get(const int64_t* acc, int comp) {
     if (comp && (unsigned long long)*acc >= (MOCA_GSTAT_POISON >> 1)) return __longlong_as_double(0x7ff8000000000000ll);
     return (double)*acc * (comp ? 1.0 / MOCA_GSTAT_SQ_SCALE : 1.0 / MOCA_GSTAT_SUM_SCALE);
 }
+// GroupNorm statistics finished: the sum and the sum of squares of 1 / inv_count values -> mean and 1 / sqrt(variance + eps), in fp64
+// (E[x^2] - mean^2 cancels; what rounding leaves below zero is zero)
+struct moca_gn_stat { double mean, rstd; };
+__device__ __forceinline__ moca_gn_stat moca_gn_finish(double sum, double sq, double inv_count, float eps) {
+    const double mean = sum * inv_count;
+    double var = sq * inv_count - mean * mean;
+    if (var < 0.0) var = 0.0;
+    return {mean, 1.0 / sqrt(var + (double)eps)};
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -21,6 +21,10 @@ must EQUAL sum(x) 2^20 and sum(x^2) 2^12.
 
 `restated(case, inp, wrong)` is the sums-based restatement with one of MUTATIONS applied; the CPU file shows that every case tells
 every mutation that applies to it from the reference.
+
+The launches of a case on guarded operands (`run_case`, `accumulate`, `fold_run`) live here too: tests/test_norm_edges_gpu.py judges what
+they leave against the references above, tests/test_norm_parent_gpu.py and tools/record_parent_fixtures.py --norm-sha hash it
+(`parent_hashes`).
 """
 import zlib
 
@@ -493,6 +497,130 @@ def check_blocks(got, ref, fps, what, group=None, tol=TOL16):
     return worst
 
 
+# ----------------------------------------------------------------------------------------------------------------- launches (GPU)
+DEV = "cuda"
+GUARD = 4                       # guard rows in front of and behind every operand
+NAN = float("nan")
+POISON = 1 << 62                # an accumulator that reads as NaN (csrc/common.h)
+
+
+class Guarded:
+    """a contiguous tensor of `shape` with GUARD rows of `fill` in front of it and behind it (a row = the last dimension)"""
+
+    def __init__(self, shape, dtype, fill, data=None, inner=None):
+        shape = tuple(shape)
+        self.row = shape[-1]
+        n = 1
+        for s in shape:
+            n *= s
+        self.buf = torch.full((n + 2 * GUARD * self.row,), fill, dtype=dtype, device=DEV)
+        self.fill = fill
+        self.t = self.buf[GUARD * self.row:GUARD * self.row + n].view(shape)
+        if data is not None:
+            self.t.copy_(data.to(DEV).to(dtype))
+        elif inner is not None:
+            self.t.fill_(inner)
+
+    def assert_guards(self, what):
+        g = torch.cat([self.buf[:GUARD * self.row], self.buf[self.buf.numel() - GUARD * self.row:]])
+        ok = torch.isnan(g).all() if self.fill != self.fill else (g == self.fill).all()
+        assert ok, f"{what}: a store landed outside the operand"
+
+
+def gin(data, dtype=None):
+    """an input: guards that read as NaN (fp16 / f32) or as a poisoned accumulator (i64)"""
+    dtype = dtype or data.dtype
+    return Guarded(data.shape, dtype, POISON if dtype == torch.int64 else NAN, data=data)
+
+
+def gout(shape, dtype=torch.float16):
+    return Guarded(shape, dtype, SENTINEL, inner=SENTINEL)
+
+
+def fixed(S, Q):
+    return gin(to_fixed(S, Q))
+
+
+def run_case(c, inp):
+    """the launches of one case on guarded operands -> (y [F][HW][C] on the host, what to check afterwards)"""
+    x, gamma, beta = inp
+    e, F, HW, Cn, fps = c["entry"], c["F"], c["HW"], c["C"], c["fps"]
+    cpg = Cn // GROUPS
+    gx, gg, gb, gy = gin(x), gin(gamma), gin(beta), gout((F, HW, Cn))
+    held = [gx, gg, gb, gy]
+    kw = dict(F=F, HW=HW, frames_per_stat=fps, eps=EPS, silu=c["silu"])
+    if e == "groupnorm":
+        assert ROUTE_NAME.get(ops.groupnorm_route(F, HW, Cn, fps)) == c["route"], c["name"]
+        ws = Guarded((ops.groupnorm_ws_floats(F, HW, Cn),), torch.float32, 12345.0, inner=0.0)
+        held.append(ws)
+        ops.groupnorm(gx.t, gy.t, gg.t, gb.t, Cn=Cn, ws=ws.t, **kw)
+    elif e == "gstat":
+        gs = fixed(*stats_sums(x, fps, cpg))
+        held.append(gs)
+        ops.groupnorm_gstat(gx.t, gy.t, gg.t, gb.t, gs.t, Cn=Cn, **kw)
+    elif e == "colsum":
+        tile = HW // 5 if HW % 5 == 0 and HW > 5 else HW
+        xd = x.double().view(F * HW // tile, tile, Cn)
+        cs = gin(torch.stack([xd.sum(1), (xd * xd).sum(1)], -1).float())          # fp32 column sums [row tile][C][2]
+        ws = Guarded((ops.groupnorm_ws_floats(F, HW, Cn),), torch.float32, 12345.0, inner=0.0)
+        held += [cs, ws]
+        ops.groupnorm_colsum(gx.t, gy.t, gg.t, gb.t, cs.t, tile_rows=tile, Cn=Cn, ws=ws.t, **kw)
+    elif e == "cat":
+        C1, C2 = c["C1"], c["C2"]
+        ga, gbb = gin(x[:, :, :C1].contiguous()), gin(x[:, :, C1:].contiguous())
+        if c["mode"] == "none":
+            gcat, gsb = fixed(*stats_sums(x, fps, cpg)), None
+        else:
+            gcat = fixed(*stats_sums(x[:, :, :C1], fps, cpg))                    # a's share, in the concat's grouping
+            gsb = fixed(*stats_sums(x[:c["Fb"], :, C1:], fps, C2 // GROUPS))     # b's own statistics of its Fb frames
+            held.append(gsb)
+        held += [ga, gbb, gcat]
+        ops.groupnorm_gstat_cat(ga.t, gbb.t, gy.t, gg.t, gb.t, gcat.t, gsb.t if gsb else None, C1=C1, C2=C2, Fb=c["Fb"] if c["mode"] == "fb" else 0, **kw)
+    elif e == "concat":
+        C1, C2 = c["C1"], c["C2"]
+        ga, gbb, gcat_out = gin(x[:, :, :C1].contiguous()), gin(x[:, :, C1:].contiguous()), gout((F, HW, Cn))
+        gs = Guarded((F // fps, GROUPS, 2), torch.int64, POISON, inner=0)
+        held += [ga, gbb, gcat_out, gs]
+        ops.concat_channels_gstat(ga.t, gbb.t, gcat_out.t, gs.t, F=F, HW=HW, C1=C1, C2=C2, frames_per_stat=fps)
+        assert torch.equal(gcat_out.t.cpu(), x), f"{c['name']}: the concat is not its sources"
+        ops.groupnorm_gstat(gcat_out.t, gy.t, gg.t, gb.t, gs.t, Cn=Cn, **kw)
+    else:
+        Cs, gw, coff = c["Cn"], c["cpg"], c["coff"]
+        S, Q = torch.zeros(F // fps, GROUPS, dtype=torch.float64), torch.zeros(F // fps, GROUPS, dtype=torch.float64)
+        for lo, hi in ((0, coff), (coff + Cs, Cn)):                                # the rest of the tensor: its share is written here
+            if hi > lo:
+                s_, q_ = stats_sums(x[:, :, lo:hi], fps, gw, lo)
+                S, Q = S + s_, Q + q_
+        gsrc, gs = gin(x[:, :, coff:coff + Cs].contiguous()), fixed(S, Q)
+        held += [gsrc, gs]
+        ops.gstat_accum(gsrc.t, gs.t, F=F, HW=HW, Cn=Cs, frames_per_stat=fps, cpg=gw, coff=coff)
+        ops.groupnorm_gstat(gx.t, gy.t, gg.t, gb.t, gs.t, Cn=Cn, **kw)
+    torch.cuda.synchronize()
+    return gy.t.cpu(), held
+
+
+def accum_start(n_sg):
+    """accumulators [n_sg][32][2] that are not zero before a launch adds to them: sums of either sign, sums of squares >= 0"""
+    idx = torch.arange(n_sg * GROUPS, dtype=torch.int64).view(n_sg, GROUPS)
+    return torch.stack([idx * 7919 - 100000, idx * 104729 + 1], -1)
+
+
+def accumulate(c, x, start):
+    """the concat / accum launch of a case alone, on its input x ([F][HW][C1 + C2] / the source [F][HW][Cn]) and accumulators that hold
+    `start` -> (the accumulators, the concat's output or None, the guarded accumulators and output)"""
+    F, HW, fps = c["F"], c["HW"], c["fps"]
+    gs = gin(start)
+    if c["entry"] == "concat":
+        C1, C2 = c["C1"], c["C2"]
+        ga, gb, go = gin(x[:, :, :C1].contiguous()), gin(x[:, :, C1:].contiguous()), gout((F, HW, C1 + C2))
+        ops.concat_channels_gstat(ga.t, gb.t, go.t, gs.t, F=F, HW=HW, C1=C1, C2=C2, frames_per_stat=fps)
+    else:
+        gx, go = gin(x), None
+        ops.gstat_accum(gx.t, gs.t, F=F, HW=HW, Cn=c["Cn"], frames_per_stat=fps, cpg=c["cpg"], coff=c["coff"])
+    torch.cuda.synchronize()
+    return gs.t.cpu(), go.t.cpu() if go else None, [gs] + ([go] if go else [])
+
+
 # ----------------------------------------------------------------------------------------------------------------- fold weights
 def fold_weights(w, gamma, S, Q, count, eps, K):
     """moca_groupnorm_fold_weights_f16 in float64 on w [N][ldw] (fp16), statistics (S, Q) [n_sg][32]: wg as the kernel's fp32 product
@@ -512,6 +640,34 @@ def fold_bias(w, bias, beta, wg_stored, mean_k, K):
     bg = b + t1.sum(1)[None] - t2.sum(2)
     mag = (bias.double().abs()[None] if bias is not None else 0.0) + t1.abs().sum(1)[None] + t2.abs().sum(2)
     return bg, mag
+
+
+def fold_operands(K, bias):
+    """host operands of one moca_groupnorm_fold_weights_f16 case: N = 72 (four whole 16-row blocks and one of 8), ldw = K + 8 (zero pad
+    columns), n_sg = 3, the statistics as accumulators `acc`"""
+    N, ldw, n_sg, eps = 72, K + 8, 3, 1e-6
+    count = 640 * (K // GROUPS)
+    g = gen(500 + K + bias)
+    w = torch.zeros(N, ldw, dtype=torch.float16)
+    w[:, :K] = (torch.randn(N, K, generator=g) * K ** -0.5).half()
+    bi = torch.randn(N, generator=g) if bias else None
+    gamma, beta = 1.0 + 0.3 * torch.randn(K, generator=g), 0.3 * torch.randn(K, generator=g)
+    mean = 3.0 * torch.randn(n_sg, GROUPS, generator=g, dtype=torch.float64)
+    var = 0.25 + torch.rand(n_sg, GROUPS, generator=g, dtype=torch.float64) * 4
+    acc = to_fixed(mean * count, (var + mean * mean) * count)
+    return dict(K=K, N=N, ldw=ldw, n_sg=n_sg, eps=eps, count=count, w=w, bias=bi, gamma=gamma, beta=beta, acc=acc)
+
+
+def fold_run(o):
+    """the launch on guarded operands -> (wg [n_sg][N][ldw], bg [n_sg][N] on the host, the guarded operands)"""
+    N, ldw, n_sg = o["N"], o["ldw"], o["n_sg"]
+    gw, gbi, gg, gb, gs = gin(o["w"]), gin(o["bias"]) if o["bias"] is not None else None, gin(o["gamma"]), gin(o["beta"]), gin(o["acc"])
+    gwg, gbg = gout((n_sg * N, ldw)), gout((n_sg * N,), torch.float32)
+    rc = L.load().moca_groupnorm_fold_weights_f16(L.ptr(gw.t), L.ptr(gbi.t) if gbi else None, L.ptr(gg.t), L.ptr(gb.t), L.ptr(gs.t), L.ptr(gwg.t),
+                                                  L.ptr(gbg.t), n_sg, N, o["K"], ldw, o["count"], o["eps"], None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    return gwg.t.cpu().view(n_sg, N, ldw), gbg.t.cpu().view(n_sg, N), [gw, gg, gb, gs, gwg, gbg] + ([gbi] if gbi else [])
 
 
 # ----------------------------------------------------------------------------------------------------------------- census
@@ -554,4 +710,76 @@ def table_classes():
             out.add(("cat", c["C1"], c["C2"], "gstat_b", c["Fb"] < c["F"], c["fps"] > 1))
         if e == "cat" and c["mode"] == "none":
             out.add(("cat", c["C1"], c["C2"], None, False, c["fps"] > 1))
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------- the parent commit's bits
+# tests/test_norm_parent_gpu.py and tools/record_parent_fixtures.py --norm-sha: sha256 of what the launches leave, on host-generated
+# operands.  Outputs start as the sentinel and the accumulators of the concat / accum launches start non-zero, so an element that was
+# not written, or an accumulator that was overwritten instead of added to, changes the hash.
+FOLD_CASES = ((320, True), (320, False), (2560, True))
+BIG = (16, 65536, 64)           # 128 MiB of fp16 exactly: the smallest tensor that leaves with non-temporal stores
+PARENT_GROUPS = ("groupnorm", "gstat", "colsum", "cat", "concat", "accum", "fold", "big")
+
+
+def sha(*tensors):
+    import hashlib
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def parent_names(group):
+    if group == "fold":
+        return ["fold_%d_bias%d" % (K, b) for K, b in FOLD_CASES]
+    if group == "big":
+        return ["big_%dx%dx%d.%s" % (BIG + (k,)) for k in ("concat", "gstat", "cat")]
+    return [n + "." + k for n, c in CASES.items() if c["entry"] == group for k in ("plain", "spike")]
+
+
+def _big_hashes():
+    """the BIG shape through concat_channels_gstat, groupnorm_gstat and groupnorm_gstat_cat (a grid tensor: the concat's accumulators are
+    exact, whatever order its blocks arrive in)"""
+    F, HW, Cn = BIG
+    C1 = C2 = Cn // 2
+    g = gen(77)
+    x = (torch.randint(-32, 33, (F, HW, Cn), generator=g, dtype=torch.int8).to(torch.float16) / 8).to(DEV)
+    gamma, beta = (1.0 + 0.2 * torch.randn(Cn, generator=g)).to(DEV), (0.2 * torch.randn(Cn, generator=g)).to(DEV)
+    a, b = x[:, :, :C1].contiguous(), x[:, :, C1:].contiguous()
+    out = {}
+    o, gs = torch.full_like(x, SENTINEL), torch.zeros(F, GROUPS, 2, dtype=torch.int64, device=DEV)
+    ops.concat_channels_gstat(a, b, o, gs, F=F, HW=HW, C1=C1, C2=C2, frames_per_stat=1)
+    out["concat"] = sha(o, gs)
+    o.fill_(SENTINEL)
+    ops.groupnorm_gstat(x, o, gamma, beta, gs, F=F, HW=HW, Cn=Cn, frames_per_stat=1, eps=EPS, silu=True)
+    out["gstat"] = sha(o)
+    o.fill_(SENTINEL)
+    ops.groupnorm_gstat_cat(a, b, o, gamma, beta, gs, None, F=F, HW=HW, C1=C1, C2=C2, frames_per_stat=1, eps=EPS, silu=True)
+    out["cat"] = sha(o)
+    return {"big_%dx%dx%d.%s" % (BIG + (k,)): v for k, v in out.items()}
+
+
+def parent_hashes(group):
+    """{name: sha256} of the group's launches, in the order of parent_names(group)"""
+    if group == "big":
+        return _big_hashes()
+    if group == "fold":
+        return {"fold_%d_bias%d" % (K, b): sha(*fold_run(fold_operands(K, b))[:2]) for K, b in FOLD_CASES}
+    out = {}
+    for n, c in CASES.items():
+        if c["entry"] != group:
+            continue
+        old = L.set_tuning(L.MOCA_TUNE_GN_SLAB, c["knob"]) if group == "groupnorm" else None
+        try:
+            for kind, inp in (("plain", plain_input(c)), ("spike", spike_input(c, 0))):
+                left = [run_case(c, inp)[0]]
+                if group in ("concat", "accum"):
+                    x = inp[0] if group == "concat" else inp[0][:, :, c["coff"]:c["coff"] + c["Cn"]].contiguous()
+                    acc, o, _ = accumulate(c, x, accum_start(c["F"] // c["fps"]))
+                    left += [acc] + ([o] if o is not None else [])
+                out[f"{n}.{kind}"] = sha(*left)
+        finally:
+            if old is not None:
+                L.set_tuning(L.MOCA_TUNE_GN_SLAB, old)
     return out

@@ -16,10 +16,7 @@ import norm_edges_ref as R  # noqa: E402
 from moca_video_amd import lib as L  # noqa: E402
 from moca_video_amd import ops  # noqa: E402
 
-DEV = "cuda"
-GUARD = 4                       # guard rows in front of and behind every operand
-NAN = float("nan")
-POISON = 1 << 62                # an accumulator that reads as NaN (csrc/common.h)
+DEV = R.DEV
 
 
 @pytest.fixture(autouse=True)
@@ -47,100 +44,7 @@ def _report():
         print(f"[worst] {k}: worst (statistics group, channel group) block {R.WORST[k]:.2e} of its max|ref| (bound {R.TOL16:.1e})")
 
 
-# ---------------------------------------------------------------- operands inside guarded allocations
-class Guarded:
-    """a contiguous tensor of `shape` with GUARD rows of `fill` in front of it and behind it (a row = the last dimension)"""
-
-    def __init__(self, shape, dtype, fill, data=None, inner=None):
-        shape = tuple(shape)
-        self.row = shape[-1]
-        n = 1
-        for s in shape:
-            n *= s
-        self.buf = torch.full((n + 2 * GUARD * self.row,), fill, dtype=dtype, device=DEV)
-        self.fill = fill
-        self.t = self.buf[GUARD * self.row:GUARD * self.row + n].view(shape)
-        if data is not None:
-            self.t.copy_(data.to(DEV).to(dtype))
-        elif inner is not None:
-            self.t.fill_(inner)
-
-    def assert_guards(self, what):
-        g = torch.cat([self.buf[:GUARD * self.row], self.buf[self.buf.numel() - GUARD * self.row:]])
-        ok = torch.isnan(g).all() if self.fill != self.fill else (g == self.fill).all()
-        assert ok, f"{what}: a store landed outside the operand"
-
-
-def gin(data, dtype=None):
-    """an input: guards that read as NaN (fp16 / f32) or as a poisoned accumulator (i64)"""
-    dtype = dtype or data.dtype
-    return Guarded(data.shape, dtype, POISON if dtype == torch.int64 else NAN, data=data)
-
-
-def gout(shape, dtype=torch.float16):
-    return Guarded(shape, dtype, R.SENTINEL, inner=R.SENTINEL)
-
-
-def fixed(S, Q):
-    return gin(R.to_fixed(S, Q))
-
-
-def run_case(c, inp):
-    """the launches of one case on guarded operands -> (y [F][HW][C] on the host, what to check afterwards)"""
-    x, gamma, beta = inp
-    e, F, HW, Cn, fps = c["entry"], c["F"], c["HW"], c["C"], c["fps"]
-    cpg = Cn // R.GROUPS
-    gx, gg, gb, gy = gin(x), gin(gamma), gin(beta), gout((F, HW, Cn))
-    held = [gx, gg, gb, gy]
-    kw = dict(F=F, HW=HW, frames_per_stat=fps, eps=R.EPS, silu=c["silu"])
-    if e == "groupnorm":
-        assert R.ROUTE_NAME.get(ops.groupnorm_route(F, HW, Cn, fps)) == c["route"], c["name"]
-        ws = Guarded((ops.groupnorm_ws_floats(F, HW, Cn),), torch.float32, 12345.0, inner=0.0)
-        held.append(ws)
-        ops.groupnorm(gx.t, gy.t, gg.t, gb.t, Cn=Cn, ws=ws.t, **kw)
-    elif e == "gstat":
-        gs = fixed(*R.stats_sums(x, fps, cpg))
-        held.append(gs)
-        ops.groupnorm_gstat(gx.t, gy.t, gg.t, gb.t, gs.t, Cn=Cn, **kw)
-    elif e == "colsum":
-        tile = HW // 5 if HW % 5 == 0 and HW > 5 else HW
-        xd = x.double().view(F * HW // tile, tile, Cn)
-        cs = gin(torch.stack([xd.sum(1), (xd * xd).sum(1)], -1).float())          # fp32 column sums [row tile][C][2]
-        ws = Guarded((ops.groupnorm_ws_floats(F, HW, Cn),), torch.float32, 12345.0, inner=0.0)
-        held += [cs, ws]
-        ops.groupnorm_colsum(gx.t, gy.t, gg.t, gb.t, cs.t, tile_rows=tile, Cn=Cn, ws=ws.t, **kw)
-    elif e == "cat":
-        C1, C2 = c["C1"], c["C2"]
-        ga, gbb = gin(x[:, :, :C1].contiguous()), gin(x[:, :, C1:].contiguous())
-        if c["mode"] == "none":
-            gcat, gsb = fixed(*R.stats_sums(x, fps, cpg)), None
-        else:
-            gcat = fixed(*R.stats_sums(x[:, :, :C1], fps, cpg))                    # a's share, in the concat's grouping
-            gsb = fixed(*R.stats_sums(x[:c["Fb"], :, C1:], fps, C2 // R.GROUPS))   # b's own statistics of its Fb frames
-            held.append(gsb)
-        held += [ga, gbb, gcat]
-        ops.groupnorm_gstat_cat(ga.t, gbb.t, gy.t, gg.t, gb.t, gcat.t, gsb.t if gsb else None, C1=C1, C2=C2, Fb=c["Fb"] if c["mode"] == "fb" else 0, **kw)
-    elif e == "concat":
-        C1, C2 = c["C1"], c["C2"]
-        ga, gbb, gcat_out = gin(x[:, :, :C1].contiguous()), gin(x[:, :, C1:].contiguous()), gout((F, HW, Cn))
-        gs = Guarded((F // fps, R.GROUPS, 2), torch.int64, POISON, inner=0)
-        held += [ga, gbb, gcat_out, gs]
-        ops.concat_channels_gstat(ga.t, gbb.t, gcat_out.t, gs.t, F=F, HW=HW, C1=C1, C2=C2, frames_per_stat=fps)
-        assert torch.equal(gcat_out.t.cpu(), x), f"{c['name']}: the concat is not its sources"
-        ops.groupnorm_gstat(gcat_out.t, gy.t, gg.t, gb.t, gs.t, Cn=Cn, **kw)
-    else:
-        Cs, gw, coff = c["Cn"], c["cpg"], c["coff"]
-        S, Q = torch.zeros(F // fps, R.GROUPS, dtype=torch.float64), torch.zeros(F // fps, R.GROUPS, dtype=torch.float64)
-        for lo, hi in ((0, coff), (coff + Cs, Cn)):                                # the rest of the tensor: its share is written here
-            if hi > lo:
-                s_, q_ = R.stats_sums(x[:, :, lo:hi], fps, gw, lo)
-                S, Q = S + s_, Q + q_
-        gsrc, gs = gin(x[:, :, coff:coff + Cs].contiguous()), fixed(S, Q)
-        held += [gsrc, gs]
-        ops.gstat_accum(gsrc.t, gs.t, F=F, HW=HW, Cn=Cs, frames_per_stat=fps, cpg=gw, coff=coff)
-        ops.groupnorm_gstat(gx.t, gy.t, gg.t, gb.t, gs.t, Cn=Cn, **kw)
-    torch.cuda.synchronize()
-    return gy.t.cpu(), held
+run_case = R.run_case           # the launches of a case on guarded operands (shared with the parent-commit hashes: tests/norm_edges_ref.py)
 
 
 def case_group(c):
@@ -169,26 +73,18 @@ def test_accumulators_exact(name):
     c = R.CASES[name]
     assert R.grid_exact(c)
     F, HW, fps = c["F"], c["HW"], c["fps"]
-    n_sg = F // fps
-    idx = torch.arange(n_sg * R.GROUPS, dtype=torch.int64).view(n_sg, R.GROUPS)
-    start = torch.stack([idx * 7919 - 100000, idx * 104729 + 1], -1)            # sums of either sign, sums of squares >= 0
-    gs = gin(start)
+    start = R.accum_start(F // fps)
     if c["entry"] == "concat":
-        C1, C2 = c["C1"], c["C2"]
-        x = R.grid_input(F, HW, C1 + C2, R.seed_of(name))
-        ga, gb, go = gin(x[:, :, :C1].contiguous()), gin(x[:, :, C1:].contiguous()), gout((F, HW, C1 + C2))
-        ops.concat_channels_gstat(ga.t, gb.t, go.t, gs.t, F=F, HW=HW, C1=C1, C2=C2, frames_per_stat=fps)
-        want = start + R.to_fixed(*R.stats_sums(x, fps, (C1 + C2) // R.GROUPS))
-        assert torch.equal(go.t.cpu(), x), f"{name}: the concat is not bit-equal to its sources"
-        go.assert_guards(name)
+        x = R.grid_input(F, HW, c["C1"] + c["C2"], R.seed_of(name))
+        want = start + R.to_fixed(*R.stats_sums(x, fps, (c["C1"] + c["C2"]) // R.GROUPS))
     else:
         x = R.grid_input(F, HW, c["Cn"], R.seed_of(name))
-        gx = gin(x)
-        ops.gstat_accum(gx.t, gs.t, F=F, HW=HW, Cn=c["Cn"], frames_per_stat=fps, cpg=c["cpg"], coff=c["coff"])
         want = start + R.to_fixed(*R.stats_sums(x, fps, c["cpg"], c["coff"]))
-    torch.cuda.synchronize()
-    gs.assert_guards(name)
-    got = gs.t.cpu()
+    got, out, held = R.accumulate(c, x, start)
+    if c["entry"] == "concat":
+        assert torch.equal(out, x), f"{name}: the concat is not bit-equal to its sources"
+    for h in held:
+        h.assert_guards(name)
     assert torch.equal(got, want), f"{name}: {(got != want).sum().item()} accumulators differ from the integer sums, first {(got != want).nonzero()[:4].tolist()}"
 
 
@@ -266,33 +162,19 @@ def test_streaming_store_variants(F, HW, Cn, streams):
 
 
 # ---------------------------------------------------------------- 5: the fold of GroupNorm into per-group weights
-@pytest.mark.parametrize("K,bias", [(320, True), (320, False), (2560, True)])
+@pytest.mark.parametrize("K,bias", R.FOLD_CASES)
 def test_fold_weights_edges(K, bias):
     """N = 72 (four whole 16-row blocks and one of 8), ldw = K + 8 (zero pad columns come back zero), n_sg = 3, statistics written here.
     wg against the float64 product within one fp16 rounding plus the three fp32 roundings in front of it (rstd, rstd gamma, w s):
     2^-11 (1 + 2^-10) relative (+ 2^-25, half an fp16 subnormal step); bg within the fp32 summation bound K 2^-24 sum|terms| of its row,
     the mean term taken from the stored wg as the kernel takes it"""
-    N, ldw, n_sg, eps = 72, K + 8, 3, 1e-6
-    cpg = K // R.GROUPS
-    count = 640 * cpg
-    g = R.gen(500 + K + bias)
-    w = torch.zeros(N, ldw, dtype=torch.float16)
-    w[:, :K] = (torch.randn(N, K, generator=g) * K ** -0.5).half()
-    bi = torch.randn(N, generator=g) if bias else None
-    gamma, beta = 1.0 + 0.3 * torch.randn(K, generator=g), 0.3 * torch.randn(K, generator=g)
-    mean = 3.0 * torch.randn(n_sg, R.GROUPS, generator=g, dtype=torch.float64)
-    var = 0.25 + torch.rand(n_sg, R.GROUPS, generator=g, dtype=torch.float64) * 4
-    acc = R.to_fixed(mean * count, (var + mean * mean) * count)
-    S, Q = R.from_fixed(acc)
-    gw, gbi, gg, gb, gs = gin(w), gin(bi) if bias else None, gin(gamma), gin(beta), gin(acc)
-    gwg, gbg = gout((n_sg * N, ldw)), gout((n_sg * N,), torch.float32)
-    rc = L.load().moca_groupnorm_fold_weights_f16(L.ptr(gw.t), L.ptr(gbi.t) if bias else None, L.ptr(gg.t), L.ptr(gb.t), L.ptr(gs.t), L.ptr(gwg.t),
-                                                  L.ptr(gbg.t), n_sg, N, K, ldw, count, eps, None)
-    assert rc == 0
-    torch.cuda.synchronize()
-    for h in (gw, gg, gb, gs, gwg, gbg) + ((gbi,) if bias else ()):
+    o = R.fold_operands(K, bias)
+    w, bi, gamma, beta, count, eps = o["w"], o["bias"], o["gamma"], o["beta"], o["count"], o["eps"]
+    S, Q = R.from_fixed(o["acc"])
+    wg, bg, held = R.fold_run(o)
+    bg = bg.double()
+    for h in held:
         h.assert_guards(f"fold_weights K={K}")
-    wg, bg = gwg.t.cpu().view(n_sg, N, ldw), gbg.t.cpu().view(n_sg, N).double()
     assert (wg[:, :, K:] == 0).all(), "pad columns of wg are not zero"
     exact, mean_k = R.fold_weights(w, gamma, S, Q, count, eps, K)
     err = (wg[:, :, :K].double() - exact).abs()

@@ -13,6 +13,10 @@ optimisation or a compiler bump legitimately changes them:
   tests/golden/attention_parent_sha.npz          (--attention-sha, on the GPU)  sha256 of the outputs of every kernel of csrc/attention.hip
                                                  (and of moca_attention_d80_f16) on the cases and host-generated operands of
                                                  tests/attention_edges_ref.py::PARENT_CASES
+  tests/golden/norm_parent_sha.npz               (--norm-sha, on the GPU)  sha256 of what every launch of the GroupNorm family of csrc/norm.hip
+                                                 leaves on the cases and host-generated operands of
+                                                 tests/norm_edges_ref.py::parent_names (outputs, and the accumulators the concat /
+                                                 accum launches add to)
   tests/golden/sampler_routes.npz                (--samplers, no GPU)  the traces of tests/sampler_routes_cpu.py::record: the UNet entry
                                                  points and launches of the sampling layer (guidance routing, host-issued loops,
                                                  ddim_step, queue noising, the host-driven FIFO loop, `supported()` tables, the
@@ -23,10 +27,11 @@ optimisation or a compiler bump legitimately changes them:
     python tools/record_parent_fixtures.py --tree ../base --plans          (any host)
     python tools/record_parent_fixtures.py --tree ../base --sha            (on the MI355X)
     python tools/record_parent_fixtures.py --tree ../base --attention-sha  (on the MI355X)
+    python tools/record_parent_fixtures.py --tree ../base --norm-sha       (on the MI355X)
     python tools/record_parent_fixtures.py --tree ../base --samplers       (any host)
 
-The package is imported from --tree, the helpers (tests/plan_cpu.py, tests/temporal_variants_ref.py, tests/attention_edges_ref.py) and the output directory are this
-checkout's.  A tree older than the host-recordable plan (no `UNetModel._pack(dev)`, a stream created unconditionally) is recorded
+The package is imported from --tree, the helpers (tests/plan_cpu.py, tests/temporal_variants_ref.py, tests/attention_edges_ref.py,
+tests/norm_edges_ref.py) and the output directory are this checkout's.  A tree older than the host-recordable plan (no `UNetModel._pack(dev)`, a stream created unconditionally) is recorded
 through two stand-ins defined here; nothing of it is modified."""
 import argparse
 import os
@@ -110,6 +115,20 @@ def record_attention_sha():
     np.savez_compressed(os.path.join(GOLD, "attention_parent_sha.npz"), names=np.asarray(names), sha256=np.asarray(shas))
 
 
+def record_norm_sha():
+    import norm_edges_ref as R
+    names, shas = [], []
+    for group in R.PARENT_GROUPS:
+        got = R.parent_hashes(group)
+        torch.cuda.synchronize()
+        assert list(got) == R.parent_names(group)
+        for n, h in got.items():
+            names.append(n)
+            shas.append(h)
+            print(group, n, h)
+    np.savez_compressed(os.path.join(GOLD, "norm_parent_sha.npz"), names=np.asarray(names), sha256=np.asarray(shas))
+
+
 def record_samplers():
     import sampler_routes_cpu
     out = sampler_routes_cpu.record()
@@ -123,6 +142,7 @@ def main():
     ap.add_argument("--plans", action="store_true")
     ap.add_argument("--sha", action="store_true")
     ap.add_argument("--attention-sha", action="store_true")
+    ap.add_argument("--norm-sha", action="store_true")
     ap.add_argument("--samplers", action="store_true")
     a = ap.parse_args()
     tree = os.path.abspath(a.tree)
@@ -136,6 +156,8 @@ def main():
         record_sha()
     if a.attention_sha:
         record_attention_sha()
+    if a.norm_sha:
+        record_norm_sha()
     if a.samplers:
         record_samplers()
 
