@@ -1,6 +1,7 @@
 // Device helpers that more than one GEMM kernel family uses (gemm.hip, gemm_tiled.hip, gemm_persistent.hip): tile
-// constants and block remaps, the prefetch blocks, the stamps of the diagnostic build, the buffer-addressed A gather, the store loops
-// of the staged fp16 tile and the LayerNorm fold.  Everything here has internal linkage; the guard lets the diagnostic unity build
+// constants and block remaps (remap_block, xcd_range), the chunk swizzle of 64-byte LDS rows (swz64), the prefetch blocks, the stamps of
+// the diagnostic build, the buffer-addressed A gather, the store loops of the staged fp16 tile, the plain store from registers
+// (store8_rowadd_res) and the LayerNorm fold (lnfold_*).  Everything here has internal linkage; the guard lets the diagnostic unity build
 // (gemm_diag.hip) see it once.
 #ifndef MOCA_GEMM_DEVICE_H
 #define MOCA_GEMM_DEVICE_H
@@ -61,6 +62,14 @@ __device__ __forceinline__ bool prefetch_block(const moca_gemm_params& p, int nb
 }
 static inline int prefetch_blocks(const moca_gemm_params& p) { return (p.prefetch && p.prefetch_kib > 0) ? PREFETCH_BLOCKS : 0; }
 
+// 1-D XCD partition of a raster of ntiles tiles: XCD x (0..7) owns the contiguous range [start, start + count), the first ntiles % 8
+// XCDs one tile more than the others
+__device__ __forceinline__ void xcd_range(int ntiles, int x, int& start, int& count) {
+    const int q = ntiles >> 3, r = ntiles & 7;
+    start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
+    count = q + (x < r ? 1 : 0);
+}
+
 template <int BN>
 __device__ __forceinline__ void remap_block(int nblk, int& logical) {
     // XCD-aware bijective remap: physical blocks b, b+8, b+16, ... share an XCD (L2);
@@ -70,6 +79,11 @@ __device__ __forceinline__ void remap_block(int nblk, int& logical) {
     const int xcd = b & 7, j = b >> 3;
     logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
 }
+
+// 64-byte LDS rows (one 32-deep k-tile row = four 16-byte chunks): chunk swizzle phys = chunk ^ swz64(row), swz64 = f((row >> 2) & 3) with
+// f = {0, 2, 3, 1} -- conflict-free for the four 16-lane groups of ds_read_b128 on the 16x16x32 operand map (derivation in DESIGN.md).
+// The LDS image of a DMA is lane-linear, so the DMA applies it to the SOURCE chunk a lane fetches; the fragment reads to the address.
+__device__ __forceinline__ int swz64(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }
 
 #ifdef MOCA_STAMPS
 // diagnostic build only (-DMOCA_STAMPS): per-block s_memtime stamps, read back with moca_debug_stamps()
@@ -91,6 +105,13 @@ __device__ unsigned long long g_stamps[STAMP_BLOCKS * STAMP_SLOTS];
             g_stamps[blockIdx.x * STAMP_SLOTS + (k)] = t__;                                        \
         }                                                                                          \
     } while (0)
+// the main-loop segment stamps (MOCA_STAMP_W) of the staggered kernels: which wave stamps, in which loop iteration (-DSEG_WAVE= / -DSEG_ITER=)
+#ifndef SEG_WAVE
+#define SEG_WAVE 0
+#endif
+#ifndef SEG_ITER
+#define SEG_ITER 2
+#endif
 #define MOCA_STAMP_P(k, dep)                                                                       \
     do {                                                                                           \
         int dep__ = (dep);                                                                         \
@@ -255,6 +276,27 @@ __device__ __forceinline__ void st_out8(half_t* ptr, const half8v v, bool nt) {
     if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt" :: "v"(ptr), "v"(v) : "memory");
     else *reinterpret_cast<half8v*>(ptr) = v;
 #endif
+}
+
+// The plain epilogue of the kernels that store from registers (gemm_persistent.hip): o = eight consecutive columns `col` .. of row m as
+// fp32 tile values.  As the staged kernels: the tile value rounded to fp16 first, then + row add, + residual in fp32, one rounding out.
+__device__ __forceinline__ void store8_rowadd_res(const moca_gemm_params& p, int m, int col, float (&o)[8], const half_t* __restrict__ rowadd,
+                                                  const half_t* __restrict__ resid, bool nt_out) {
+    if (m >= p.M) return;
+    if (rowadd) {
+        const half8v e = *reinterpret_cast<const half8v*>(rowadd + (int64_t)(m / p.rowadd_div) * p.ld_rowadd + col);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) o[r] = (float)(half_t)o[r] + (float)e[r];
+    }
+    if (resid) {
+        const half8v e = *reinterpret_cast<const half8v*>(resid + (int64_t)m * p.ldr + col);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) o[r] = (rowadd ? o[r] : (float)(half_t)o[r]) + (float)e[r];
+    }
+    half8v h;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) h[r] = (half_t)o[r];
+    st_out8(reinterpret_cast<half_t*>(p.out) + (int64_t)m * p.ldo + col, h, nt_out);
 }
 
 // Residual rows of a launch whose output streams (>= 128 MiB: out_streams) are read with non-temporal loads: they are read once and,
@@ -587,18 +629,29 @@ __device__ __forceinline__ void store_fp16_tile_rowsum(const moca_gemm_params& p
 //      behind the DMAs) and keeps the raw values of the first two row partials in registers; lnfold_finish() (after the
 //      prologue DMAs are out) adds any further partials and turns the sums into (rstd, -mean * rstd).  Four registers are carried
 //      through the main loop; lnfold_publish() puts them into LDS behind the staged tile for the accumulator -> fp16 staging
-//      pass (rows past M repeat the last row; their stores are skipped anyway). ----
+//      pass (rows past M repeat the last row; their stores are skipped anyway).
+//      g4p / g4q (gemm_persistent.hip) run the same three steps per tile: `col` = n0 + their W-row permutation of tid,
+//      `fold` = false for a launch without the flag, which yields (1, 0, 0, bias), and a publish without the barrier (they have their own). ----
 struct LnFoldRegs { float rs, rb, ws, b; };
 struct LnFoldRaw { float2 p0, p1; float ws, b; };
-// (`row` = the global A row of this thread's tile row: m0 + tid, or the gathered row of the temporal-attention tiling)
+// the formula alone: sum and sum of squares of a row of K values -> (rstd, -mean * rstd)
+__device__ __forceinline__ float2 lnfold_stats(float s, float q, int K, float eps) {
+    const float inv_k = 1.0f / (float)K;
+    const float mean = s * inv_k;
+    const float var = fmaxf(q * inv_k - mean * mean, 0.f);
+    const float rs = rsqrtf(var + eps);
+    return float2{rs, -mean * rs};
+}
+// (`row` = the global A row of this thread's tile row: m0 + tid, or the gathered row of the temporal-attention tiling; `col` = the
+//  packed W row whose wsum / bias this thread < BN owns: n0 + tid)
 template <int TM, int BN>
-__device__ __forceinline__ LnFoldRaw lnfold_issue(const moca_gemm_params& p, int row, int n0, int tid) {
+__device__ __forceinline__ LnFoldRaw lnfold_issue(const moca_gemm_params& p, int row, int col, int tid, bool fold = true) {
     LnFoldRaw r = {float2{0.f, 0.f}, float2{0.f, 0.f}, 0.f, 0.f};
     if (tid < BN) {
-        r.ws = p.lnf_wsum[n0 + tid];
-        r.b = p.bias ? p.bias[n0 + tid] : 0.f;
+        if (fold) r.ws = p.lnf_wsum[col];
+        r.b = p.bias ? p.bias[col] : 0.f;
     }
-    if (tid < TM) {
+    if (fold && tid < TM) {
         const int m = min(row, p.M - 1);
         r.p0 = *reinterpret_cast<const float2*>(p.lnf_part + (int64_t)m * 2);
         if (p.lnf_nparts > 1) r.p1 = *reinterpret_cast<const float2*>(p.lnf_part + ((int64_t)p.M + m) * 2);
@@ -606,29 +659,27 @@ __device__ __forceinline__ LnFoldRaw lnfold_issue(const moca_gemm_params& p, int
     return r;
 }
 template <int TM, int BN>
-__device__ __forceinline__ LnFoldRegs lnfold_finish(const moca_gemm_params& p, const LnFoldRaw& raw, int row, int tid) {
-    LnFoldRegs r = {0.f, 0.f, raw.ws, raw.b};
-    if (tid < TM) {
+__device__ __forceinline__ LnFoldRegs lnfold_finish(const moca_gemm_params& p, const LnFoldRaw& raw, int row, int tid, bool fold = true) {
+    LnFoldRegs r = {fold ? 0.f : 1.f, 0.f, raw.ws, raw.b};
+    if (fold && tid < TM) {
         const int m = min(row, p.M - 1);
         float s = raw.p0.x + raw.p1.x, q = raw.p0.y + raw.p1.y;
         for (int i = 2; i < p.lnf_nparts; ++i) {
             const float2 v = *reinterpret_cast<const float2*>(p.lnf_part + ((int64_t)i * p.M + m) * 2);
             s += v.x; q += v.y;
         }
-        const float inv_k = 1.0f / (float)p.K;
-        const float mean = s * inv_k;
-        const float var = fmaxf(q * inv_k - mean * mean, 0.f);
-        r.rs = rsqrtf(var + p.ln_eps);
-        r.rb = -mean * r.rs;
+        const float2 st = lnfold_stats(s, q, p.K, p.ln_eps);
+        r.rs = st.x;
+        r.rb = st.y;
     }
     return r;
 }
 // lds: [TM] float2 (rstd, -mean * rstd), then [BN] wsum, then [BN] bias
-template <int TM, int BN>
+template <int TM, int BN, bool SYNC = true>
 __device__ __forceinline__ void lnfold_publish(const LnFoldRegs& r, float* lds, int tid) {
     if (tid < TM) *reinterpret_cast<float2*>(lds + 2 * tid) = float2{r.rs, r.rb};
     if (tid < BN) { lds[2 * TM + tid] = r.ws; lds[2 * TM + BN + tid] = r.b; }
-    __syncthreads();
+    if constexpr (SYNC) __syncthreads();
 }
 // step 2, per accumulator tile: v = rstd * acc + (-mean * rstd) * wsum + bias
 __device__ __forceinline__ f32x4 lnfold_apply(const f32x4 acc, const float2 st, const f32x4 ws, const f32x4 b) {

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w80h_kernel(const moca_gemm_param
     const unsigned a_voff = (unsigned)(((lane & 15) * p.C + (lane >> 4) * 8) * 2);
     // W piece (as w80s): lane -> row lane >> 2, physical chunk lane & 3; this wave's pieces wq, 4 + wq and (wq < 2) 8 + wq
     const int lrow = lane >> 2, pch = lane & 3;
-    const int lch = pch ^ ((0x78 >> (2 * ((lrow >> 2) & 3))) & 3);
+    const int lch = pch ^ swz64(lrow);
     unsigned w_off[3];
 #pragma unroll
     for (int g = 0; g < 3; ++g) w_off[g] = (unsigned)(((int64_t)(n0 + ((g < 2 ? g * 4 + wq : 8 + (wq & 1))) * 16 + lrow) * p.ldw + lch * 8) * 2);
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w80h_kernel(const moca_gemm_param
 
     // fragment addresses.  W as w80s.  A: per dx one register = the lane's pixel (fr + dx - 1 of block cb) in halo row 5 rg of slot 0;
     // (mt, dy) and the odd slot are immediates.  The block's pixel -1 / 16 is the neighbouring piece, or -- at the image's edge -- the gap.
-    const int swz = (fg ^ ((0x78 >> (2 * ((fr >> 2) & 3))) & 3)) << 4;
+    const int swz = (fg ^ swz64(fr)) << 4;
     const int b_off0 = WRING + (wave_n * WTN + fr) * RB + swz;
     int a_base[3], a_cur[3];
 #pragma unroll

@@ -1,8 +1,10 @@
 // The persistent GEMM kernels of the linears: a fixed grid (G4P_BLOCKS / SQP_BLOCKS, gemm_launch.h) walks the tiles, the DMA stream
 // never stops between tiles and the epilogue goes from registers to memory:
-//   gemm_g4p_kernel / gemm_g4q_kernel<GEGLU>  the persistent form of g4 (gemm_tiled.hip) on either MFMA shape
+//   gemm_g4p_kernel / gemm_g4q_kernel<GEGLU>  the persistent form of g4 (gemm_tiled.hip): ONE body (g4p_body), instantiated on either
+//                                             MFMA shape (G4pMma16 / G4pMma32: what a wave holds of the tile and where it goes)
 //   gemm_sqp_kernel<GEGLU>                     the persistent form of the 256 x 256 staggered kernel (gemm_tiled.hip)
-// Which calls they run: persistent_ok() / route_of() in gemm.hip.
+// Which calls they run: persistent_ok() / route_of() in gemm.hip.  What they share with each other and with the tiled kernels --
+// swz64, xcd_range, the LayerNorm-fold statistics (lnfold_*), the plain store store8_rowadd_res -- is in gemm_device.h.
 #include "gemm_launch.h"
 
 namespace {
@@ -23,6 +25,7 @@ namespace {
 //   * LayerNorm-fold statistics of a tile (row: rstd, -mean rstd; column: wsum, bias) are fetched at the tile's start and
 //     published in 3 KiB of LDS behind the ring.
 // Buffer-addressed DMA (SGPR descriptors, 32-bit per-lane offsets, out-of-range = zero fill) as in the staggered kernels.
+// "g4q" is the same kernel on v_mfma_f32_32x32x16_f16 (MOCA_TUNE_GEMM_MF32; slower in the A/B, profiles/r05_ab_g4p_mfma_shape.txt).
 // =====================================================================================
 // LDS row rho (0..127) of the W tile <- packed W row n0 + g4p_perm(rho): MFMA tile nt = (rho >> 4) & 3, column j = rho & 15 of wave
 // column wn = rho >> 6 holds output column  wn * 64 + (nt >> 1) * 32 + 8 (j >> 2) + 4 (nt & 1) + (j & 3)  of the tile
@@ -30,18 +33,157 @@ __device__ __forceinline__ int g4p_perm(int rho) {
     const int wn = rho >> 6, nt = (rho >> 4) & 3, j = rho & 15;
     return wn * 64 + (nt >> 1) * 32 + 8 * (j >> 2) + 4 * (nt & 1) + (j & 3);
 }
-__device__ __forceinline__ void st_out8_nt(half_t* ptr, const half8v v, bool nt) { st_out8(ptr, v, nt); }
-
-template <bool GEGLU>
-__global__ __launch_bounds__(256, 2) void gemm_g4p_kernel(const moca_gemm_params p) {
+// W-row permutation for the 32x32x16 operand map (g4q): LDS row rho -> tile nt = (rho >> 5) & 1 of wave column wn = rho >> 6, MFMA row i = rho & 31 =
+// 8 g + 4 h + r (g = accumulator register group, h = lane >> 5) holds column 16 (g >> 1) + 8 h + 4 (g & 1) + r of the tile's 32.
+__device__ __forceinline__ int g4q_perm(int rho) {
+    const int wn = rho >> 6, nt = (rho >> 5) & 1, i = rho & 31;
+    const int g = i >> 3, h = (i >> 2) & 1, r = i & 3;
+    return wn * 64 + nt * 32 + 16 * (g >> 1) + 8 * h + 4 * (g & 1) + r;
+}
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int TM = 256, BN = 128, KS = 32, RB = 64, MT = 8, NT = 4;
+// value tiles (lo, hi = columns 0..3, 4..7) and their gate tiles -> eight GEGLU outputs
+__device__ __forceinline__ half8v g4p_geglu8(const f32x4 vlo, const f32x4 vhi, const f32x4 glo, const f32x4 ghi) {
+    const f32x4 v[2] = {vlo, vhi}, g[2] = {glo, ghi};
+    half8v h;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const f32x2 lo = moca_geglu2(f32x2{v[i][0], v[i][1]}, f32x2{g[i][0], g[i][1]});
+        const f32x2 hi = moca_geglu2(f32x2{v[i][2], v[i][3]}, f32x2{g[i][2], g[i][3]});
+        h[4 * i + 0] = (half_t)lo[0]; h[4 * i + 1] = (half_t)lo[1]; h[4 * i + 2] = (half_t)hi[0]; h[4 * i + 3] = (half_t)hi[1];
+    }
+    return h;
+}
+// eight consecutive plain columns (lo, hi) of row m from `col`: + row add, + residual, store
+__device__ __forceinline__ void g4p_store8(const moca_gemm_params& p, int m, int col, const f32x4 lo, const f32x4 hi, const half_t* rowadd,
+                                           const half_t* resid, bool nt_out) {
+    float o[8];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { o[r] = lo[r]; o[4 + r] = hi[r]; }
+    store8_rowadd_res(p, m, col, o, rowadd, resid, nt_out);
+}
+
+// What a wave holds of the 256 x 128 tile (wave tile 128 x 64 = MT x NT MFMA tiles of ROWS rows, KF fragment k-steps per 32-deep k-tile)
+// and where it goes: the body below is written on these.  A lane's place in the operand map: fr = its row of an MFMA tile, fk = its
+// 16-byte k chunk within a k-step; lst / lws / lbi = the published statistics (lnfold_publish's layout).
+struct G4pLane { int fr, fk, wave_m, wave_n; const float *lst, *lws, *lbi; };
+
+// v_mfma_f32_16x16x32_f16: 8 x 4 tiles, one k-step per k-tile (32 MFMAs per phase)
+struct G4pMma16 {
+    static constexpr int MT = 8, NT = 4, ROWS = 16, KF = 1;
+    typedef f32x4 acc_t;
+    static __device__ __forceinline__ int perm(int rho) { return g4p_perm(rho); }
+    static __device__ __forceinline__ acc_t mfma(half8v b, half8v a, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(b, a, c, 0, 0, 0); }   // D^T: lane = row m
+    static __device__ __forceinline__ int dma_after(int j) { return (j % 5 == 2 && j / 5 < 6) ? j / 5 : -1; }      // DMA piece issued behind MFMA j
+    static __device__ __forceinline__ void read(const char* cur, const int (&fa_off)[MT][KF], const int (&fb_off)[NT][KF], half8v (&af)[MT][KF], half8v (&bf)[NT][KF]) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) af[mt][0] = *reinterpret_cast<const half8v*>(cur + fa_off[mt][0]);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bf[nt][0] = *reinterpret_cast<const half8v*>(cur + fb_off[nt][0]);
+    }
+    // lane = row m0 + wave_m * 128 + mt * 16 + fr, 8 consecutive columns per tile pair
+    template <bool GEGLU>
+    static __device__ __forceinline__ void epilogue(const moca_gemm_params& p, const acc_t (&acc)[MT][NT], const G4pLane& l, int m0, int n0,
+                                                    const half_t* rowadd, const half_t* resid, bool nt_out) {
+        const int fr = l.fr, fg = l.fk, wave_m = l.wave_m, wave_n = l.wave_n;
+        f32x4 cw[NT], cb[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            cw[nt] = *reinterpret_cast<const f32x4*>(l.lws + wave_n * 64 + nt * 16 + 4 * fg);
+            cb[nt] = *reinterpret_cast<const f32x4*>(l.lbi + wave_n * 64 + nt * 16 + 4 * fg);
+        }
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int rl = wave_m * 128 + mt * 16 + fr;
+            const int m = m0 + rl;
+            const float2 st = *reinterpret_cast<const float2*>(l.lst + 2 * rl);
+            f32x4 v[NT];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) v[nt] = lnfold_apply(acc[mt][nt], st, cw[nt], cb[nt]);
+            if constexpr (GEGLU) {
+                // value tiles 0, 1 and their gate tiles 2, 3 -> output columns on0 + wave_n * 32 + 8 fg + (0..7)
+                const half8v h = g4p_geglu8(v[0], v[1], v[2], v[3]);
+                if (m < p.M) st_out8(reinterpret_cast<half_t*>(p.out) + (int64_t)m * p.ldo + (n0 >> 1) + wave_n * 32 + 8 * fg, h, nt_out);
+            } else {
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh)
+                    g4p_store8(p, m, n0 + wave_n * 64 + hh * 32 + 8 * fg, v[2 * hh], v[2 * hh + 1], rowadd, resid, nt_out);
+            }
+        }
+    }
+};
+
+// v_mfma_f32_32x32x16_f16 ("g4q"): 4 x 2 tiles, two k-steps per k-tile (16 MFMAs per phase).  The kernel is bound by the SIMDs' issue
+// port (an MFMA of either shape holds it for 8 cycles): half as many MFMA instructions for the same matrix cycles, the same fragment bytes.
+struct G4pMma32 {
+    static constexpr int MT = 4, NT = 2, ROWS = 32, KF = 2;
+    typedef f32x16 acc_t;
+    static __device__ __forceinline__ int perm(int rho) { return g4q_perm(rho); }
+    static __device__ __forceinline__ acc_t mfma(half8v b, half8v a, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, c, 0, 0, 0); }   // D^T: lane & 31 = row m
+    static __device__ __forceinline__ int dma_after(int j) { return ((j & 1) && j / 2 < 6) ? j / 2 : -1; }
+    static __device__ __forceinline__ void read(const char* cur, const int (&fa_off)[MT][KF], const int (&fb_off)[NT][KF], half8v (&af)[MT][KF], half8v (&bf)[NT][KF]) {
+#pragma unroll
+        for (int ks = 0; ks < KF; ++ks) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) bf[nt][ks] = *reinterpret_cast<const half8v*>(cur + fb_off[nt][ks]);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) af[mt][ks] = *reinterpret_cast<const half8v*>(cur + fa_off[mt][ks]);
+        }
+    }
+    // lane = row m0 + wave_m * 128 + mt * 32 + (lane & 31); accumulator registers 4 g + r of a tile are (permuted W rows) columns
+    // 16 (g >> 1) + 8 (lane >> 5) + 4 (g & 1) + r of the tile's 32
+    // (the 16 column constants of a lane stay in registers for the GEGLU form; the plain form, which also holds row add / residual
+    //  operands, re-reads them from LDS per use)
+    template <bool GEGLU>
+    static __device__ __forceinline__ void epilogue(const moca_gemm_params& p, const acc_t (&acc)[MT][NT], const G4pLane& l, int m0, int n0,
+                                                    const half_t* rowadd, const half_t* resid, bool nt_out) {
+        const int fr = l.fr, fh = l.fk, wave_m = l.wave_m, wave_n = l.wave_n;
+        f32x4 cw[NT][4], cb[NT][4];
+        auto constants = [&](int nt, int g) {
+            cw[nt][g] = *reinterpret_cast<const f32x4*>(l.lws + wave_n * 64 + nt * 32 + 8 * g + 4 * fh);
+            cb[nt][g] = *reinterpret_cast<const f32x4*>(l.lbi + wave_n * 64 + nt * 32 + 8 * g + 4 * fh);
+        };
+        if constexpr (GEGLU) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) constants(nt, g);
+        }
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int rl = wave_m * 128 + mt * 32 + fr;
+            const int m = m0 + rl;
+            const float2 st = *reinterpret_cast<const float2*>(l.lst + 2 * rl);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {                        // store s: registers g = 2 s, 2 s + 1 -> 8 consecutive columns 16 s + 8 fh
+                f32x4 v[NT][2];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int gg = 0; gg < 2; ++gg) {
+                        const int g = 2 * s + gg;
+                        const f32x4 a4 = {acc[mt][nt][4 * g], acc[mt][nt][4 * g + 1], acc[mt][nt][4 * g + 2], acc[mt][nt][4 * g + 3]};
+                        if constexpr (!GEGLU) constants(nt, g);
+                        v[nt][gg] = lnfold_apply(a4, st, cw[nt][g], cb[nt][g]);
+                    }
+                if constexpr (GEGLU) {                           // value tile 0, gate tile 1
+                    const half8v h = g4p_geglu8(v[0][0], v[0][1], v[1][0], v[1][1]);
+                    if (m < p.M) st_out8(reinterpret_cast<half_t*>(p.out) + (int64_t)m * p.ldo + (n0 >> 1) + wave_n * 32 + 16 * s + 8 * fh, h, nt_out);
+                } else {
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        g4p_store8(p, m, n0 + wave_n * 64 + nt * 32 + 16 * s + 8 * fh, v[nt][0], v[nt][1], rowadd, resid, nt_out);
+                }
+            }
+        }
+    }
+};
+
+template <bool GEGLU, typename MMA>
+__device__ __forceinline__ void g4p_body(const moca_gemm_params& p) {
+    constexpr int TM = 256, BN = 128, KS = 32, RB = 64, MT = MMA::MT, NT = MMA::NT, KF = MMA::KF;
     constexpr int A_BYTES = TM * RB, STAGE = A_BYTES + BN * RB, RING = 3 * STAGE;     // 24 KiB per k-tile, 72 KiB ring
-    constexpr int NMMA = MT * NT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* lst = reinterpret_cast<float*>(smem + RING);          // [TM] float2 (rstd, -mean rstd), [BN] wsum, [BN] bias  (MFMA column order)
-    float* lws = lst + 2 * TM;
-    float* lbi = lws + BN;
+    float* lst = reinterpret_cast<float*>(smem + RING);          // lnfold_publish's layout: [TM] float2 (rstd, -mean rstd), [BN] wsum, [BN] bias  (MFMA column order)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -50,29 +192,24 @@ __global__ __launch_bounds__(256, 2) void gemm_g4p_kernel(const moca_gemm_params
     if (prefetch_block(p, nper, 256)) return;
 
     const int tiles_n = p.N / BN;
-    const int ntiles = ((p.M + TM - 1) / TM) * tiles_n;
     // tiles of this block: XCD x = b & 7 owns a contiguous range of the raster, its J = nper / 8 blocks walk it with stride J
     int t_cur, t_end;
     const int J = nper >> 3;
-    {
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        t_cur = start + j;
-        t_end = start + q + (x < r ? 1 : 0);
-    }
+    xcd_range(((p.M + TM - 1) / TM) * tiles_n, blockIdx.x & 7, t_cur, t_end);
+    t_end += t_cur;
+    t_cur += blockIdx.x >> 3;
     if (t_cur >= t_end) return;                                  // (block-uniform)
     const int nk = 2 * (p.K / 64);                               // K % 64 == 0 (host-checked)
 
     // ---- DMA addressing: piece = 16 rows x 64 B, lane -> row lane >> 2, physical chunk lane & 3 ----
     const int lrow = lane >> 2, pch = lane & 3;
-    const int lch = pch ^ ((0x78 >> (2 * ((lrow >> 2) & 3))) & 3);
+    const int lch = pch ^ swz64(lrow);
     const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.a), 0, OOB_OFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, OOB_OFF, 0x00020000);
     unsigned a_off[4], w_off[2];
     int w_perm[2];
 #pragma unroll
-    for (int g = 0; g < 2; ++g) w_perm[g] = g4p_perm((g * 4 + wave) * 16 + lrow);
+    for (int g = 0; g < 2; ++g) w_perm[g] = MMA::perm((g * 4 + wave) * 16 + lrow);
     auto set_dma_tile = [&](int t) {                             // t < 0: no tile (every lane out of range: zero fill, no traffic)
         const int tm = t / tiles_n, tn = t - tm * tiles_n;
 #pragma unroll
@@ -91,44 +228,44 @@ __global__ __launch_bounds__(256, 2) void gemm_g4p_kernel(const moca_gemm_params
         else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, sa + A_BYTES + ((j - 4) * 4 + wave) * 1024, 16, w_off[j - 4], soff, 0, 0);
     };
 
-    const int fr = lane & 15, fg = lane >> 4;
-    int fa_off[MT], fb_off[NT];
+    // ---- fragments: operand row lane % ROWS of an MFMA tile, 16-byte chunk (4 / KF) ks + lane / ROWS of the k-tile's four ----
+    const G4pLane l = {lane & (MMA::ROWS - 1), lane / MMA::ROWS, wave_m, wave_n, lst, lst + 2 * TM, lst + 2 * TM + BN};
+    int fa_off[MT][KF], fb_off[NT][KF];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const int row = wave_m * 128 + mt * 16 + fr;
-        fa_off[mt] = row * RB + ((fg ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3)) << 4);
-    }
+    for (int ks = 0; ks < KF; ++ks) {
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int row = wave_n * 64 + nt * 16 + fr;
-        fb_off[nt] = A_BYTES + row * RB + ((fg ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3)) << 4);
+        for (int mt = 0; mt < MT; ++mt) {
+            const int row = wave_m * 128 + mt * MMA::ROWS + l.fr;
+            fa_off[mt][ks] = row * RB + ((((4 / KF) * ks + l.fk) ^ swz64(row)) << 4);
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int row = wave_n * 64 + nt * MMA::ROWS + l.fr;
+            fb_off[nt][ks] = A_BYTES + row * RB + ((((4 / KF) * ks + l.fk) ^ swz64(row)) << 4);
+        }
     }
 
-    f32x4 acc[MT][NT];
-    half8v af[MT], bf[NT];
+    typename MMA::acc_t acc[MT][NT];
+    half8v af[MT][KF], bf[NT][KF];
     int s0 = 0, s1 = 1, s2 = 2;                                  // ring slots of k-tiles i, i+1, i+2 of the running stream
-    // one phase = one k-tile: fragments -> registers, 32 MFMAs; EVEN phases issue the pair (kt2, kt2 + 1) of the DMA tile: kt2 into the
+    // one phase = one k-tile: fragments -> registers, its MFMAs; EVEN phases issue the pair (kt2, kt2 + 1) of the DMA tile: kt2 into the
     // slot of k-tile i - 1, kt2 + 1 into k-tile i's own slot (hence the barrier behind the fragment reads)
     auto phase = [&](auto even_tag, int kt2) {
         constexpr bool even = decltype(even_tag)::value;
-        const char* cur = smem + s0 * STAGE;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) af[mt] = *reinterpret_cast<const half8v*>(cur + fa_off[mt]);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bf[nt] = *reinterpret_cast<const half8v*>(cur + fb_off[nt]);
+        MMA::read(smem + s0 * STAGE, fa_off, fb_off, af, bf);
         if constexpr (even) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int j = 0; j < NMMA; ++j) {
-            const int mt = j / NT, nt = j % NT;
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[nt], af[mt], acc[mt][nt], 0, 0, 0);   // D^T: lane = row m
+        for (int j = 0; j < KF * MT * NT; ++j) {
+            const int ks = j / (MT * NT), mt = (j / NT) % MT, nt = j % NT;
+            acc[mt][nt] = MMA::mfma(bf[nt][ks], af[mt][ks], acc[mt][nt]);
             if constexpr (even) {
-                if (j % 5 == 2 && j / 5 < 6) {
-                    dma_piece(kt2, s2, j / 5);
-                    dma_piece(kt2 + 1, s0, j / 5);
+                if (MMA::dma_after(j) >= 0) {
+                    dma_piece(kt2, s2, MMA::dma_after(j));
+                    dma_piece(kt2 + 1, s0, MMA::dma_after(j));
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -139,40 +276,10 @@ __global__ __launch_bounds__(256, 2) void gemm_g4p_kernel(const moca_gemm_params
 
     // statistics of tile t: raw values -> registers (issued early), finished and published behind the tile's main loop
     const bool fold = (p.flags & MOCA_EP_LNFOLD) != 0;
-    float2 rp0, rp1;
-    float rws, rbi;
+    LnFoldRaw raw;
     auto stat_issue = [&](int t) {
         const int tm = t / tiles_n, tn = t - tm * tiles_n;
-        rp0 = float2{0.f, 0.f}; rp1 = float2{0.f, 0.f}; rws = 0.f; rbi = 0.f;
-        if (tid < BN) {
-            const int n = tn * BN + g4p_perm(tid);
-            if (fold) rws = p.lnf_wsum[n];
-            if (p.bias) rbi = p.bias[n];
-        }
-        if (fold) {
-            const int m = min(tm * TM + tid, p.M - 1);
-            rp0 = *reinterpret_cast<const float2*>(p.lnf_part + (int64_t)m * 2);
-            if (p.lnf_nparts > 1) rp1 = *reinterpret_cast<const float2*>(p.lnf_part + ((int64_t)p.M + m) * 2);
-        }
-    };
-    auto stat_publish = [&](int t) {
-        float rs = 1.f, rb = 0.f;
-        if (fold) {
-            const int tm = t / tiles_n;
-            const int m = min(tm * TM + tid, p.M - 1);
-            float s = rp0.x + rp1.x, q = rp0.y + rp1.y;
-            for (int i = 2; i < p.lnf_nparts; ++i) {
-                const float2 v = *reinterpret_cast<const float2*>(p.lnf_part + ((int64_t)i * p.M + m) * 2);
-                s += v.x; q += v.y;
-            }
-            const float inv_k = 1.0f / (float)p.K;
-            const float mean = s * inv_k;
-            const float var = fmaxf(q * inv_k - mean * mean, 0.f);
-            rs = rsqrtf(var + p.ln_eps);
-            rb = -mean * rs;
-        }
-        *reinterpret_cast<float2*>(lst + 2 * tid) = float2{rs, rb};
-        if (tid < BN) { lws[tid] = rws; lbi[tid] = rbi; }
+        raw = lnfold_issue<TM, BN>(p, tm * TM + tid, tn * BN + MMA::perm(tid), tid, fold);
     };
 
     // ---- prologue: first pair of the first tile ----
@@ -186,8 +293,9 @@ __global__ __launch_bounds__(256, 2) void gemm_g4p_kernel(const moca_gemm_params
     const bool nt_out = out_streams(p);
     const half_t* __restrict__ resid = reinterpret_cast<const half_t*>(p.residual);
     const half_t* __restrict__ rowadd = reinterpret_cast<const half_t*>(p.rowadd);
+#ifdef MOCA_STAMPS
     int tile_no = 0;
-    (void)tile_no;
+#endif
     while (true) {
         const int t_next = t_cur + J < t_end ? t_cur + J : -1;
         const int tm = t_cur / tiles_n, tn = t_cur - tm * tiles_n;
@@ -201,7 +309,7 @@ __global__ __launch_bounds__(256, 2) void gemm_g4p_kernel(const moca_gemm_params
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = typename MMA::acc_t(0.f);
         for (int i = 0; i < nk; i += 2) {
             const bool last = i + 2 >= nk;
             if (last) set_dma_tile(t_next);                      // the stream moves on to the next tile's first pair
@@ -217,65 +325,14 @@ __global__ __launch_bounds__(256, 2) void gemm_g4p_kernel(const moca_gemm_params
 #ifdef MOCA_STAMPS
         if (stamp_it) MOCA_STAMP(3);
 #endif
-        stat_publish(t_cur);
+        lnfold_publish<TM, BN, false>(lnfold_finish<TM, BN>(p, raw, m0 + tid, tid, fold), lst, tid);
         if (t_next >= 0) stat_issue(t_next);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
 #ifdef MOCA_STAMPS
         if (stamp_it) MOCA_STAMP(4);
 #endif
-
-        // ---- epilogue from registers: lane = row m0 + wave_m * 128 + mt * 16 + fr, 8 consecutive columns per tile pair ----
-        f32x4 cw[NT], cb[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            cw[nt] = *reinterpret_cast<const f32x4*>(lws + wave_n * 64 + nt * 16 + 4 * fg);
-            cb[nt] = *reinterpret_cast<const f32x4*>(lbi + wave_n * 64 + nt * 16 + 4 * fg);
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int rl = wave_m * 128 + mt * 16 + fr;
-            const int m = m0 + rl;
-            const float2 st = *reinterpret_cast<const float2*>(lst + 2 * rl);
-            f32x4 v[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) v[nt] = st.x * acc[mt][nt] + (st.y * cw[nt] + cb[nt]);
-            if constexpr (GEGLU) {
-                // value tiles 0, 1 and their gate tiles 2, 3 -> output columns on0 + wave_n * 32 + 8 fg + (0..7)
-                half8v h;
-#pragma unroll
-                for (int nv = 0; nv < 2; ++nv) {
-                    const f32x2 lo = moca_geglu2(f32x2{v[nv][0], v[nv][1]}, f32x2{v[nv + 2][0], v[nv + 2][1]});
-                    const f32x2 hi = moca_geglu2(f32x2{v[nv][2], v[nv][3]}, f32x2{v[nv + 2][2], v[nv + 2][3]});
-                    h[4 * nv + 0] = (half_t)lo[0]; h[4 * nv + 1] = (half_t)lo[1]; h[4 * nv + 2] = (half_t)hi[0]; h[4 * nv + 3] = (half_t)hi[1];
-                }
-                if (m < p.M) st_out8(reinterpret_cast<half_t*>(p.out) + (int64_t)m * p.ldo + (n0 >> 1) + wave_n * 32 + 8 * fg, h, nt_out);
-            } else {
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    const int col = n0 + wave_n * 64 + hh * 32 + 8 * fg;
-                    float o[8];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { o[r] = v[2 * hh][r]; o[4 + r] = v[2 * hh + 1][r]; }
-                    if (m < p.M) {
-                        if (rowadd) {
-                            const half8v e = *reinterpret_cast<const half8v*>(rowadd + (int64_t)(m / p.rowadd_div) * p.ld_rowadd + col);
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) o[r] = (float)(half_t)o[r] + (float)e[r];   // (as the staged kernels: fp16 tile, then + row add, + residual in fp32)
-                        }
-                        if (resid) {
-                            const half8v e = *reinterpret_cast<const half8v*>(resid + (int64_t)m * p.ldr + col);
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) o[r] = (rowadd ? o[r] : (float)(half_t)o[r]) + (float)e[r];
-                        }
-                        half8v h;
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) h[r] = (half_t)o[r];
-                        st_out8(reinterpret_cast<half_t*>(p.out) + (int64_t)m * p.ldo + col, h, nt_out);
-                    }
-                }
-            }
-        }
+        MMA::template epilogue<GEGLU>(p, acc, l, m0, n0, rowadd, resid, nt_out);      // from registers
 #ifdef MOCA_STAMPS
         if (stamp_it) { MOCA_STAMP(5); MOCA_STAMP_HW(); }
         ++tile_no;
@@ -285,279 +342,19 @@ __global__ __launch_bounds__(256, 2) void gemm_g4p_kernel(const moca_gemm_params
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");           // the next tile's first pair has landed (and the stores have left)
         __builtin_amdgcn_s_barrier();
     }
-#endif
 }
+#endif
 
-// "g4q": g4p on v_mfma_f32_32x32x16_f16 (wave tile 128 x 64 = 4 x 2 tiles).  The kernel is bound by the SIMDs' issue port (an MFMA of
-// either shape holds it for 8 cycles): half as many MFMA instructions for the same matrix cycles, the same fragment bytes.
-// W-row permutation for this operand map: LDS row rho -> tile nt = (rho >> 5) & 1 of wave column wn = rho >> 6, MFMA row i = rho & 31 =
-// 8 g + 4 h + r (g = accumulator register group, h = lane >> 5) holds column 16 (g >> 1) + 8 h + 4 (g & 1) + r of the tile's 32.
-__device__ __forceinline__ int g4q_perm(int rho) {
-    const int wn = rho >> 6, nt = (rho >> 5) & 1, i = rho & 31;
-    const int g = i >> 3, h = (i >> 2) & 1, r = i & 3;
-    return wn * 64 + nt * 32 + 16 * (g >> 1) + 8 * h + 4 * (g & 1) + r;
+template <bool GEGLU>
+__global__ __launch_bounds__(256, 2) void gemm_g4p_kernel(const moca_gemm_params p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    g4p_body<GEGLU, G4pMma16>(p);
+#endif
 }
 template <bool GEGLU>
 __global__ __launch_bounds__(256, 2) void gemm_g4q_kernel(const moca_gemm_params p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int TM = 256, BN = 128, KS = 32, RB = 64, MT = 4, NT = 2;      // 32 x 32 MFMA tiles per wave (128 x 64)
-    constexpr int A_BYTES = TM * RB, STAGE = A_BYTES + BN * RB, RING = 3 * STAGE;     // 24 KiB per k-tile, 72 KiB ring
-        extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* lst = reinterpret_cast<float*>(smem + RING);          // [TM] float2 (rstd, -mean rstd), [BN] wsum, [BN] bias  (MFMA column order)
-    float* lws = lst + 2 * TM;
-    float* lbi = lws + BN;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wave_m = wave >> 1, wave_n = wave & 1;
-    const int nper = p.reserved2_;                               // persistent blocks (multiple of 8); the rest of the grid prefetches
-    if (prefetch_block(p, nper, 256)) return;
-
-    const int tiles_n = p.N / BN;
-    const int ntiles = ((p.M + TM - 1) / TM) * tiles_n;
-    // tiles of this block: XCD x = b & 7 owns a contiguous range of the raster, its J = nper / 8 blocks walk it with stride J
-    int t_cur, t_end;
-    const int J = nper >> 3;
-    {
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3;
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int start = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-        t_cur = start + j;
-        t_end = start + q + (x < r ? 1 : 0);
-    }
-    if (t_cur >= t_end) return;                                  // (block-uniform)
-    const int nk = 2 * (p.K / 64);                               // K % 64 == 0 (host-checked)
-
-    // ---- DMA addressing: piece = 16 rows x 64 B, lane -> row lane >> 2, physical chunk lane & 3 ----
-    const int lrow = lane >> 2, pch = lane & 3;
-    const int lch = pch ^ ((0x78 >> (2 * ((lrow >> 2) & 3))) & 3);
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.a), 0, OOB_OFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, OOB_OFF, 0x00020000);
-    unsigned a_off[4], w_off[2];
-    int w_perm[2];
-#pragma unroll
-    for (int g = 0; g < 2; ++g) w_perm[g] = g4q_perm((g * 4 + wave) * 16 + lrow);
-    auto set_dma_tile = [&](int t) {                             // t < 0: no tile (every lane out of range: zero fill, no traffic)
-        const int tm = t / tiles_n, tn = t - tm * tiles_n;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int row = tm * TM + (g * 4 + wave) * 16 + lrow;
-            a_off[g] = (t >= 0 && row < p.M) ? (unsigned)(((int64_t)row * p.lda + lch * 8) * 2) : OOB_OFF;
-        }
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-            w_off[g] = t >= 0 ? (unsigned)(((int64_t)(tn * BN + w_perm[g]) * p.ldw + lch * 8) * 2) : OOB_OFF;
-    };
-    auto dma_piece = [&](int kt, int slot, int j) {              // piece j (0..3: A, 4..5: W) of k-tile kt of the DMA tile
-        const lds_ptr sa = (lds_ptr)smem + slot * STAGE;
-        const unsigned soff = (unsigned)(kt * KS * 2);
-        if (j < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, sa + (j * 4 + wave) * 1024, 16, a_off[j], soff, 0, 0);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, sa + A_BYTES + ((j - 4) * 4 + wave) * 1024, 16, w_off[j - 4], soff, 0, 0);
-    };
-
-    const int fr = lane & 31, fh = lane >> 5;                    // 32x32x16 operand map: row lane & 31, k = 8 (lane >> 5) .. + 7
-    int fa_off[MT][2], fb_off[NT][2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int row = wave_m * 128 + mt * 32 + fr;
-            fa_off[mt][ks] = row * RB + (((2 * ks + fh) ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3)) << 4);
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int row = wave_n * 64 + nt * 32 + fr;
-            fb_off[nt][ks] = A_BYTES + row * RB + (((2 * ks + fh) ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3)) << 4);
-        }
-    }
-
-    f32x16 acc[MT][NT];
-    half8v af[MT][2], bf[NT][2];
-    int s0 = 0, s1 = 1, s2 = 2;                                  // ring slots of k-tiles i, i+1, i+2 of the running stream
-    // one phase = one k-tile: fragments -> registers, 32 MFMAs; EVEN phases issue the pair (kt2, kt2 + 1) of the DMA tile: kt2 into the
-    // slot of k-tile i - 1, kt2 + 1 into k-tile i's own slot (hence the barrier behind the fragment reads)
-    auto phase = [&](auto even_tag, int kt2) {
-        constexpr bool even = decltype(even_tag)::value;
-        const char* cur = smem + s0 * STAGE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bf[nt][ks] = *reinterpret_cast<const half8v*>(cur + fb_off[nt][ks]);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) af[mt][ks] = *reinterpret_cast<const half8v*>(cur + fa_off[mt][ks]);
-        }
-        if constexpr (even) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int j = 0; j < 2 * MT * NT; ++j) {
-            const int ks = j / (MT * NT), mt = (j / NT) % MT, nt = j % NT;
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[nt][ks], af[mt][ks], acc[mt][nt], 0, 0, 0);   // D^T: lane & 31 = row m
-            if constexpr (even) {
-                if ((j & 1) && j / 2 < 6) {
-                    dma_piece(kt2, s2, j / 2);
-                    dma_piece(kt2 + 1, s0, j / 2);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        { const int t = s0; s0 = s1; s1 = s2; s2 = t; }
-    };
-
-    // statistics of tile t: raw values -> registers (issued early), finished and published behind the tile's main loop
-    const bool fold = (p.flags & MOCA_EP_LNFOLD) != 0;
-    float2 rp0, rp1;
-    float rws, rbi;
-    auto stat_issue = [&](int t) {
-        const int tm = t / tiles_n, tn = t - tm * tiles_n;
-        rp0 = float2{0.f, 0.f}; rp1 = float2{0.f, 0.f}; rws = 0.f; rbi = 0.f;
-        if (tid < BN) {
-            const int n = tn * BN + g4q_perm(tid);
-            if (fold) rws = p.lnf_wsum[n];
-            if (p.bias) rbi = p.bias[n];
-        }
-        if (fold) {
-            const int m = min(tm * TM + tid, p.M - 1);
-            rp0 = *reinterpret_cast<const float2*>(p.lnf_part + (int64_t)m * 2);
-            if (p.lnf_nparts > 1) rp1 = *reinterpret_cast<const float2*>(p.lnf_part + ((int64_t)p.M + m) * 2);
-        }
-    };
-    auto stat_publish = [&](int t) {
-        float rs = 1.f, rb = 0.f;
-        if (fold) {
-            const int tm = t / tiles_n;
-            const int m = min(tm * TM + tid, p.M - 1);
-            float s = rp0.x + rp1.x, q = rp0.y + rp1.y;
-            for (int i = 2; i < p.lnf_nparts; ++i) {
-                const float2 v = *reinterpret_cast<const float2*>(p.lnf_part + ((int64_t)i * p.M + m) * 2);
-                s += v.x; q += v.y;
-            }
-            const float inv_k = 1.0f / (float)p.K;
-            const float mean = s * inv_k;
-            const float var = fmaxf(q * inv_k - mean * mean, 0.f);
-            rs = rsqrtf(var + p.ln_eps);
-            rb = -mean * rs;
-        }
-        *reinterpret_cast<float2*>(lst + 2 * tid) = float2{rs, rb};
-        if (tid < BN) { lws[tid] = rws; lbi[tid] = rbi; }
-    };
-
-    // ---- prologue: first pair of the first tile ----
-    stat_issue(t_cur);
-    set_dma_tile(t_cur);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) { dma_piece(0, 0, j); dma_piece(1, 1, j); }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    const bool nt_out = out_streams(p);
-    const half_t* __restrict__ resid = reinterpret_cast<const half_t*>(p.residual);
-    const half_t* __restrict__ rowadd = reinterpret_cast<const half_t*>(p.rowadd);
-    while (true) {
-        const int t_next = t_cur + J < t_end ? t_cur + J : -1;
-        const int tm = t_cur / tiles_n, tn = t_cur - tm * tiles_n;
-        const int m0 = tm * TM, n0 = tn * BN;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
-        for (int i = 0; i < nk; i += 2) {
-            const bool last = i + 2 >= nk;
-            if (last) set_dma_tile(t_next);                      // the stream moves on to the next tile's first pair
-            phase(yes_t{}, last ? 0 : i + 2);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            phase(no_t{}, 0);
-            if (!last) {
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // pair (i+2, i+3) complete
-                __builtin_amdgcn_s_barrier();
-            }
-        }
-        stat_publish(t_cur);
-        if (t_next >= 0) stat_issue(t_next);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-
-        // ---- epilogue from registers: lane = row m0 + wave_m * 128 + mt * 32 + (lane & 31); accumulator registers 4 g + r of a tile
-        //      are (permuted W rows) columns 16 (g >> 1) + 8 (lane >> 5) + 4 (g & 1) + r of the tile's 32 ----
-        // (the 16 column constants of a lane stay in registers for the GEGLU form; the plain form, which also holds row add / residual
-        //  operands, re-reads them from LDS per use)
-        f32x4 cw[NT][4], cb[NT][4];
-        if constexpr (GEGLU) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    cw[nt][g] = *reinterpret_cast<const f32x4*>(lws + wave_n * 64 + nt * 32 + 8 * g + 4 * fh);
-                    cb[nt][g] = *reinterpret_cast<const f32x4*>(lbi + wave_n * 64 + nt * 32 + 8 * g + 4 * fh);
-                }
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int rl = wave_m * 128 + mt * 32 + fr;
-            const int m = m0 + rl;
-            const float2 st = *reinterpret_cast<const float2*>(lst + 2 * rl);
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {                        // store s: registers g = 2 s, 2 s + 1 -> 8 consecutive columns 16 s + 8 fh
-                f32x4 v[NT][2];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int gg = 0; gg < 2; ++gg) {
-                        const int g = 2 * s + gg;
-                        const f32x4 a4 = {acc[mt][nt][4 * g], acc[mt][nt][4 * g + 1], acc[mt][nt][4 * g + 2], acc[mt][nt][4 * g + 3]};
-                        if constexpr (!GEGLU) {
-                            cw[nt][g] = *reinterpret_cast<const f32x4*>(lws + wave_n * 64 + nt * 32 + 8 * g + 4 * fh);
-                            cb[nt][g] = *reinterpret_cast<const f32x4*>(lbi + wave_n * 64 + nt * 32 + 8 * g + 4 * fh);
-                        }
-                        v[nt][gg] = st.x * a4 + (st.y * cw[nt][g] + cb[nt][g]);
-                    }
-                if constexpr (GEGLU) {
-                    half8v h;
-#pragma unroll
-                    for (int gg = 0; gg < 2; ++gg) {
-                        const f32x2 lo = moca_geglu2(f32x2{v[0][gg][0], v[0][gg][1]}, f32x2{v[1][gg][0], v[1][gg][1]});
-                        const f32x2 hi = moca_geglu2(f32x2{v[0][gg][2], v[0][gg][3]}, f32x2{v[1][gg][2], v[1][gg][3]});
-                        h[4 * gg + 0] = (half_t)lo[0]; h[4 * gg + 1] = (half_t)lo[1]; h[4 * gg + 2] = (half_t)hi[0]; h[4 * gg + 3] = (half_t)hi[1];
-                    }
-                    if (m < p.M) st_out8(reinterpret_cast<half_t*>(p.out) + (int64_t)m * p.ldo + (n0 >> 1) + wave_n * 32 + 16 * s + 8 * fh, h, nt_out);
-                } else {
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        const int col = n0 + wave_n * 64 + nt * 32 + 16 * s + 8 * fh;
-                        float o[8];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) { o[r] = v[nt][0][r]; o[4 + r] = v[nt][1][r]; }
-                        if (m < p.M) {
-                            if (rowadd) {
-                                const half8v e = *reinterpret_cast<const half8v*>(rowadd + (int64_t)(m / p.rowadd_div) * p.ld_rowadd + col);
-#pragma unroll
-                                for (int r = 0; r < 8; ++r) o[r] = (float)(half_t)o[r] + (float)e[r];
-                            }
-                            if (resid) {
-                                const half8v e = *reinterpret_cast<const half8v*>(resid + (int64_t)m * p.ldr + col);
-#pragma unroll
-                                for (int r = 0; r < 8; ++r) o[r] = (rowadd ? o[r] : (float)(half_t)o[r]) + (float)e[r];
-                            }
-                            half8v h;
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) h[r] = (half_t)o[r];
-                            st_out8(reinterpret_cast<half_t*>(p.out) + (int64_t)m * p.ldo + col, h, nt_out);
-                        }
-                    }
-                }
-            }
-        }
-        if (t_next < 0) break;
-        t_cur = t_next;
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");           // the next tile's first pair has landed (and the stores have left)
-        __builtin_amdgcn_s_barrier();
-    }
+    g4p_body<GEGLU, G4pMma32>(p);
 #endif
 }
 
@@ -594,9 +391,6 @@ __device__ __forceinline__ int sqp_perm(int rho) {              // LDS row of th
 template <bool GEGLU>
 __global__ __launch_bounds__(512, 2) void gemm_sqp_kernel(const moca_gemm_params p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-#ifndef SEG_WAVE
-#define SEG_WAVE 0
-#endif
     constexpr int MT = 4, NT = 8, KS = 32, RB = 64, WTM = 64, WTN = 128, TM = 256, BN = 256;
     constexpr int A_BYTES = TM * RB, STAGE = A_BYTES + BN * RB, NS = 5, PPW = 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -623,9 +417,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sqp_kernel(const moca_gemm_params
             tm_base = xi * sm; tn_base = xj * sub_n;
             q_base = 0; q_cnt = sm * sub_n;
         } else {
-            const int ntiles = tiles_m * tiles_n, q = ntiles >> 3, r = ntiles & 7;
-            q_base = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-            q_cnt = q + (x < r ? 1 : 0);
+            xcd_range(tiles_m * tiles_n, x, q_base, q_cnt);
             sub_n = tiles_n; tm_base = 0; tn_base = 0;
         }
     }
@@ -655,7 +447,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sqp_kernel(const moca_gemm_params
 
     // ---- DMA stream: piece = 16 rows x 64 B; A pieces w and 8 + w, W pieces w and 8 + w of every k-tile (4 per wave) ----
     const int lrow = lane >> 2, pch = lane & 3;
-    const int lch = pch ^ ((0x78 >> (2 * ((lrow >> 2) & 3))) & 3);
+    const int lch = pch ^ swz64(lrow);
     const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.a), 0, OOB_OFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, OOB_OFF, 0x00020000);
     unsigned a_off[2], w_off[2];
@@ -689,7 +481,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sqp_kernel(const moca_gemm_params
     };
 
     const int fr = lane & 15, fg = lane >> 4;
-    const int swz = (fg ^ ((0x78 >> (2 * ((fr >> 2) & 3))) & 3)) << 4;
+    const int swz = (fg ^ swz64(fr)) << 4;
     const int a_off0 = (wave_m * WTM + fr) * RB + swz;
     const int b_off0 = A_BYTES + (wave_n * WTN + fr) * RB + swz;
     f32x4 acc[MT][NT];
@@ -721,7 +513,6 @@ __global__ __launch_bounds__(512, 2) void gemm_sqp_kernel(const moca_gemm_params
     const bool fold = (p.flags & MOCA_EP_LNFOLD) != 0;
     const float* const dummy = reinterpret_cast<const float*>(p.w);
     constexpr unsigned STAT_SCRATCH = 8192;                      // offset of the raw-value areas inside the free slot
-    const int stat_floats = 2 + 2 * (fold ? p.lnf_nparts : 0);   // per lane: wsum, bias, (sum, sum of squares) per row partial
     auto stat_dma = [&](int q, unsigned slot_off) {              // waves 0..3 only
         int tm, tn;
         tile_of(q < q_end ? q : 0, tm, tn);
@@ -761,15 +552,12 @@ __global__ __launch_bounds__(512, 2) void gemm_sqp_kernel(const moca_gemm_params
         f.ws = fold ? ws : 0.f;
         f.b = p.bias ? b : 0.f;
         if (fold) {
-            const float inv_k = 1.0f / (float)p.K;
-            const float mean = s * inv_k;
-            const float var = fmaxf(qq * inv_k - mean * mean, 0.f);
-            f.rs = rsqrtf(var + p.ln_eps);
-            f.rb = -mean * f.rs;
+            const float2 st = lnfold_stats(s, qq, p.K, p.ln_eps);
+            f.rs = st.x;
+            f.rb = st.y;
         }
         return f;
     };
-    (void)stat_floats;
 
     // ---- prologue (once per block): two pairs in flight, the first landed everywhere ----
     LnFoldRegs lf = {1.f, 0.f, 0.f, 0.f};
@@ -942,22 +730,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sqp_kernel(const moca_gemm_params
                         float o[8];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { o[r] = v[2 * hh][r]; o[4 + r] = v[2 * hh + 1][r]; }
-                        if (m < p.M) {
-                            if (rowadd) {
-                                const half8v e = *reinterpret_cast<const half8v*>(rowadd + (int64_t)(m / p.rowadd_div) * p.ld_rowadd + col);
-#pragma unroll
-                                for (int r = 0; r < 8; ++r) o[r] = (float)(half_t)o[r] + (float)e[r];
-                            }
-                            if (resid) {
-                                const half8v e = *reinterpret_cast<const half8v*>(resid + (int64_t)m * p.ldr + col);
-#pragma unroll
-                                for (int r = 0; r < 8; ++r) o[r] = (rowadd ? o[r] : (float)(half_t)o[r]) + (float)e[r];
-                            }
-                            half8v h;
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) h[r] = (half_t)o[r];
-                            st_out8(reinterpret_cast<half_t*>(p.out) + (int64_t)m * p.ldo + col, h, nt_out);
-                        }
+                        store8_rowadd_res(p, m, col, o, rowadd, resid, nt_out);
                     }
                 }
             }

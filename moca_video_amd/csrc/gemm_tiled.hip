@@ -276,7 +276,7 @@ __global__ __launch_bounds__(512, 2) void gemm_glds_kernel(const moca_gemm_param
     constexpr int NRD = 4 + NT;      // fragment reads per half k-tile
 
     LnFoldRaw lraw = {float2{0.f, 0.f}, float2{0.f, 0.f}, 0.f, 0.f};
-    if (p.flags & MOCA_EP_LNFOLD) lraw = lnfold_issue<TM, BN>(p, m0 + tid, n0, tid);
+    if (p.flags & MOCA_EP_LNFOLD) lraw = lnfold_issue<TM, BN>(p, m0 + tid, n0 + tid, tid);
     MOCA_STAMP_P(10, a_row_b[0] + b_row_b[0]);
     if (nk > 0) issue(kt_begin, 0);
     MOCA_STAMP_P(11, 0);
@@ -491,8 +491,7 @@ __global__ __launch_bounds__(512, 2) void gemm_glds_kernel(const moca_gemm_param
 // resident block leaves the matrix pipe idle in those phases (s_memtime stamps: main loop only 35-42 % of a
 // K = 320 tile).  One 32-deep k-tile = one MFMA k-step: per tile 32 MFMAs, 12 fragment ds_read_b128 and 6 DMA
 // pieces per wave, one s_barrier; fragments are double-buffered in registers, the DMA runs three tiles ahead.
-// LDS rows are 64 B; chunk swizzle phys = chunk ^ f((row>>2)&3), f = {0,2,3,1} (conflict-free for the four
-// 16-lane groups of ds_read_b128 on the 16x16x32 operand map; derivation in DESIGN.md).
+// LDS rows are 64 B, their 16-byte chunks swizzled by swz64() (gemm_device.h).
 // =====================================================================================
 template <int AMODE, bool FAST>
 __global__ __launch_bounds__(256, 2) void gemm_g4_kernel(const moca_gemm_params p) {
@@ -537,7 +536,7 @@ __global__ __launch_bounds__(256, 2) void gemm_g4_kernel(const moca_gemm_params 
     // DMA piece = 1 KiB = 16 rows x 64 B: lane -> row (lane>>2), physical chunk lane&3; A piece g of this
     // wave covers rows (g*4 + wave)*16 .. +15 (g = 0..3), W piece g rows (g*4 + wave)*16 .. (g = 0..1)
     const int lrow = lane >> 2, pch = lane & 3;
-    const int lch = pch ^ ((0x78 >> (2 * ((lrow >> 2) & 3))) & 3);     // logical chunk fetched into this lane's slot
+    const int lch = pch ^ swz64(lrow);     // logical chunk fetched into this lane's slot
     AGather<AMODE, FAST, 4, KS> ga(p, lch);
 #pragma unroll
     for (int g = 0; g < 4; ++g) ga.init_row(g, m0 + (g * 4 + wave) * 16 + lrow);
@@ -582,12 +581,12 @@ __global__ __launch_bounds__(256, 2) void gemm_g4_kernel(const moca_gemm_params 
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         const int row = wave_m * 128 + mt * 16 + fr;
-        a_off[mt] = row * RB + ((fg ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3)) << 4);
+        a_off[mt] = row * RB + ((fg ^ swz64(row)) << 4);
     }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int row = wave_n * 64 + nt * 16 + fr;
-        b_off[nt] = A_BYTES + row * RB + ((fg ^ ((0x78 >> (2 * ((row >> 2) & 3))) & 3)) << 4);
+        b_off[nt] = A_BYTES + row * RB + ((fg ^ swz64(row)) << 4);
     }
 
     // ONE fragment set: the LDS-read latency at the head of a phase is covered by the co-resident block's
@@ -631,7 +630,7 @@ __global__ __launch_bounds__(256, 2) void gemm_g4_kernel(const moca_gemm_params 
 
     // ---- prologue: pair (0, 1) ----
     LnFoldRaw lraw = {float2{0.f, 0.f}, float2{0.f, 0.f}, 0.f, 0.f};
-    if (p.flags & MOCA_EP_LNFOLD) lraw = lnfold_issue<TM, BN>(p, m0 + tid, n0, tid);
+    if (p.flags & MOCA_EP_LNFOLD) lraw = lnfold_issue<TM, BN>(p, m0 + tid, n0 + tid, tid);
     issue_pair(kt_begin, 0, 1);
     LnFoldRegs lf = {0.f, 0.f, 0.f, 0.f};
     if (p.flags & MOCA_EP_LNFOLD) lf = lnfold_finish<TM, BN>(p, lraw, m0 + tid, tid);

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(512, 2) void MOCA_W80S_NAME(const moca_gemm_params 
     //   j = 0: big piece w      j = 1: big piece 8 + w      j = 2: big piece 16 + w (w < 4)  or  small piece w - 4 (w >= 4)
     //   j = 3: small piece 4 + w (w < 6)  or  small piece 2 + w (w = 6, 7: a repeat, so that every wave issues 4 per k-tile)
     const int lrow = lane >> 2, pch = lane & 3;
-    const int lch = pch ^ ((0x78 >> (2 * ((lrow >> 2) & 3))) & 3);
+    const int lch = pch ^ swz64(lrow);
     const bool flex_is_big = wave < 4;
     const int kt_last_pair = kt_begin + nk - 2;
     BGather<AMODE, NAP, KS> ga(p, lch, kt_begin, kt_last_pair);
@@ -146,6 +146,7 @@ __global__ __launch_bounds__(512, 2) void MOCA_W80S_NAME(const moca_gemm_params 
         for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = bv;
     }
 
+    // (swz64(fr), written out: through the helper the SHAPE 3 kernels leave their encodings, the causal one two instructions longer)
     const int swz = (fg ^ ((0x78 >> (2 * ((fr >> 2) & 3))) & 3)) << 4;
     const int a_off0 = (wave_m * WTM + fr) * RB + swz;
     const int b_off0 = A_BYTES + (wave_n * WTN + fr) * RB + swz;
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(512, 2) void MOCA_W80S_NAME(const moca_gemm_params 
 
     // ---- prologue: pairs (0,1) and (2,3) in flight, pair (0,1) landed everywhere ----
     LnFoldRaw lraw = {float2{0.f, 0.f}, float2{0.f, 0.f}, 0.f, 0.f};
-    if (p.flags & MOCA_EP_LNFOLD) lraw = lnfold_issue<TM, BN>(p, grow(tid), n0, tid);
+    if (p.flags & MOCA_EP_LNFOLD) lraw = lnfold_issue<TM, BN>(p, grow(tid), n0 + tid, tid);
     ga.seek(kt_begin);
     sync_src();
     issue_pair(0, 1);
@@ -224,12 +225,6 @@ __global__ __launch_bounds__(512, 2) void MOCA_W80S_NAME(const moca_gemm_params 
 #endif
         // ---- LOADe: tile i only ----
 #ifdef MOCA_STAMPS
-#ifndef SEG_WAVE
-#define SEG_WAVE 0
-#endif
-#ifndef SEG_ITER
-#define SEG_ITER 2
-#endif
         const bool seg = i == SEG_ITER;
         if (seg) MOCA_STAMP_W(8, SEG_WAVE);
 #endif

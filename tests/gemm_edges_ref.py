@@ -1,8 +1,9 @@
-"""Operands, route table and float64 torch restatements for tests/test_gemm_edges_gpu.py and tests/test_gemm_edges_cpu.py.
+"""Operands, route table and float64 torch restatements for tests/test_gemm_edges_gpu.py and tests/test_gemm_edges_cpu.py, and the
+cases of tests/test_gemm_persistent_parent_gpu.py (PERSISTENT_PARENT_CASES: the persistent kernels against the parent commit's bits).
 
 Every reference works on the fp16-rounded operands it is handed and returns float64 [M][N]; the metric is taken per block of 64
-output rows so that a wrong tile cannot hide under another tile's maximum.  Nothing here touches a GPU by itself: the builders make
-their tensors on the CPU from a seeded generator and the caller moves them."""
+output rows so that a wrong tile cannot hide under another tile's maximum.  The builders make their tensors on the CPU from a seeded
+generator; only launch() and the parent-bits runner behind it (the last two sections) move them to the device and run a kernel."""
 import torch
 import torch.nn.functional as F
 
@@ -532,3 +533,207 @@ def query_sweep(visit):
         finally:
             for k, v in old.items():
                 L.set_tuning(k, v)
+
+
+# ---------------------------------------------------------------- one launch (tests/test_gemm_edges_gpu.py and the parent-bits cases)
+DEV = "cuda"
+
+
+def geo_kw(geo, C, up_phase=0):
+    if geo["kind"] == "tconv":
+        return dict(mode=L.MOCA_A_TCONV3, tconv=(C, geo["T"], geo["HW"]))
+    oh, ow = (geo["H"], geo["W"]) if up_phase else geo_out(geo)
+    return dict(mode=L.MOCA_A_CONV3X3, conv=(C, geo["H"], geo["W"], oh, ow, geo["stride"], geo["up"], geo["nopad"]))
+
+
+def pack(case, geo=None, act=None):
+    ops = _ops()
+    if geo is None:
+        return ops.pack_geglu(case["w"], case["bias"]) if act == "geglu" else ops.pack_linear(case["w"], case["bias"])
+    return (ops.pack_tconv3 if geo["kind"] == "tconv" else ops.pack_conv3x3)(case["w"], case["bias"])
+
+
+def assert_route(route, a, pw, M, kw, residual=False, rowadd=False, splits=1):
+    """the plain form of this call (fp16 output, one split, no activation) runs on the route's kernel and has its signature; a
+    persistent kernel's case runs on that kernel as it is launched"""
+    ops = _ops()
+    d = torch.empty(1, pw.N, dtype=torch.float16)      # (output / residual / row add of the question: read for pointer and row stride only)
+    if route in PERSISTENT:
+        got = ops.gemm_route(a, pw, d, M=M, residual=d if residual else None, rowadd=d if rowadd else None, splits=splits,
+                             splitk_ws=d if splits > 1 else None, **kw)
+        assert got == ROUTE_ID[route], f"{route}: M={M} N={pw.N} K={pw.K} runs on route {got}"
+        assert route != "sq256" or ops.gemm_colsum_rows(a, pw, M=M) == 0      # (the 256-row kernel it replaces would answer 256)
+        return
+    plain = {k: v for k, v in kw.items() if k in ("mode", "conv", "tconv", "force_small")}
+    pwq = pw
+    if pw.geglu:                                       # (the GEGLU flag is part of the epilogue, not of the shape)
+        pwq = ops.PackedWeight(pw.w, pw.bias, pw.N, pw.K, pw.N)
+    linear = "mode" not in kw
+    got = signature(route, a, pwq, M=M, **plain)
+    assert got == expected_signature(route, linear=linear), f"{route}: M={M} N={pw.N} K={pw.K} runs on another kernel: {got}"
+    if "up_phase" in kw:                               # (K = 4 C: a launch only as a phase; the queries do not look at the operand shape)
+        plain["up_phase"] = kw["up_phase"]
+    got = ops.gemm_route(a, pwq, d, M=M, **plain)
+    assert got == ROUTE_ID[route], f"{route}: M={M} N={pw.N} K={pw.K} runs on route {got}"
+
+
+_embed = embed
+
+
+def launch(route, case, *, geo=None, C=None, act=None, embed=True, splits=1, out_f32=False, alias=False, lda_pad=24, a_dev=None,
+           check_route=True, **extra):
+    """One moca_gemm_f16 call for `case` (linear_case / random_geo_case / a probe).  embed: every operand sits in a
+    larger NaN-filled allocation -- a [M + 2][K + lda_pad] from row 1 (linear), out / residual / row add with 8 pad columns and one guard
+    row above and below.  Returns (out view, out buffer or None, pw)."""
+    ops = _ops()
+    M = case["M"]
+    pw = pack(case, geo, act)
+    n_out = pw.n_out if act == "geglu" else pw.N
+    kw = dict(extra)
+    if geo is not None:
+        a = case["x"].to(DEV).reshape(-1, C)
+        kw.update(geo_kw(geo, C))
+    elif a_dev is not None:
+        a = a_dev
+    elif embed:
+        _, a = _embed(case["a"], pad=lda_pad, dev=DEV)
+    else:
+        a = case["a"].to(DEV)
+    if needs_force_small(route, M):
+        kw["force_small"] = True
+    if act == "gelu":
+        kw["gelu"] = True
+    if check_route:
+        assert_route(route, a, pw, M, kw, case.get("res") is not None, case.get("rowadd") is not None, splits)
+        assert route not in PERSISTENT or not out_f32
+    odt = torch.float32 if out_f32 else torch.float16
+    obuf, out = canary_out(M, n_out, DEV, dtype=odt) if embed else (None, torch.full((M, n_out), NAN, dtype=odt, device=DEV))
+    res = ra = None
+    if case.get("res") is not None:
+        if alias:                                      # x = f(x) + x in place (attention.py:217-219)
+            out.copy_(case["res"].to(DEV))
+            res = out
+        else:
+            res = _embed(case["res"], dev=DEV)[1] if embed else case["res"].to(DEV)
+    if case.get("rowadd") is not None:
+        ra = _embed(case["rowadd"], dev=DEV)[1] if embed else case["rowadd"].to(DEV)
+    ws = None
+    if splits > 1:
+        s = normalise_splits(pw.K, splits)
+        ws = torch.full((s * M * pw.N + 4096,), NAN, dtype=torch.float32, device=DEV) if s > 1 else None
+        if ws is None:                                 # (the entry asks for a workspace whenever the REQUESTED factor is > 1)
+            ws = torch.full((4096,), NAN, dtype=torch.float32, device=DEV)
+    ops.gemm(a, pw, out, M=M, residual=res, rowadd=ra, rowadd_div=case.get("div", 1), splits=splits, splitk_ws=ws, out_f32=out_f32, **kw)
+    if ws is not None:
+        assert torch.isnan(ws[-4096:]).all(), f"{route}: the split-K slabs run past the workspace of the normalised factor"
+    launch.ws = ws
+    return out, obuf, pw
+
+
+# ---------------------------------------------------------------- the persistent kernels against the parent commit's bits
+# (tests/test_gemm_persistent_parent_gpu.py, tools/record_parent_fixtures.py --persistent-sha).  Shapes: the smallest tile count all three
+# routes take, with an 8-row M tail; K = 64 / 128 / 320 = one, two and five k-tile pairs (320 moves sqp's 5-slot ring phase from tile to tile).
+PARENT_ROUTES = ("g4p", "g4q", "sqp")
+PARENT_MN, PARENT_KS = (8200, 2048), (64, 128, 320)
+PARENT_2D = (4090, 4096, 64)                        # 16 x 16 tiles of sqp: choose_xcd_n takes the 2-D partition xcd_n = 2 (4 W + 2 A against 8 W + A, A ~ W)
+PARENT_STREAM = (16384, 4096, 64)                   # an output of exactly 128 MiB: reserved4_ bit 0, the streaming st_out8
+PARENT_PREFETCH_KIB = 25
+
+
+def _persistent_parent_cases():
+    M, N = PARENT_MN
+    out = []
+    for route in PARENT_ROUTES:
+        add = lambda name, **spec: out.append((route, f"{route}.{name}", dict(dict(M=M, N=N, K=64, bias=1, div=0, res=0), **spec)))
+        for K in PARENT_KS:
+            for bias in (1, 0):
+                for div in (0, 7, M):
+                    for res in (0, 1):
+                        add(f"plain.K{K}.bias{bias}.div{div}.res{res}", K=K, bias=bias, div=div, res=res)
+            add(f"alias.K{K}", K=K, res=1, alias=1)
+            add(f"geglu.K{K}", K=K, geglu=1)
+        for nparts in (1, 2, 3, 10):
+            add(f"fold.parts{nparts}", K=128, nparts=nparts, div=7, res=1)
+            add(f"fold.parts{nparts}.geglu", K=128, nparts=nparts, geglu=1)
+        add("prefetch", div=7, res=1, prefetch_kib=PARENT_PREFETCH_KIB)
+        if route == "sqp":
+            add("walk1", K=320, div=7, res=1, walk=1)
+            add("walk1.geglu", K=320, geglu=1, walk=1)
+            add("xcd2d", M=PARENT_2D[0], N=PARENT_2D[1], K=PARENT_2D[2], res=1)
+        add("stream", M=PARENT_STREAM[0], N=PARENT_STREAM[1], K=PARENT_STREAM[2])
+    return out
+
+
+PERSISTENT_PARENT_CASES = _persistent_parent_cases()
+
+
+def sha(*tensors):
+    import hashlib
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+_PARENT_OPERANDS = {}
+
+
+def _parent_operands(M, N, K):
+    """host-generated operands of one shape, shared by its cases (the last shape is kept): a, w, bias, row adds for rowadd_div 7 and M,
+    residual -- drawn in this order from one seeded generator, so a case's operands do not depend on which cases ran before it"""
+    if _PARENT_OPERANDS.get("key") != (M, N, K):
+        g = gen(9000 + K + N)
+        _PARENT_OPERANDS.clear()
+        _PARENT_OPERANDS.update(key=(M, N, K), a=randh(g, M, K), w=randh(g, N, K, scale=K ** -0.5), bias=torch.randn(N, generator=g) * 0.1,
+                                ra7=randh(g, (M + 6) // 7, N), raM=randh(g, 1, N), res=randh(g, M, N))
+    return _PARENT_OPERANDS
+
+
+def run_persistent_parent_case(route, name, spec):
+    """one launch of PERSISTENT_PARENT_CASES under the knobs in force -> sha256 of the output rows; the canary round them must be intact"""
+    M, N, K = spec["M"], spec["N"], spec["K"]
+    if spec.get("nparts"):
+        import gemm_fused_ref as FR
+        ops = _ops()
+        c = FR._case("B", route, M, N, K, 9100 + spec["nparts"], nparts=spec["nparts"], geglu=bool(spec.get("geglu")), div=spec["div"],
+                     res=bool(spec["res"]))
+        t = FR.build(c, FR.operands(c), DEV)
+        got = ops.gemm_route(t["a"], t["pw"], t["out"], **t["kw"])
+        assert got == ROUTE_ID[route], f"{name}: runs on route {got}"
+        ops.gemm(t["a"], t["pw"], t["out"], **t["kw"])
+        out, obuf = t["out"], t["obuf"]
+    else:
+        o = _parent_operands(M, N, K)
+        div = spec["div"]
+        case = dict(M=M, a=o["a"], w=o["w"], bias=o["bias"] if spec["bias"] else None, div=max(div, 1),
+                    rowadd=None if not div else (o["ra7"] if div == 7 else o["raM"]), res=o["res"] if spec["res"] else None)
+        extra = {}
+        if spec.get("prefetch_kib"):
+            extra["prefetch"] = torch.randint(0, 256, (spec["prefetch_kib"] << 10,), dtype=torch.uint8, generator=gen(9200)).to(DEV)
+        out, obuf, _ = launch(route, case, act="geglu" if spec.get("geglu") else None, alias=bool(spec.get("alias")), **extra)
+    torch.cuda.synchronize()
+    assert not torch.isnan(out).any(), f"{name}: an output row was not written"
+    assert_canary(obuf, M, out.shape[1], name)
+    return sha(out)
+
+
+def persistent_parent_hashes(route):
+    """{name: sha256} of the route's cases of PERSISTENT_PARENT_CASES, in their order; the route's knobs (and a case's
+    MOCA_TUNE_SQP_WALK) set and restored around them"""
+    out = {}
+    old = {k: L.set_tuning(k, v) for k, v in PERSISTENT[route]["knobs"].items()}
+    try:
+        for r, name, spec in PERSISTENT_PARENT_CASES:
+            if r != route:
+                continue
+            walk = L.set_tuning(L.MOCA_TUNE_SQP_WALK, spec["walk"]) if "walk" in spec else None
+            try:
+                out[name] = run_persistent_parent_case(route, name, spec)
+            finally:
+                if walk is not None:
+                    L.set_tuning(L.MOCA_TUNE_SQP_WALK, walk)
+    finally:
+        for k, v in old.items():
+            L.set_tuning(k, v)
+        _PARENT_OPERANDS.clear()
+    return out

@@ -34,7 +34,7 @@ import pytest
 import torch
 
 import gemm_edges_ref as R
-from gemm_edges_ref import NAN, TOL16, TOL32
+from gemm_edges_ref import NAN, TOL16, TOL32, assert_route, geo_kw, launch, pack
 
 pytestmark = pytest.mark.gpu
 
@@ -83,92 +83,6 @@ def gather_paths(route):
 
 
 ROUTE_GATHER = [(r, g) for r in R.CONV_ROUTES for g in gather_paths(r)]
-
-
-# ---------------------------------------------------------------- one launch
-def geo_kw(geo, C, up_phase=0):
-    if geo["kind"] == "tconv":
-        return dict(mode=L.MOCA_A_TCONV3, tconv=(C, geo["T"], geo["HW"]))
-    oh, ow = (geo["H"], geo["W"]) if up_phase else R.geo_out(geo)
-    return dict(mode=L.MOCA_A_CONV3X3, conv=(C, geo["H"], geo["W"], oh, ow, geo["stride"], geo["up"], geo["nopad"]))
-
-
-def pack(case, geo=None, act=None):
-    if geo is None:
-        return ops.pack_geglu(case["w"], case["bias"]) if act == "geglu" else ops.pack_linear(case["w"], case["bias"])
-    return (ops.pack_tconv3 if geo["kind"] == "tconv" else ops.pack_conv3x3)(case["w"], case["bias"])
-
-
-def assert_route(route, a, pw, M, kw, residual=False, rowadd=False, splits=1):
-    """the plain form of this call (fp16 output, one split, no activation) runs on the route's kernel and has its signature; a
-    persistent kernel's case runs on that kernel as it is launched"""
-    d = torch.empty(1, pw.N, dtype=torch.float16)      # (output / residual / row add of the question: read for pointer and row stride only)
-    if route in R.PERSISTENT:
-        got = ops.gemm_route(a, pw, d, M=M, residual=d if residual else None, rowadd=d if rowadd else None, splits=splits,
-                             splitk_ws=d if splits > 1 else None, **kw)
-        assert got == R.ROUTE_ID[route], f"{route}: M={M} N={pw.N} K={pw.K} runs on route {got}"
-        assert route != "sq256" or ops.gemm_colsum_rows(a, pw, M=M) == 0      # (the 256-row kernel it replaces would answer 256)
-        return
-    plain = {k: v for k, v in kw.items() if k in ("mode", "conv", "tconv", "force_small")}
-    pwq = pw
-    if pw.geglu:                                       # (the GEGLU flag is part of the epilogue, not of the shape)
-        pwq = ops.PackedWeight(pw.w, pw.bias, pw.N, pw.K, pw.N)
-    linear = "mode" not in kw
-    got = R.signature(route, a, pwq, M=M, **plain)
-    assert got == R.expected_signature(route, linear=linear), f"{route}: M={M} N={pw.N} K={pw.K} runs on another kernel: {got}"
-    if "up_phase" in kw:                               # (K = 4 C: a launch only as a phase; the queries do not look at the operand shape)
-        plain["up_phase"] = kw["up_phase"]
-    got = ops.gemm_route(a, pwq, d, M=M, **plain)
-    assert got == R.ROUTE_ID[route], f"{route}: M={M} N={pw.N} K={pw.K} runs on route {got}"
-
-
-def launch(route, case, *, geo=None, C=None, act=None, embed=True, splits=1, out_f32=False, alias=False, lda_pad=24, a_dev=None,
-           check_route=True, **extra):
-    """One moca_gemm_f16 call for `case` (gemm_edges_ref.linear_case / random_geo_case / a probe).  embed: every operand sits in a
-    larger NaN-filled allocation -- a [M + 2][K + lda_pad] from row 1 (linear), out / residual / row add with 8 pad columns and one guard
-    row above and below.  Returns (out view, out buffer or None, pw)."""
-    M = case["M"]
-    pw = pack(case, geo, act)
-    n_out = pw.n_out if act == "geglu" else pw.N
-    kw = dict(extra)
-    if geo is not None:
-        a = case["x"].to(DEV).reshape(-1, C)
-        kw.update(geo_kw(geo, C))
-    elif a_dev is not None:
-        a = a_dev
-    elif embed:
-        _, a = R.embed(case["a"], pad=lda_pad, dev=DEV)
-    else:
-        a = case["a"].to(DEV)
-    if R.needs_force_small(route, M):
-        kw["force_small"] = True
-    if act == "gelu":
-        kw["gelu"] = True
-    if check_route:
-        assert_route(route, a, pw, M, kw, case.get("res") is not None, case.get("rowadd") is not None, splits)
-        assert route not in R.PERSISTENT or not out_f32
-    odt = torch.float32 if out_f32 else torch.float16
-    obuf, out = R.canary_out(M, n_out, DEV, dtype=odt) if embed else (None, torch.full((M, n_out), NAN, dtype=odt, device=DEV))
-    res = ra = None
-    if case.get("res") is not None:
-        if alias:                                      # x = f(x) + x in place (attention.py:217-219)
-            out.copy_(case["res"].to(DEV))
-            res = out
-        else:
-            res = R.embed(case["res"], dev=DEV)[1] if embed else case["res"].to(DEV)
-    if case.get("rowadd") is not None:
-        ra = R.embed(case["rowadd"], dev=DEV)[1] if embed else case["rowadd"].to(DEV)
-    ws = None
-    if splits > 1:
-        s = R.normalise_splits(pw.K, splits)
-        ws = torch.full((s * M * pw.N + 4096,), NAN, dtype=torch.float32, device=DEV) if s > 1 else None
-        if ws is None:                                 # (the entry asks for a workspace whenever the REQUESTED factor is > 1)
-            ws = torch.full((4096,), NAN, dtype=torch.float32, device=DEV)
-    ops.gemm(a, pw, out, M=M, residual=res, rowadd=ra, rowadd_div=case.get("div", 1), splits=splits, splitk_ws=ws, out_f32=out_f32, **kw)
-    if ws is not None:
-        assert torch.isnan(ws[-4096:]).all(), f"{route}: the split-K slabs run past the workspace of the normalised factor"
-    launch.ws = ws
-    return out, obuf, pw
 
 
 def check(out, obuf, case, what, group, tol=TOL16):

@@ -1,5 +1,5 @@
 """GPU: what moca_gemm_f16 does beyond bias, row add, residual and GEGLU (csrc/gemm_device.h store_fp16_tile_ln, lnfold_issue / _finish /
-_apply and their copies in gemm_persistent.hip, the two-source gather and the per-row-group weights of gemm_w80s_kernel.inc / gemm_ws.hip,
+_apply as the tiled kernels and g4p / g4q call them, lnfold_stats under sqp's stat_read in gemm_persistent.hip, the two-source gather and the per-row-group weights of gemm_w80s_kernel.inc / gemm_ws.hip,
 MOCA_EP_GSTAT with gstat_cpg / gstat_coff, the MOCA_EP_TATTN epilogue), on the kernel each case is meant for, against float64 torch on
 the same fp16 operands (tests/gemm_fused_ref.py: the case tables, checked without a device by tests/test_gemm_fused_cpu.py).
 

@@ -17,6 +17,9 @@ optimisation or a compiler bump legitimately changes them:
                                                  leaves on the cases and host-generated operands of
                                                  tests/norm_edges_ref.py::parent_names (outputs, and the accumulators the concat /
                                                  accum launches add to)
+  tests/golden/gemm_persistent_parent_sha.npz    (--persistent-sha, on the GPU)  sha256 of the output rows of the persistent GEMM kernels
+                                                 of csrc/gemm_persistent.hip (g4p, g4q, sqp) on the cases and host-generated operands
+                                                 of tests/gemm_edges_ref.py::PERSISTENT_PARENT_CASES
   tests/golden/sampler_routes.npz                (--samplers, no GPU)  the traces of tests/sampler_routes_cpu.py::record: the UNet entry
                                                  points and launches of the sampling layer (guidance routing, host-issued loops,
                                                  ddim_step, queue noising, the host-driven FIFO loop, `supported()` tables, the
@@ -28,10 +31,11 @@ optimisation or a compiler bump legitimately changes them:
     python tools/record_parent_fixtures.py --tree ../base --sha            (on the MI355X)
     python tools/record_parent_fixtures.py --tree ../base --attention-sha  (on the MI355X)
     python tools/record_parent_fixtures.py --tree ../base --norm-sha       (on the MI355X)
+    python tools/record_parent_fixtures.py --tree ../base --persistent-sha (on the MI355X)
     python tools/record_parent_fixtures.py --tree ../base --samplers       (any host)
 
 The package is imported from --tree, the helpers (tests/plan_cpu.py, tests/temporal_variants_ref.py, tests/attention_edges_ref.py,
-tests/norm_edges_ref.py) and the output directory are this checkout's.  A tree older than the host-recordable plan (no `UNetModel._pack(dev)`, a stream created unconditionally) is recorded
+tests/norm_edges_ref.py, tests/gemm_edges_ref.py) and the output directory are this checkout's.  A tree older than the host-recordable plan (no `UNetModel._pack(dev)`, a stream created unconditionally) is recorded
 through two stand-ins defined here; nothing of it is modified."""
 import argparse
 import os
@@ -129,6 +133,21 @@ def record_norm_sha():
     np.savez_compressed(os.path.join(GOLD, "norm_parent_sha.npz"), names=np.asarray(names), sha256=np.asarray(shas))
 
 
+def record_persistent_sha():
+    import gemm_edges_ref as R
+    names, shas = [], []
+    for route in R.PARENT_ROUTES:
+        got = R.persistent_parent_hashes(route)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        for n, h in got.items():
+            names.append(n)
+            shas.append(h)
+            print(route, n, h)
+    assert names == [n for _, n, _ in R.PERSISTENT_PARENT_CASES]
+    np.savez_compressed(os.path.join(GOLD, "gemm_persistent_parent_sha.npz"), names=np.asarray(names), sha256=np.asarray(shas))
+
+
 def record_samplers():
     import sampler_routes_cpu
     out = sampler_routes_cpu.record()
@@ -143,6 +162,7 @@ def main():
     ap.add_argument("--sha", action="store_true")
     ap.add_argument("--attention-sha", action="store_true")
     ap.add_argument("--norm-sha", action="store_true")
+    ap.add_argument("--persistent-sha", action="store_true")
     ap.add_argument("--samplers", action="store_true")
     a = ap.parse_args()
     tree = os.path.abspath(a.tree)
@@ -158,6 +178,8 @@ def main():
         record_attention_sha()
     if a.norm_sha:
         record_norm_sha()
+    if a.persistent_sha:
+        record_persistent_sha()
     if a.samplers:
         record_samplers()
 
