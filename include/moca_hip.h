@@ -587,7 +587,13 @@ int moca_base_ddim_step_f32(moca_fifo_state* state, float* x, const float* eps_c
  * built by the host in fp32 as the reference's buffers are (:136-153,:376).  mask is [B][per], or with MOCA_DDPM_MASK_C0
  * [B][mask_inner] read with channel stride 0 (per % mask_inner == 0).  out may alias x; out, x_recon, mean are optional (one at
  * least; out needs noise).  eps_c NULL: no reverse step, out = orig (`q_sample`; x0, noise_q, out only).  per need not be a multiple
- * of 4.  t_b outside [0, n_tab) reads no table entry: every output of sample b is NaN.  state non-NULL: then iter += 1,
+ * of 4.  eps_c NULL with mask (and x, which it reads; out may be x): the blend alone, out = orig mask + (1 - mask) x -- what the
+ * upstream latent-diffusion DDIM loop runs BEFORE the model call of a step (`img_orig = q_sample(x0, ts)`, then :648's expression):
+ * DDIM / DPM-Solver inpainting launches it in front of the forward with t = the plan's timestep rows, and on a private clean row
+ * {.., sac 1, s1mac 0, scale 1} to paste x0 back exactly.  Access widths and checks are those of the step: 16-byte groups where x,
+ * out, x0, noise_q (and a full mask) are 16-byte aligned and a group lies inside one sample, a one-channel mask 16 bytes wide where
+ * it is aligned and per % 4 == mask_inner % 4 == 0, 4 bytes otherwise; every pointer 4-byte aligned, per % mask_inner == 0.
+ * t_b outside [0, n_tab) reads no table entry: every output of sample b is NaN.  state non-NULL: then iter += 1,
  * ext_noise = 0 (the captured step of fifo_graph.DdpmEngine); NULL: the state is not touched (host-issued calls). */
 #define MOCA_DDPM_X0 1
 #define MOCA_DDPM_CLIP 2

@@ -16,6 +16,8 @@ Public surface mirrors the reference interfaces for this path only:
   freeinit_ddim_sampling   FreeInit (Wu et al., 2023) over base_ddim_sampling: re-noise with the initial noise, freq_mix_3d, sample again
   DPMSolverSampler     DPM-Solver++(2M) (Lu et al., 2022) on DDIMSampler's timestep grid and one-graph step; no counterpart in the reference
   dpm_solver_sampling, v2v_dpm_solver_sampling   base_ddim_sampling / v2v_ddim_sampling with that solver (20 steps where DDIM takes 50)
+  inpaint_ddim_sampling, inpaint_dpm_solver_sampling   masked inpainting (keep the clip where mask == 1) at DDIM / DPM-Solver speed:
+                       upstream's blend in front of every step of the one-graph loop (DDIMSampler.sample / decode with mask=, x0=)
   load_multiprompts, run_multiprompts  its prompt file and driver (moca_video_amd.io)
   instantiate_from_config       utils/utils.py:27-42
   AutoencoderKL                 lvdm/models/autoencoder.py:13-107 + lvdm/modules/networks/ae_modules.py:364-579
@@ -40,10 +42,12 @@ from .clip_vision import FrozenOpenCLIPImageEmbedder, FrozenOpenCLIPImageEmbedde
 from .wrapper import LatentVisualDiffusion  # noqa: E402
 from .fifo import fifo_ddim_sampling_multiprompts, freeinit_ddim_sampling, v2v_ddim_sampling, v2v_invert_sampling  # noqa: E402
 from .fifo import dpm_solver_sampling, v2v_dpm_solver_sampling  # noqa: E402
+from .fifo import inpaint_ddim_sampling, inpaint_dpm_solver_sampling  # noqa: E402
 from .sampler import DPMSolverSampler  # noqa: E402
 from .io import load_multiprompts, run_multiprompts  # noqa: E402
 
 __all__ = ["UNetModel", "DiffusionWrapper", "DenoiseModel", "AutoencoderKL", "FrozenOpenCLIPEmbedder", "SimpleTokenizer", "ImageProjModel", "Resampler",
            "FrozenOpenCLIPImageEmbedder", "FrozenOpenCLIPImageEmbedderV2", "LatentVisualDiffusion", "instantiate_from_config",
            "load_unet_config", "fifo_ddim_sampling_multiprompts", "v2v_ddim_sampling", "v2v_invert_sampling", "freeinit_ddim_sampling", "load_multiprompts", "run_multiprompts",
-           "DPMSolverSampler", "dpm_solver_sampling", "v2v_dpm_solver_sampling"]
+           "DPMSolverSampler", "dpm_solver_sampling", "v2v_dpm_solver_sampling",
+           "inpaint_ddim_sampling", "inpaint_dpm_solver_sampling"]

@@ -137,45 +137,6 @@ __global__ void gaussian_sample_kernel(const float* __restrict__ mom, const floa
     }
 }
 
-// ---- the walk of q_sample_kernel and ddpm_step_kernel: one thread per group of four consecutive elements of the FLAT [B * per]
-// range, each sample with its own coefficients.  A group that lies inside one sample (and every pointer being 16-byte aligned) moves
-// as float4; a group that straddles two samples (per % 4 != 0) or the end goes element by element -- nothing is read or written past
-// B * per.
-struct group4 {
-    int64_t e0, b0;   // first element, its sample
-    int cnt;          // elements inside [0, total)
-    bool vec;         // whole, inside sample b0, pointers aligned
-};
-
-__device__ __forceinline__ group4 group4_at(int64_t q, int64_t total, int64_t per, int vec_ok) {
-    group4 g;
-    g.e0 = q * 4;
-    g.b0 = g.e0 / per;
-    g.cnt = total - g.e0 < 4 ? (int)(total - g.e0) : 4;
-    g.vec = vec_ok && g.cnt == 4 && (g.e0 + 3) / per == g.b0;
-    return g;
-}
-
-// p NULL: v keeps what it holds / nothing is stored
-__device__ __forceinline__ void group4_ld(const float* p, int64_t e0, bool vec, int cnt, float (&v)[4]) {
-    if (!p) return;
-    if (vec) {
-        const float4 q = *reinterpret_cast<const float4*>(p + e0);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        for (int j = 0; j < cnt; ++j) v[j] = p[e0 + j];
-    }
-}
-
-__device__ __forceinline__ void group4_st(float* p, int64_t e0, bool vec, int cnt, const float (&v)[4]) {
-    if (!p) return;
-    if (vec) {
-        *reinterpret_cast<float4*>(p + e0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        for (int j = 0; j < cnt; ++j) p[e0 + j] = v[j];
-    }
-}
-
 // q_sample over per-sample schedule indices (ddim.py:652-671 `stochastic_encode`): out[b][p] = ca[t[b]] * x0[b][p] + cb[t[b]] * noise[b][p].
 // The gather of both tables runs here (t and the tables are device memory: nothing for the host to read, the launch can be captured).
 // mul, mul, add with no contraction = the torch expression bit for bit.  out may alias x0 (every element is read before it is written,
@@ -227,7 +188,8 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* x0, const fl
 //   orig = sac x0 [scale] + s1mac noise_q                   :415-420
 //   out = orig mask + (1 - mask) out                        :648
 // mul / add / sub only and no contraction: bit-equal to the torch expression over the same tables.  coef[t] = {srac, srm1, c1, c2,
-// std, sac, s1mac, scale}.  eps_c NULL: no reverse step, out = orig (`q_sample`).  Groups of four as above (vec_ok: every pointer
+// std, sac, s1mac, scale}.  eps_c NULL: no reverse step, out = orig (`q_sample`), or with a mask out = orig mask + (1 - mask) x: the
+// blend alone, which upstream's DDIM loop runs BEFORE the model call of a step (DDIM / DPM-Solver inpainting).  Groups of four as above (vec_ok: every pointer
 // is 16-byte aligned); out may alias x (each thread reads all it needs before it writes).  t_b outside [0, n_tab): nothing is read
 // from the table and every output of sample b is NaN.
 struct ddpm_args {
@@ -261,7 +223,7 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const ddpm_args a) {
     const int64_t n4 = (total + 3) / 4;
     const float qnan = __builtin_nanf("");
     const bool x0_param = a.flags & MOCA_DDPM_X0, clip = a.flags & MOCA_DDPM_CLIP, use_scale = a.flags & MOCA_DDPM_SCALE;
-    const bool blend = a.eps_c && a.mask;
+    const bool blend = a.mask != nullptr;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
         const group4 g = group4_at(q, total, per, a.vec_ok);
         const int64_t e0 = g.e0, b0 = g.b0;
@@ -274,18 +236,7 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const ddpm_args a) {
         if (a.out) group4_ld(a.noise, e0, vec, cnt, nz);
         group4_ld(a.x0, e0, vec, cnt, x0);
         group4_ld(a.noise_q, e0, vec, cnt, nq);
-        if (blend) {
-            if (!(a.flags & MOCA_DDPM_MASK_C0)) {
-                group4_ld(a.mask, e0, vec, cnt, mk);
-            } else if (vec && a.mask_vec) {                     // per % 4 == 0 and inner % 4 == 0: the group stays inside one channel
-                group4_ld(a.mask, b0 * a.mask_inner + (e0 - b0 * per) % a.mask_inner, true, 4, mk);
-            } else {
-                for (int j = 0; j < cnt; ++j) {
-                    const int64_t b = (e0 + j) / per;
-                    mk[j] = a.mask[b * a.mask_inner + (e0 + j - b * per) % a.mask_inner];
-                }
-            }
-        }
+        if (blend) mask_read4(a.mask, g, per, a.mask_inner, a.flags & MOCA_DDPM_MASK_C0, a.mask_vec, mk);
         ddpm_coef k = ddpm_load_coef(a, b0);
         int64_t b_cur = b0;
         for (int j = 0; j < cnt; ++j) {
@@ -297,11 +248,7 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const ddpm_args a) {
                 }
             }
             float orig = 0.f;
-            if (a.x0) {
-                float s = k.sac * x0[j];
-                if (use_scale) s = s * k.scale;
-                orig = s + k.s1mac * nq[j];                     // :415-420
-            }
+            if (a.x0) orig = q_sample_orig(x0[j], nq[j], k.sac, k.s1mac, k.scale, use_scale);   // :415-420
             float v = orig;
             rc[j] = mn[j] = qnan;
             if (a.eps_c) {
@@ -311,11 +258,13 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const ddpm_args a) {
                 if (clip) r = r < -1.f ? -1.f : (r > 1.f ? 1.f : r);          // :581 (NaN stays NaN, as clamp_)
                 const float m = k.c1 * r + k.c2 * x[j];                       // :219-222
                 v = m + k.sd * (nz[j] * a.temperature);                       // :601,608
-                if (blend) v = orig * mk[j] + (1.f - mk[j]) * v;              // :648
+                if (blend) v = mask_blend(orig, mk[j], v);                     // :648
                 if (!k.bad) {
                     rc[j] = r;
                     mn[j] = m;
                 }
+            } else if (blend) {
+                v = mask_blend(orig, mk[j], x[j]);                             // the blend alone, in front of a DDIM / solver step
             }
             o[j] = k.bad ? qnan : v;
         }
@@ -406,7 +355,7 @@ extern "C" int moca_ddpm_step_f32(moca_fifo_state* state, const float* x, float*
     if (eps_c) {                                                 // a reverse step: at least one output; the blend wants all three
         if (!x || !(out || x_recon || mean) || (out && !noise)) return MOCA_E_BADARG;
         if (!mask != !x0 || (mask && !out)) return MOCA_E_BADARG;
-    } else if (!x0 || !out || mask || eps_u || x_recon || mean) { // q_sample only
+    } else if (!x0 || !out || eps_u || x_recon || mean || (mask && !x)) {   // q_sample only; with a mask the blend alone, which reads x
         return MOCA_E_BADARG;
     }
     const bool c0 = mask && (flags & MOCA_DDPM_MASK_C0);

@@ -213,6 +213,86 @@ def v2v_dpm_solver_sampling(model, cond, latents=None, frames=None, steps=20, t_
     return images, sampler, samples
 
 
+def latent_mask(mask, latent_shape, factor=8):
+    """the inpainting mask at latent resolution.  A mask whose last two dims are the latents' goes through as it is; one at pixel
+    resolution [.., factor h, factor w] is reduced once, on the host side of the sampler: a latent cell is kept (1) only if ALL of its
+    factor x factor pixels are kept -- a min-pool, so a cell the caller wants partly regenerated is regenerated"""
+    h, w = int(latent_shape[-2]), int(latent_shape[-1])
+    if mask.dim() < 2:
+        raise ValueError(f"mask {tuple(mask.shape)} has no (H, W) dims")
+    if tuple(mask.shape[-2:]) == (h, w):
+        return mask
+    if tuple(mask.shape[-2:]) != (factor * h, factor * w):
+        raise ValueError(f"mask {tuple(mask.shape)}: its last two dims are neither the latents' {(h, w)} nor the pixels' {(factor * h, factor * w)}")
+    lead = tuple(mask.shape[:-2])
+    return mask.to(torch.float32).reshape(lead + (h, factor, w, factor)).amin(dim=(-3, -1))
+
+
+def _inpaint_sampling(sampler, model, cond, mask, latents, frames, n_rows, cfg_scale, uc_emb, x_T, t_start, paste_back, noise, sample_kw,
+                      decode_kw):
+    """the common body of `inpaint_ddim_sampling` and `inpaint_dpm_solver_sampling` on a sampler whose schedule is made"""
+    from .sampler import HostBlend, check_inpaint
+    if (latents is None) == (frames is None):
+        raise ValueError("inpainting wants exactly one of latents= and frames=: the clip whose masked region is kept")
+    if frames is not None:
+        latents = model.encode_first_stage_2DAE(frames.to(model.device))
+    x0 = latents.to(model.device)
+    mask = latent_mask(mask.to(model.device), x0.shape)
+    check_inpaint(x0.shape, mask, x0)
+    if t_start is not None and not 1 <= int(t_start) <= int(n_rows) - 1:
+        raise ValueError(f"t_start = {t_start}: the clip is encoded at schedule index t_start and decoded over t_start rows, "
+                         f"so 1 <= t_start <= {int(n_rows) - 1}")
+    uc = base_uncond(model, cond, x0.shape[0], cfg_scale, uc_emb)
+    if t_start is None:                                       # from noise: `sample`
+        samples, _ = sampler.sample(S=n_rows, conditioning=cond, batch_size=x0.shape[0], shape=tuple(x0.shape[1:]), verbose=False,
+                                    unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc, x_T=x_T, mask=mask, x0=x0,
+                                    **sample_kw)
+    else:                                                     # from the clip itself, noised to row t_start: the v2v path
+        t_start = int(t_start)
+        x_enc = sampler.stochastic_encode(x0, torch.full((x0.shape[0],), t_start, dtype=torch.long), noise=noise)
+        samples = sampler.decode(x_enc, cond, t_start, unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc, mask=mask,
+                                 x0=x0, **decode_kw)
+    sampler.release()
+    if paste_back:
+        samples = HostBlend(model, samples, mask, x0).paste(samples.to(torch.float32).contiguous().clone())
+    images = model.decode_first_stage_2DAE(samples) if getattr(model, "first_stage_model", None) is not None else None
+    return images, sampler, samples
+
+
+def inpaint_ddim_sampling(model, cond, mask, latents=None, frames=None, ddim_steps=50, ddim_eta=0., cfg_scale=1.0, uc_emb=None, x_T=None,
+                          t_start=None, paste_back=True, use_graph=True, noise=None, noises=None, mask_noises=None):
+    """Masked inpainting at DDIM speed: regenerate a clip where `mask == 0` and keep it where `mask == 1`, in `ddim_steps` forwards on
+    the one-graph step (`DDIMSampler.sample` / `decode` with `mask=` / `x0=`: upstream's blend in front of every step).  A mask over
+    frames continues a clip or fills in between kept frames; a mask over pixels inpaints.  Exactly one of `latents` [B,4,T,h,w] and
+    `frames` [B,3,T,H,W] (VAE-encoded first, as in `v2v_ddim_sampling`) is the clip.  `mask` broadcasts against the latents, at latent
+    resolution or at pixel resolution [.., 8h, 8w] (`latent_mask`: a latent cell is kept only if all of its 64 pixels are).
+    `t_start` None: from noise (`x_T` fixes it) over the whole schedule; `t_start` = k: the clip noised to schedule row k
+    (`stochastic_encode`, `noise` fixes that draw) and decoded over k rows, the video-to-video path, 1 <= k <= ddim_steps - 1.
+    The sampler blends before every step and not behind the last, so its kept region is one DDIM step away from the clip;
+    `paste_back` finishes with one launch of the same kernel on the clean row: the kept region of the returned latents then equals the
+    clip's bit for bit.  `noises[i]` / `mask_noises[i]` fix step i's two draws.  Returns (images, sampler, samples) like
+    `base_ddim_sampling`."""
+    sampler = DDIMSampler(model)
+    sampler.use_graph = use_graph
+    sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_eta=ddim_eta, verbose=False)
+    draws = dict(noises=noises, mask_noises=mask_noises)
+    return _inpaint_sampling(sampler, model, cond, mask, latents, frames, ddim_steps, cfg_scale, uc_emb, x_T, t_start, paste_back, noise,
+                             dict(draws, eta=ddim_eta), draws)
+
+
+def inpaint_dpm_solver_sampling(model, cond, mask, latents=None, frames=None, steps=20, order=2, cfg_scale=1.0, uc_emb=None, x_T=None,
+                                t_start=None, paste_back=True, use_graph=True, lower_order_final=True, noise=None, mask_noises=None):
+    """`inpaint_ddim_sampling` with DPM-Solver++(2M) (`DPMSolverSampler`): `steps` schedule rows, the blend in front of every stepped
+    row (the identity rows at the clean end stay unstepped and unblended), q_sample's noise the solver's only draw
+    (`mask_noises[k]` fixes stepped row k's).  Returns (images, sampler, samples) like `base_ddim_sampling`."""
+    sampler = DPMSolverSampler(model, order=order, lower_order_final=lower_order_final)
+    sampler.use_graph = use_graph
+    sampler.make_schedule(ddim_num_steps=steps, verbose=False)
+    draws = dict(mask_noises=mask_noises)
+    return _inpaint_sampling(sampler, model, cond, mask, latents, frames, steps, cfg_scale, uc_emb, x_T, t_start, paste_back, noise,
+                             draws, draws)
+
+
 def refuse_multistep(sampler):
     """the FIFO loops take `DDIMSampler`'s first-order step only"""
     if getattr(sampler, "multistep", False):

@@ -24,7 +24,8 @@ plan's input buffer by one schedule-table row per replay -- `BaseEngine` (DDIM s
 (`p_sample_loop`) -- which owns the one- or two-branch plan, the reset core, the launches around the forward and the shared clauses
 of `supported()`.  Each of the three says beside `supported()` what a built engine is good for (`key`), which is what `EngineCache`
 compares.  `DpmEngine` is `BaseEngine` with the tables and the step of DPM-Solver++(2M) (`dpmpp_tables`): same launches around the
-forward, the multistep bit in the step's flag word, no draw."""
+forward, the multistep bit in the step's flag word, no draw.  Both take `mask=` / `x0=` (inpainting): a masked engine launches
+`moca_ddpm_step_f32` in its blend-only mode on the latents in front of the forward, behind a draw that covers q_sample's noise too."""
 from __future__ import annotations
 
 import contextlib
@@ -517,11 +518,17 @@ class _TrajectoryEngine(_StepEngine):
         self.state = torch.zeros(8, dtype=torch.int32, device=dev)
         return dev, x.numel()
 
+    def _blend_launch(self):
+        """None, or `blend(lib, state, stream)`: what a masked engine launches on the latents in front of the forward"""
+        return None
+
     def _wrap_step(self, draw, step):
         """the launch sequence of one replay: [timestep rows of table row S - 1 - iter; the Philox draws over the buffer `draw`, None:
-        nothing is drawn] + the UNet forward + [`step(lib, state, eps_c, eps_u, stream)`: the engine's step kernel on the conditional
-        rows of `plan.out` and the unconditional ones, NULL without guidance]"""
+        nothing is drawn; on a masked engine the blend of `_blend_launch`, behind the draw] + the UNet forward + [`step(lib, state,
+        eps_c, eps_u, stream)`: the engine's step kernel on the conditional rows of `plan.out` and the unconditional ones, NULL without
+        guidance]"""
         lib, plan, B = _l.load(), self.plan, self.shape[0]
+        blend = self._blend_launch()
         eps = plan.out.reshape((2 if self.guided else 1) * B, -1)
         st_ = _l.ptr(self.state)
         S_ = lambda: C.c_void_p(ops.current_stream())
@@ -530,6 +537,8 @@ class _TrajectoryEngine(_StepEngine):
             _l.check(lib.moca_base_set_timestep(st_, _l.ptr(self.t_table), self.S, _l.ptr(plan.t_rows), plan.t_rows.numel(), S_()), "moca_base_set_timestep")
             if draw is not None:
                 _l.check(lib.moca_fifo_randn_f32(st_, _l.ptr(draw), draw.numel(), S_()), "moca_fifo_randn_f32")
+            if blend is not None:
+                blend(lib, st_, S_())
 
         def post():
             step(lib, st_, _l.ptr(eps[:B]), _l.ptr(eps[B:]) if self.guided else None, S_())
@@ -585,7 +594,14 @@ class BaseEngine(_TrajectoryEngine):
     `n_rows` (default: the whole schedule) builds the tables over the FIRST n_rows schedule rows, so that the S of the captured kernels
     is n_rows and step i uses row n_rows - 1 - i: `DDIMSampler.decode(x, c, t_start)` (ddim.py:674-692) is this engine with
     n_rows = t_start.  `encode` noises a clean latent into the plan's input buffer (`stochastic_encode`, ddim.py:652-671) with the
-    tables of the WHOLE schedule, so a video-to-video run is reset -> encode(x0, t_start) -> t_start steps, all on the device."""
+    tables of the WHOLE schedule, so a video-to-video run is reset -> encode(x0, t_start) -> t_start steps, all on the device.
+
+    `mask=` / `x0=` build a MASKED engine (inpainting, upstream's DDIM loop): in front of the forward of every step, behind the draws,
+    `moca_ddpm_step_f32` in its blend-only mode (no eps) rewrites the latents in place, x = q_sample(x0, t_row) mask + (1 - mask) x:
+    the kernel gathers the model's own q_sample tables at the plan's timestep rows, which the launch before it wrote, so the blend
+    follows `n_rows` and `set_schedule` by itself.  Fresh q-noise every step: the step's Philox launch covers
+    [noise | pad to 16 B | noise_q], as `DdpmEngine`'s.  `mask` and `x0` live on the device, written by `reset`.  Nothing is blended
+    behind the last step.  An unmasked engine records exactly the launches it recorded before there was a mask."""
 
     @staticmethod
     def supported(model, x, cond, uc, scale, features_adapter=None):
@@ -611,16 +627,18 @@ class BaseEngine(_TrajectoryEngine):
         return _TrajectoryEngine._supports_crossattn(model, [cond, uc])
 
     @staticmethod
-    def key(sampler, x, cond, uc, cfg_scale, features_adapter=None, n_rows=None):
+    def key(sampler, x, cond, uc, cfg_scale, features_adapter=None, n_rows=None, mask=None):
         """what an engine built by `BaseEngine(model, sampler, x, cond, uc, cfg_scale, ...)` is good for: everything the plan and the
         captured launches bake in -- latent shape, context lengths, scale, the schedule's timesteps and sigmas, device, `c_concat`
-        channel counts, adapter map shapes and the table rows (`n_rows` keeps `decode`'s engine and `sample`'s apart)"""
+        channel counts, adapter map shapes, the table rows (`n_rows` keeps `decode`'s engine and `sample`'s apart) and whether and how
+        a mask is read (`mask_kind`, None without one)"""
         return (tuple(x.shape), n_ctx(cond), n_ctx(uc), float(cfg_scale), sampler.ddim_timesteps.tobytes(),
                 np.asarray(sampler.ddim_sigmas).tobytes(), str(x.device), tuple(int(c.shape[1]) for c in cond.get("c_concat") or ()),
                 None if features_adapter is None else tuple(tuple(f.shape) for f in features_adapter),
-                len(sampler.ddim_timesteps) if n_rows is None else int(n_rows))
+                len(sampler.ddim_timesteps) if n_rows is None else int(n_rows), None if mask is None else mask_kind(mask, x.shape))
 
-    def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, keep_pred_x0=False, features_adapter=None, n_rows=None):
+    def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, keep_pred_x0=False, features_adapter=None, n_rows=None, mask=None,
+                 x0=None):
         S = len(sampler.ddim_timesteps) if n_rows is None else int(n_rows)
         if not 1 <= S <= len(sampler.ddim_timesteps):
             raise ValueError(f"n_rows = {n_rows}: the schedule has {len(sampler.ddim_timesteps)} rows")
@@ -639,10 +657,52 @@ class BaseEngine(_TrajectoryEngine):
         self.model = model
         self._reinit_bufs = None                             # `reinit` (FreeInit): made by its first call
         self._reinit_src = (None, None)
-        self.noise = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._open_mask(x, mask, x0)
+        n_pad = (n + 3) // 4 * 4                             # q_sample's draw starts 16-byte aligned
+        draw = torch.zeros(n_pad + n if self.masked else n, dtype=torch.float32, device=dev)
+        self.noise = draw[:n]                                # (what `encode` and `reinit` draw into, too)
+        self.noise_q = draw[n_pad:] if self.masked else None
         self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev) if keep_pred_x0 else None
-        self.reset(x, cond, uc, seed, features_adapter=features_adapter)
-        self._wrap_ddim_step(self.noise, self.noise, cfg_scale, bool(sampler.use_scale))
+        self.reset(x, cond, uc, seed, features_adapter=features_adapter, mask=mask, x0=x0)
+        self._wrap_ddim_step(draw, self.noise, cfg_scale, bool(sampler.use_scale))
+
+    def _open_mask(self, x, mask, x0):
+        """(constructor) the buffers of a masked engine: the mask as the kernel reads it and x0, both filled by `reset`; the blend reads
+        the model's DDPM table (`sqrt_alphas_cumprod`, `sqrt_one_minus_alphas_cumprod`, `scale_arr` per timestep)"""
+        if (mask is None) != (x0 is None):
+            raise ValueError("mask= and x0= go together: the mask says where x0 is kept")
+        self.masked = mask is not None
+        self.mask = self.x0 = None
+        self.mask_inner = self.blend_flags = 0
+        if self.masked:
+            m, mflag, self.mask_inner = mask_operand(mask, x.shape, self.device)
+            self.blend_flags = mflag | self.model._ddpm_flags(x0_param=False)
+            self.mask = torch.empty_like(m)
+            self.x0 = torch.empty(x.numel(), dtype=torch.float32, device=self.device)
+            self.blend_coef = self.model._ddpm_dev(self.device)["coef"]
+
+    def _blend_launch(self):
+        if not self.masked:
+            return None
+        plan, (B, T), n = self.plan, (self.shape[0], self.shape[2]), self.x0.numel()
+        # (state NULL: the counter is the step kernel's to advance; t = the timestep rows, row stride = frames, as DdpmEngine reads them)
+        return lambda lib, st_, stream: _l.check(lib.moca_ddpm_step_f32(
+            None, _l.ptr(plan.x_in), _l.ptr(plan.x_in), None, None, None, None, None, _l.ptr(self.mask), _l.ptr(self.x0), _l.ptr(self.noise_q),
+            _l.ptr(self.blend_coef), _l.ptr(plan.t_rows), T, B, int(self.blend_coef.shape[0]), n // B, self.mask_inner, 1.0, 1.0,
+            self.blend_flags, stream), "moca_ddpm_step_f32")
+
+    def _checked_mask(self, mask, x0):
+        """(`reset`, before anything is enqueued) `DdpmEngine.reset`'s validation -> the mask as the kernel reads it, None unmasked"""
+        if (mask is not None) != self.masked or (x0 is not None) != self.masked:
+            raise ValueError("mask and x0 go with an engine built for them")
+        if not self.masked:
+            return None
+        m, _, inner = mask_operand(mask, self.shape, self.device)
+        if m.shape != self.mask.shape or inner != self.mask_inner:
+            raise ValueError(f"mask {tuple(mask.shape)} is read another way than the mask the engine was built with")
+        if tuple(x0.shape) != self.shape:
+            raise ValueError(f"x0 {tuple(x0.shape)} does not match the engine's latents {self.shape}")
+        return m
 
     @staticmethod
     def _schedule_tables(sampler, n_rows):
@@ -738,13 +798,18 @@ class BaseEngine(_TrajectoryEngine):
         for i, v in enumerate((0, it, seed & 0xffffffff, (seed >> 32) & 0xffffffff, 0)):
             st[i:i + 1].fill_(v - (1 << 32) if v >= 1 << 31 else v)
 
-    def reset(self, x, cond, uc, seed=0, features_adapter=None):
-        """start a new trajectory on the same plan: latents x_T, contexts, fps, adapter maps, iteration 0, a new noise stream; the
-        engine's own schedule, should `set_schedule` have replaced it"""
+    def reset(self, x, cond, uc, seed=0, features_adapter=None, mask=None, x0=None):
+        """start a new trajectory on the same plan: latents x_T, contexts, fps, adapter maps, iteration 0, a new noise stream; on a
+        masked engine `mask` (read the way the engine's mask is) and `x0`; the engine's own schedule, should `set_schedule` have
+        replaced it"""
         plan = self.plan
         if (features_adapter is None) != (plan.adapter_in is None):
             raise ValueError("features_adapter goes with an engine built for it")
+        m = self._checked_mask(mask, x0)
         with self._restart(x, cond, uc, seed, fps=(16, 16) if self.hybrid else None):
+            if m is not None:
+                self.mask.copy_(m)
+                self.x0.copy_(x0.reshape(-1).to(self.device, torch.float32))
             if self._schedule_set:                               # (the built tables end at row S - 1: the counter stays at 0)
                 self._write_schedule(*self._built)
                 self.enc_coef, self._schedule_set = self._built_enc, False
@@ -784,11 +849,15 @@ class BaseEngine(_TrajectoryEngine):
         src.record_stream(plan.stream)
         t_d.record_stream(plan.stream)
 
-    def step(self, noise=None):
-        """one DDIM step (enqueued, not synchronised); `noise` [B,C,T,H,W] fixes the draw"""
+    def step(self, noise=None, mask_noise=None):
+        """one DDIM step (enqueued, not synchronised); `noise` [B,C,T,H,W] fixes the draw and, on a masked engine, `mask_noise`
+        q_sample's (both or neither: one flag tells the Philox launch that the host filled the buffer)"""
+        if (mask_noise is not None) != (self.masked and noise is not None):
+            raise ValueError("a masked engine takes the step's two draws together, noise and mask_noise, or neither; an unmasked one "
+                             "has no mask_noise")
         with self._step():
             if noise is not None:
-                self._fix_noise((self.noise, noise))
+                self._fix_noise((self.noise, noise), *([(self.noise_q, mask_noise)] if self.masked else []))
 
 
 class DpmEngine(BaseEngine):
@@ -798,7 +867,9 @@ class DpmEngine(BaseEngine):
     differs:
 
       * nothing is drawn in a step: no `moca_fifo_randn_f32` launch, `step()` takes no noise.  The step kernel's noise operand (not
-        read) is the buffer `encode` and `reinit` draw into;
+        read) is the buffer `encode` and `reinit` draw into.  The one exception is a MASKED engine (`mask=` / `x0=`, as `BaseEngine`'s):
+        the blend in front of every stepped row needs q_sample's noise, so its Philox launch covers `noise_q` alone and
+        `step(mask_noise=)` fixes that draw;
       * `pred_x0` is always allocated: it is the solver's history, read and rewritten by the step kernel.  Nothing resets it: the first
         stepped row of every table has c_1 = 0 and does not read it, and every trajectory (after `reset`, `encode`, `reinit`,
         `set_schedule`) starts on the first row of its table;
@@ -815,7 +886,7 @@ class DpmEngine(BaseEngine):
                 and _TrajectoryEngine._supports_crossattn(model, [cond]))
 
     @staticmethod
-    def key(sampler, x, cond, uc, cfg_scale, features_adapter=None, n_rows=None):
+    def key(sampler, x, cond, uc, cfg_scale, features_adapter=None, n_rows=None, mask=None):
         """what an engine built by `DpmEngine(model, sampler, x, cond, uc, cfg_scale, ...)` is good for: `BaseEngine.key`'s entries behind a
         leading "dpmpp" (both share a cache), with the solver's order and `lower_order_final` and the scale bit of the flag word where
         that key holds the sigmas, and no unconditional entries without guidance"""
@@ -824,9 +895,9 @@ class DpmEngine(BaseEngine):
                 sampler.ddim_timesteps.tobytes(), (int(sampler.order), bool(sampler.lower_order_final), bool(sampler.use_scale)),
                 str(x.device), tuple(int(c.shape[1]) for c in cond.get("c_concat") or ()),
                 None if features_adapter is None else tuple(tuple(f.shape) for f in features_adapter),
-                len(sampler.ddim_timesteps) if n_rows is None else int(n_rows))
+                len(sampler.ddim_timesteps) if n_rows is None else int(n_rows), None if mask is None else mask_kind(mask, x.shape))
 
-    def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, features_adapter=None, n_rows=None):
+    def __init__(self, model, sampler, x, cond, uc, cfg_scale, seed=0, features_adapter=None, n_rows=None, mask=None, x0=None):
         S = len(sampler.ddim_timesteps) if n_rows is None else int(n_rows)
         if not 1 <= S <= len(sampler.ddim_timesteps):
             raise ValueError(f"n_rows = {n_rows}: the schedule has {len(sampler.ddim_timesteps)} rows")
@@ -847,10 +918,12 @@ class DpmEngine(BaseEngine):
         self._reinit_src = (None, None)
         self.noise = torch.zeros(n, dtype=torch.float32, device=dev)           # the draws of `encode` / `reinit`; no step reads it
         self.pred_x0 = torch.empty(n, dtype=torch.float32, device=dev)         # the history
-        self.reset(x, cond, uc if guided else None, seed, features_adapter=features_adapter)
+        self._open_mask(x, mask, x0)
+        self.noise_q = torch.zeros(n, dtype=torch.float32, device=dev) if self.masked else None
+        self.reset(x, cond, uc if guided else None, seed, features_adapter=features_adapter, mask=mask, x0=x0)
         plan = self.plan
         flags = _l.MOCA_BASE_MULTISTEP | (_l.MOCA_BASE_SCALE if sampler.use_scale else 0)
-        self._wrap_step(None, lambda lib, st_, eps_c, eps_u, stream: _l.check(lib.moca_base_ddim_step_f32(
+        self._wrap_step(self.noise_q, lambda lib, st_, eps_c, eps_u, stream: _l.check(lib.moca_base_ddim_step_f32(
             st_, _l.ptr(plan.x_in), eps_c, eps_u, _l.ptr(self.noise), _l.ptr(self.pred_x0), _l.ptr(self.coef), self.S, float(cfg_scale),
             flags, n, stream), "moca_base_ddim_step_f32"))
 
@@ -864,12 +937,16 @@ class DpmEngine(BaseEngine):
 
     n_stepped = property(lambda self: self.end_iter - self.it0, doc="the steps of a trajectory over the current schedule")
 
-    def step(self):
-        """one solver step (enqueued, not synchronised)"""
+    def step(self, mask_noise=None):
+        """one solver step (enqueued, not synchronised); on a masked engine `mask_noise` [B,C,T,H,W] fixes q_sample's draw"""
         if self.n_iter >= self.end_iter:
             raise ValueError(f"the schedule has {self.n_stepped} stepped rows: step {self.n_iter - self.it0} would run past the clean end")
+        if mask_noise is not None and not self.masked:
+            raise ValueError("mask_noise goes with a masked engine: an unmasked solver step draws nothing")
         with self._step():
-            pass
+            if mask_noise is not None:
+                self._fix_noise((self.noise_q, mask_noise))
+
 
 class InvertEngine(_TrajectoryEngine):
     """One step of deterministic DDIM inversion (`DDIMSampler.encode`) as ONE hipGraph: [timestep rows of step i] + the UNet forward +

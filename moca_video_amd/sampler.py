@@ -12,7 +12,9 @@ Differences from the reference, all explicit:
   * the Grounded-SAM-2 mask producer (ddim.py:713-969) is out of scope: masks come in as
     tensors (`davis_masks`), no debug PNG/matplotlib dumps are written (:432-554,611-641);
   * the two CFG branches are evaluated as ONE batched UNet call when their contexts have
-    the same length (bit-equivalent: every UNet op is per-sample).
+    the same length (bit-equivalent: every UNet op is per-sample);
+  * `sample` / `decode` implement `mask=` / `x0=`, which the reference declares (ddim.py:109-190) and never reads: the blend of the
+    upstream latent-diffusion DDIM loop in front of every step (`moca_ddpm_step_f32` without eps: the blend alone).
 """
 from __future__ import annotations
 
@@ -26,7 +28,7 @@ from . import lib as _l
 from . import ops
 from .conditioning import _f32c, check_schedule_index, cond_image_rows, guidance_eps
 from .fifo_graph import (BaseEngine, DpmEngine, EngineCache, InvertEngine, ddim_coef, dpm_stepped_rows, dpmpp_tables, invert_coef,
-                         state_block)
+                         mask_operand, state_block)
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
@@ -94,6 +96,56 @@ def noise_queue(z, alphas_per_frame, frame_index, noises):
     _l.check(_l.load().moca_fifo_prepare_queue_f32(_l.ptr(z), _l.ptr(noise), _l.ptr(out), _l.ptr(cz), _l.ptr(cn), _l.ptr(fi), b * c, tz, Q,
                                                    h * w, _st()), "moca_fifo_prepare_queue_f32")
     return out
+
+
+def check_inpaint(shape, mask, x0):
+    """the argument contract of masked sampling over latents of `shape`: `mask` and `x0` come together, `x0` has the latents' shape,
+    `mask` broadcasts against them (ValueError otherwise) -> whether the call is masked"""
+    if (mask is None) != (x0 is None):
+        raise ValueError("mask= and x0= go together: the mask says where x0 is kept (mask == 1) and where the sampler regenerates")
+    if mask is None:
+        return False
+    shape = tuple(int(v) for v in shape)
+    if tuple(x0.shape) != shape:
+        raise ValueError(f"x0 {tuple(x0.shape)} does not have the latents' shape {shape}")
+    ms = tuple(mask.shape)
+    if len(ms) > len(shape) or any(m not in (1, v) for m, v in zip(ms[::-1], shape[::-1])):
+        raise ValueError(f"mask {ms} does not broadcast against the latents {shape}")
+    return True
+
+
+class HostBlend:
+    """The inpainting blend of the host-issued loops and of paste-back: `moca_ddpm_step_f32` without eps, the launch the masked step
+    engines replay -- one kernel serves both, no torch arithmetic on latents.  `blend(x, timestep, noise_q)` rewrites x IN PLACE:
+    x = q_sample(x0, timestep) mask + (1 - mask) x over the model's own DDPM table, `noise_q` None: drawn from the host generator.
+    `blend.paste(x)` is the same launch on a private clean row (sac 1, s1mac 0, scale 1): orig = 1 x0 + 0 noise is x0 exactly, so
+    where mask == 1 the result equals x0 bit for bit."""
+
+    def __init__(self, model, x, mask, x0):
+        dev = x.device
+        self.model = model
+        self.mask, self.mflag, self.inner = mask_operand(mask, x.shape, dev)
+        self.x0 = _f32c(x0.to(dev))
+
+    def _launch(self, x, coef, t, noise_q, flags):
+        from .ddpm import launch_ddpm_step
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+            raise ValueError("the blend runs in place on contiguous fp32 cuda latents")
+        B = x.shape[0]
+        launch_ddpm_step(coef, t, B=B, per=x.numel() // B, x=x, out=x, mask=self.mask, x0=self.x0, noise_q=noise_q, mask_inner=self.inner,
+                         flags=flags | self.mflag, t_stride=0)
+        return x
+
+    def __call__(self, x, timestep, noise_q=None):
+        noise_q = torch.randn_like(x) if noise_q is None else _f32c(noise_q.to(x.device))        # q_sample's default draw, ddpm3d.py:413
+        if noise_q.shape != x.shape:
+            raise ValueError(f"mask noise {tuple(noise_q.shape)} does not match the latents {tuple(x.shape)}")
+        t = torch.full((1,), int(timestep), dtype=torch.int64, device=x.device)
+        return self._launch(x, self.model._ddpm_dev(x.device)["coef"], t, noise_q, self.model._ddpm_flags(x0_param=False))
+
+    def paste(self, x):
+        clean = torch.tensor([[0., 0., 0., 0., 0., 1., 0., 1.]], device=x.device)
+        return self._launch(x, clean, torch.zeros(1, dtype=torch.int64, device=x.device), torch.zeros_like(x), 0)
 
 
 class DDIMSampler(object):
@@ -173,13 +225,14 @@ class DDIMSampler(object):
             x.numel(), _st()), "moca_ddim_update_f32")
         return x_prev, pred_x0
 
-    def _engine_for(self, img, cond, uc, scale, seed, n_rows, features_adapter=None):
+    def _engine_for(self, img, cond, uc, scale, seed, n_rows, features_adapter=None, mask=None, x0=None):
         """the cached step graph (fifo_graph.BaseEngine) for this call, reset to a new trajectory; built when `BaseEngine.key` changes.
-        `n_rows`: the rows of the schedule tables the captured kernels index (all of them for `sample`, the first t_start for `decode`)"""
-        return self._engines.get(BaseEngine.key(self, img, cond, uc, scale, features_adapter, n_rows),
+        `n_rows`: the rows of the schedule tables the captured kernels index (all of them for `sample`, the first t_start for `decode`);
+        `mask` / `x0`: a masked engine (another mask that is read the same way reuses it)"""
+        return self._engines.get(BaseEngine.key(self, img, cond, uc, scale, features_adapter, n_rows, mask),
                                  lambda: BaseEngine(self.model, self, img, cond, uc, scale, seed=seed, features_adapter=features_adapter,
-                                                    n_rows=n_rows),
-                                 lambda eng: eng.reset(img, cond, uc, seed, features_adapter=features_adapter))
+                                                    n_rows=n_rows, mask=mask, x0=x0),
+                                 lambda eng: eng.reset(img, cond, uc, seed, features_adapter=features_adapter, mask=mask, x0=x0))
 
     _base_engine = property(lambda self: self._engines.entry, doc="None, or the (key, engine) of the cached step graph")
 
@@ -187,20 +240,29 @@ class DDIMSampler(object):
         """free the cached step graph of `sample` (plan buffers + hipGraph)"""
         self._engines.release()
 
-    def _run_steps(self, x, cond, uc, scale, n_steps, noises, use_graph, features_adapter=None):
+    def _run_steps(self, x, cond, uc, scale, n_steps, noises, use_graph, features_adapter=None, mask=None, x0=None, mask_noises=None):
         """the loop of `sample` and `decode`: n_steps calls of p_sample_ddim over `ddim_timesteps[:n_steps]` flipped -- step i at schedule
         index n_steps - 1 - i, `noises[i]` fixing its draw -- as one hipGraph per step (fifo_graph.BaseEngine: latents, schedule and
-        noise stay on the device) where `use_graph` and `BaseEngine.supported` allow it, else host-issued"""
+        noise stay on the device) where `use_graph` and `BaseEngine.supported` allow it, else host-issued.  With `mask` / `x0`
+        (`check_inpaint` has seen them) every step starts with upstream's blend, x = q_sample(x0, t) mask + (1 - mask) x, `mask_noises[i]`
+        fixing its draw: inside the masked engine's graph, or `HostBlend` in front of the host-issued step."""
         noise = lambda i: None if noises is None else noises[i]
+        mask_noise = lambda i: None if mask_noises is None else mask_noises[i]
         if n_steps > 0 and use_graph and self.share_prefix and BaseEngine.supported(self.model, x, cond, uc, scale,
                                                                                     features_adapter=features_adapter):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())                  # the host generator seeds the device stream
-            eng = self._engine_for(x, cond, uc, scale, seed, n_steps, features_adapter=features_adapter)
+            eng = self._engine_for(x, cond, uc, scale, seed, n_steps, features_adapter=features_adapter, mask=mask, x0=x0)
             for i in range(n_steps):
-                eng.step(noise=noise(i))
+                eng.step(noise=noise(i), **({} if mask is None else {"mask_noise": mask_noise(i)}))
             return eng.latents().to(x.dtype)
         unet_kwargs = {} if features_adapter is None else {"features_adapter": list(features_adapter)}
+        blend = None
+        if mask is not None and n_steps > 0:
+            x = _f32c(x).clone()                                                 # (the blend runs in place: the caller keeps x_T)
+            blend = HostBlend(self.model, x, mask, x0)
         for i, step in enumerate(np.flip(self.ddim_timesteps[:n_steps])):
+            if blend is not None:
+                x = blend(_f32c(x), int(step), mask_noise(i))
             ts = torch.full((x.shape[0],), int(step), device=x.device, dtype=torch.long)
             x, _ = self.p_sample_ddim(x, cond, ts, index=n_steps - i - 1, use_original_steps=False, unconditional_guidance_scale=scale,
                                       unconditional_conditioning=uc, noise=noise(i), **unet_kwargs)
@@ -209,19 +271,26 @@ class DDIMSampler(object):
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, eta=0., x_T=None, verbose=False,
                unconditional_guidance_scale=1., unconditional_conditioning=None, latents_dir=None, noises=None,
-               features_adapter=None, **kwargs):
+               features_adapter=None, mask=None, x0=None, mask_noises=None, **kwargs):
         """ddim.py:109-181 -> ddim_sampling (:183-252): the base 'N DDIM steps, single prompt' loop.  `features_adapter` (a list of
         maps, entry k [batch*T, C_k, h_k, w_k]) is what the reference's `sample(**kwargs)` hands down to `apply_model` and the UNet
-        (openaimodel3d.py:562-567): constant over the trajectory, the same for both guidance branches."""
+        (openaimodel3d.py:562-567): constant over the trajectory, the same for both guidance branches.
+
+        `mask` / `x0`: masked inpainting as upstream's latent-diffusion DDIM loop has it (the reference declares both and never reads
+        the mask): before the model call of every step, at the step's timestep t,
+        `img = model.q_sample(x0, t) * mask + (1 - mask) * img` -- mask == 1 keeps x0, fresh q-noise every step (`mask_noises[i]` fixes
+        step i's), nothing blended behind the last step, so the kept region of the result is one DDIM step away from x0 (pasting
+        back is the driver's job, `fifo.inpaint_ddim_sampling`).  `x0` has the latents' shape, `mask` broadcasts against them."""
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         size = (batch_size,) + tuple(shape)
+        check_inpaint(size, mask, x0)
         device = self.model.betas.device
         img = torch.randn(size, device=device) if x_T is None else x_T
         if latents_dir is not None:
             torch.save(img, f"{latents_dir}/0.pt")                    # :233-234
         total_steps = self.ddim_timesteps.shape[0]
         img = self._run_steps(img, conditioning, unconditional_conditioning, unconditional_guidance_scale, total_steps, noises, self.use_graph,
-                              features_adapter=features_adapter)
+                              features_adapter=features_adapter, mask=mask, x0=x0, mask_noises=mask_noises)
         if latents_dir is not None:
             torch.save(img, f"{latents_dir}/{total_steps}.pt")        # :249-250
         return img, {}
@@ -239,6 +308,7 @@ class DDIMSampler(object):
         start, `BaseEngine.set_schedule` where the step count changes (no new capture), `BaseEngine.reinit` between trajectories (latents,
         initial noise, filter and fresh noise stay on the device), one read-back at the end -- one per trajectory with `return_all`.
         Elsewhere the same loop is composed on the host from `freeinit_reinit` and host-issued steps.
+        Takes no `mask=` / `x0=`: masked inpainting across re-initialised trajectories is out of scope (`sample` and `decode` have it).
         Returns (samples of the last trajectory, the list of every trajectory's samples or None)."""
         from .freeinit import freeinit_reinit
         steps = [int(s) for s in steps]
@@ -315,18 +385,20 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False, noises=None, use_graph=None):
+               use_original_steps=False, noises=None, use_graph=None, mask=None, x0=None, mask_noises=None):
         """ddim.py:674-692: `t_start` calls of p_sample_ddim (temperature 1, fresh noise per step) over `ddim_timesteps[:t_start]`
         flipped -- step i at schedule index t_start - 1 - i -- returning the latents only.  `noises[i]` fixes step i's draw; `use_graph`
         (default: `self.use_graph`) as in `sample`: where `BaseEngine.supported` holds, one hipGraph per step on an engine over the first
-        t_start rows of the schedule tables, else (no guidance pair among the rest) the host-issued p_sample_ddim loop."""
+        t_start rows of the schedule tables, else (no guidance pair among the rest) the host-issued p_sample_ddim loop.  `mask` / `x0` /
+        `mask_noises`: `sample`'s blend in front of every step."""
+        check_inpaint(x_latent.shape, mask, x0)
         if use_original_steps:
             raise NotImplementedError(
                 "decode(use_original_steps=True) cannot run in the reference: p_sample_ddim reads self.model.ddim_sigmas_for_original_num_steps "
                 "(ddim.py:325), which exists only on the sampler, and self.model.scale_arr_prev (ddim.py:352), which is never registered")
         n_steps = self.ddim_timesteps[:t_start].shape[0]              # :677-678 (numpy slicing: a t_start past the schedule is the whole of it)
         return self._run_steps(x_latent, cond, unconditional_conditioning, unconditional_guidance_scale, n_steps, noises,
-                               self.use_graph if use_graph is None else use_graph)
+                               self.use_graph if use_graph is None else use_graph, mask=mask, x0=x0, mask_noises=mask_noises)
 
     def _invert_engine_for(self, x0, cond, uc, scale):
         """the cached step graph of `encode` (fifo_graph.InvertEngine) reset to the clip `x0`; built when `InvertEngine.key` changes.  It
@@ -633,7 +705,9 @@ class DPMSolverSampler(DDIMSampler):
     A trajectory over n schedule rows steps all but the identity rows at the clean end (`uniform` schedules have one, at timestep 0:
     one forward fewer than DDIM), first order on its first step and -- `lower_order_final` -- on its last, second order between them
     (`order` 1: first order throughout, which is DDIM at eta 0).  The solver is deterministic: `eta` other than 0, `noises=` and a
-    temperature other than 1 are refused, nothing is drawn.  `p_sample_ddim`, `ddim_step`, `fifo_onestep`, `encode`,
+    temperature other than 1 are refused, nothing is drawn -- but for masked inpainting (`mask=` / `x0=` of `sample` and `decode`),
+    whose blend in front of every stepped row draws q_sample's noise (`mask_noises=` fixes it); the identity rows at the clean end stay
+    unstepped and unblended.  `p_sample_ddim`, `ddim_step`, `fifo_onestep`, `encode`,
     `stochastic_encode` are the parent's; FIFO / MoCA sampling refuses this sampler (`multistep`): diagonal denoising holds one frame
     per schedule level and moves each by one level per iteration, which ties the queue length to first-order steps."""
     multistep = True
@@ -656,13 +730,13 @@ class DPMSolverSampler(DDIMSampler):
         if temperature != 1.:
             raise ValueError(f"temperature = {temperature}: DPM-Solver++ draws nothing, there is no step noise to scale")
 
-    def _dpm_engine_for(self, img, cond, uc, scale, seed, n_rows, features_adapter=None):
+    def _dpm_engine_for(self, img, cond, uc, scale, seed, n_rows, features_adapter=None, mask=None, x0=None):
         """the cached step graph (fifo_graph.DpmEngine) for this call, reset to a new trajectory; built when `DpmEngine.key` changes.  It
         shares the one-entry cache of the parent's engines."""
-        return self._engines.get(DpmEngine.key(self, img, cond, uc, scale, features_adapter, n_rows),
+        return self._engines.get(DpmEngine.key(self, img, cond, uc, scale, features_adapter, n_rows, mask),
                                  lambda: DpmEngine(self.model, self, img, cond, uc, scale, seed=seed, features_adapter=features_adapter,
-                                                   n_rows=n_rows),
-                                 lambda eng: eng.reset(img, cond, uc, seed, features_adapter=features_adapter))
+                                                   n_rows=n_rows, mask=mask, x0=x0),
+                                 lambda eng: eng.reset(img, cond, uc, seed, features_adapter=features_adapter, mask=mask, x0=x0))
 
     def _on_graph(self, x, cond, uc, scale, use_graph, features_adapter):
         """-> (whether the call runs on `DpmEngine`, its unconditional branch: None without guidance)"""
@@ -671,16 +745,20 @@ class DPMSolverSampler(DDIMSampler):
         return bool(use_graph and (self.share_prefix or not guided)
                     and DpmEngine.supported(self.model, x, cond, uc, scale, features_adapter=features_adapter)), uc
 
-    def _steps_host(self, x, cond, uc, scale, n_rows, features_adapter=None):
-        """the host-issued trajectory over the first `n_rows` schedule rows: per stepped row `guidance_eps` + `cfg_combine`, then the
-        engine's step launch on a private 32-byte state block, the device table and a history buffer (eps_u NULL: eps is combined)"""
+    def _steps_host(self, x, cond, uc, scale, n_rows, features_adapter=None, mask=None, x0=None, mask_noises=None):
+        """the host-issued trajectory over the first `n_rows` schedule rows: per stepped row [with a mask, `HostBlend` at the row's
+        timestep,] `guidance_eps` + `cfg_combine`, then the engine's step launch on a private 32-byte state block, the device table and
+        a history buffer (eps_u NULL: eps is combined)"""
         coef, t_table = dpmpp_tables(self, n_rows, self.order, self.lower_order_final)
         x = _f32c(x).clone()                                  # (the step kernel updates in place: the caller keeps x_T)
         dev = x.device
         state, coef_d, hist = state_block(0).to(dev), coef.to(dev), torch.empty_like(x)
         flags = _l.MOCA_BASE_MULTISTEP | (_l.MOCA_BASE_SCALE if self.use_scale else 0)
         unet_kwargs = {} if features_adapter is None else {"features_adapter": list(features_adapter)}
+        blend = None if mask is None else HostBlend(self.model, x, mask, x0)
         for k in range(dpm_stepped_rows(coef)):
+            if blend is not None:
+                blend(x, int(t_table[n_rows - 1 - k]), None if mask_noises is None else mask_noises[k])
             ts = torch.full((x.shape[0],), int(t_table[n_rows - 1 - k]), device=dev, dtype=torch.long)
             e_t = _f32c(self._cfg_eps(x, ts, cond, uc, scale, **unet_kwargs))
             # (noise: required, not read)
@@ -688,30 +766,34 @@ class DPMSolverSampler(DDIMSampler):
                                                        n_rows, 1.0, flags, x.numel(), _st()), "moca_base_ddim_step_f32")
         return x
 
-    def _run_steps(self, x, cond, uc, scale, n_steps, noises, use_graph, features_adapter=None):
+    def _run_steps(self, x, cond, uc, scale, n_steps, noises, use_graph, features_adapter=None, mask=None, x0=None, mask_noises=None):
         """the loop of `sample` and `decode`: the stepped rows among `ddim_timesteps[:n_steps]`, flipped, on `DpmEngine` where `use_graph`
-        and `DpmEngine.supported` allow it, else host-issued"""
+        and `DpmEngine.supported` allow it, else host-issued; with `mask` / `x0` the blend in front of every stepped row"""
         self._refuse_draws(noises)
         if n_steps <= 0:
             return x
         graph, uc_g = self._on_graph(x, cond, uc, scale, use_graph, features_adapter)
         if graph:
-            eng = self._dpm_engine_for(x, cond, uc_g, scale, 0, n_steps, features_adapter=features_adapter)
-            for _ in range(eng.n_stepped):
-                eng.step()
+            # (an unmasked trajectory draws nothing: seed 0; a masked one seeds its q-noise stream from the host generator)
+            seed = 0 if mask is None or mask_noises is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+            eng = self._dpm_engine_for(x, cond, uc_g, scale, seed, n_steps, features_adapter=features_adapter, mask=mask, x0=x0)
+            for k in range(eng.n_stepped):
+                eng.step(**({} if mask is None else {"mask_noise": None if mask_noises is None else mask_noises[k]}))
             return eng.latents().to(x.dtype)
-        return self._steps_host(x, cond, uc, scale, n_steps, features_adapter=features_adapter).to(x.dtype)
+        return self._steps_host(x, cond, uc, scale, n_steps, features_adapter=features_adapter, mask=mask, x0=x0,
+                                mask_noises=mask_noises).to(x.dtype)
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, eta=0., x_T=None, verbose=False,
                unconditional_guidance_scale=1., unconditional_conditioning=None, latents_dir=None, noises=None,
-               features_adapter=None, **kwargs):
-        """`DDIMSampler.sample` with the solver's steps: S schedule rows, S - 1 forwards on a `uniform` schedule"""
+               features_adapter=None, mask=None, x0=None, mask_noises=None, **kwargs):
+        """`DDIMSampler.sample` with the solver's steps: S schedule rows, S - 1 forwards on a `uniform` schedule.  `mask` / `x0`: the
+        parent's blend in front of every stepped row, `mask_noises[k]` fixing stepped row k's q-noise (`noises=` stays refused)"""
         self._refuse_draws(noises, kwargs.get("temperature", 1.))
         return super().sample(S, batch_size, shape, conditioning=conditioning, eta=eta, x_T=x_T, verbose=verbose,
                               unconditional_guidance_scale=unconditional_guidance_scale,
                               unconditional_conditioning=unconditional_conditioning, latents_dir=latents_dir, noises=None,
-                              features_adapter=features_adapter, **kwargs)
+                              features_adapter=features_adapter, mask=mask, x0=x0, mask_noises=mask_noises, **kwargs)
 
     @torch.no_grad()
     def sample_freeinit(self, steps, batch_size, shape, LPF, conditioning=None, eta=0., x_T=None, z_rands=None, noises=None,
